@@ -1,18 +1,24 @@
 """Headline benchmark: active voxels / second through ResUNetBN2C fwd + GCL loss + bwd + SGD step
 (BASELINE.json metric; workload = configs[2], the GCL training step at KITTI 0.3 m, bs = 4 x 7 clouds).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL gradient all-reduce over xGMI)
 
 One "step" = SURVEY.md 8(d)'s t_step on one synthetic batch: host -> device copy of the batch (pinned memory, issued one
 step ahead on a copy stream: what a loader does), SparseTensor / coordinate-map build, kernel maps, 23 sparse convs +
 21 BNs forward, finest-contrastive loss, backward, (gradient all-reduce,) SGD step.  The timed region rotates over
 ``--batches`` (default 4) DISTINCT pre-generated batches, so coordinates, hash tables and cache contents change every
-step.  Rank 0 prints ONE JSON line; `roofline` prices the dominant HIP kernel (per-launch times measured by events on
-the launch stream inside the timed region) against the pipe it actually runs on -- the fp16 MFMA pipe for the fp16x3
-convolutions (every fp32 product = 3 fp16 MFMA terms), HBM for bandwidth-bound kernels; `cpu_baseline` times the C /
-OpenMP restatement of MinkowskiEngine's CPU path (oracle/me_cpu.c, kind "port") on the SAME first batch, all usable
-host cores.
+step.  Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: batches, warm-up, the K timed
+steps.  ``--full`` adds the figures that cost time of their own: `roofline` prices the dominant HIP kernel (per-launch
+times measured by events on the launch stream in the last timed step) against the pipe it actually runs on -- the fp16
+MFMA pipe for the fp16x3 convolutions (every fp32 product = 3 fp16 MFMA terms), HBM for bandwidth-bound kernels;
+`cpu_baseline` times the C / OpenMP restatement of MinkowskiEngine's CPU path (oracle/me_cpu.c, kind "port") on the
+SAME first batch, all usable host cores; `secondary` measures configs[1] / configs[4] in a child process.
+``--dump-outputs DIR`` writes what the last timed step computed (loss, its three parts, the step's voxel count, the
+model's parameters and BatchNorm statistics after its SGD update) as DIR/<name>.npy, after the clock has stopped.  That
+step starts from the seeded initial model and optimizer state (put back with the clock stopped), so that its outputs
+are the same in every run to rounding: the loss backward's float atomics differ in the last bit from run to run, and
+over many steps training amplifies that.
 """
 import argparse
 import itertools
@@ -48,6 +54,12 @@ def parse():
                     help="diagnostic: keep the batches in HBM (no H2D in the step); the line is then NOT the headline")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the configs[1] / configs[4] measurements appended as `secondary` (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline (kernel events in the last timed step), cpu_baseline and secondary; a "
+                         "plain run times the headline only (--no-* switch single figures off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB); that "
+                         "step starts from the seeded initial state, so the outputs repeat from run to run")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--secondary-worker", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args()
@@ -72,24 +84,60 @@ def usable_cores():
     return max(1, min(n, 64))
 
 
-def _gen_batch(job):
+def _gen_sample(job):
     from gcl_amd import synthetic
-    seed, batch_size, group_mode = job
-    return synthetic.make_train_batch(seed, batch_size=batch_size, group_mode=group_mode)
+    seed, group_mode = job
+    return synthetic.make_train_sample(seed, group_mode=group_mode)
 
 
 def make_batches(rank, n, batch_size, group_mode):
     """``n`` distinct synthetic batches of this rank (seeds 100 + rank + 1000 j), generated by worker processes BEFORE
-    anything touches the GPU (the generator is numpy / scipy loader work and is not timed)."""
-    jobs = [(100 + rank + 1000 * j, batch_size, group_mode) for j in range(n)]
-    workers = max(1, min(n, usable_cores() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))))
+    anything touches the GPU (the generator is numpy / scipy loader work and is not timed).  Batch j is
+    synthetic.make_train_batch(seed_j, batch_size, group_mode=group_mode): its samples (each seeded on its own,
+    seed_j * 1000 + b) are one job each, so that all of the batches' samples are generated at once, and are collated here."""
+    from gcl_amd import synthetic
+    seeds = [100 + rank + 1000 * j for j in range(n)]
+    jobs = [(s * 1000 + b, group_mode) for s in seeds for b in range(batch_size)]
+    workers = max(1, min(len(jobs), usable_cores() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))))
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or \
         any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
     if workers == 1 or profiled:       # under rocprofv3 the GPU is initialised before main(): no forked workers then
-        return [_gen_batch(j) for j in jobs]
-    import multiprocessing as mp
-    with mp.get_context("fork").Pool(workers) as pool:
-        return pool.map(_gen_batch, jobs)
+        samples = [_gen_sample(j) for j in jobs]
+    else:
+        import multiprocessing as mp
+        with mp.get_context("fork").Pool(workers) as pool:
+            samples = pool.map(_gen_sample, jobs)
+    return [synthetic.collate_train(samples[j * batch_size:(j + 1) * batch_size]) for j in range(n)]
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, loss, parts, n_vox, model):
+    """What the last timed step computed, as out_dir/<name>.npy: ``loss`` and ``loss_parts`` (pos, finest, neg; float32),
+    ``active_voxels`` (float64) and ``state.<key>`` for every floating-point entry of the model's state dict after the
+    step's SGD update (parameters and BatchNorm running statistics, float32).  Above DUMP_LIMIT_BYTES in all, every array
+    of more than 4096 values is replaced by the same fraction of its flattened values (indices drawn from a seeded
+    generator, sorted), so that the same arguments always dump the same positions."""
+    arrays = {"loss": np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32),
+              "loss_parts": np.array([p.item() for p in parts], dtype=np.float32),
+              "active_voxels": np.array(float(n_vox), dtype=np.float64)}
+    for k, v in model.state_dict().items():
+        if v.is_floating_point():
+            arrays[f"state.{k}"] = v.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = 0.9 * DUMP_LIMIT_BYTES / total
+        rng = np.random.RandomState(0)
+        for k in sorted(arrays):
+            a = arrays[k].reshape(-1)
+            if a.size > 4096:
+                arrays[k] = a[np.sort(rng.choice(a.size, max(4096, int(a.size * frac)), replace=False))]
+        total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) of the last timed step to {out_dir}")
 
 
 def cpu_baseline_worker():
@@ -587,6 +635,8 @@ def main():
         host = [{k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in hb.items()} for hb in host]
     cfg = make_config(batch_size=args.batch_size)
     trainer = FinestContrastiveLossTrainer(cfg, device=dev, ddp=ddp.FlatDDP() if world > 1 else None)
+    # --dump-outputs: the seeded initial state, put back before the last timed step (see the loop)
+    state0 = ({k: v.detach().clone() for k, v in trainer.model.state_dict().items()} if args.dump_outputs else None)
 
     def sync():
         torch.cuda.synchronize()
@@ -624,8 +674,22 @@ def main():
     n_vox = 0
     step_trace = os.environ.get("GCL_BENCH_STEP_TIMES") == "1"     # diagnostic: per-step GPU interval and host time
     step_events, step_host, step_mem = [], [], []
+    kernel_events = args.full and not args.no_kernel_events          # roofline: a --full figure
     for it in range(args.steps):
-        if it == args.steps - 1 and not args.no_kernel_events:
+        if it == args.steps - 1 and state0 is not None:
+            # --dump-outputs: the loss backward's float atomics differ in the last bit from run to run and training
+            # amplifies that over the steps, so the last step starts from the seeded initial parameters, BatchNorm
+            # statistics and optimizer state (momentum buffers rebuilt by the step, as in a first step): its outputs then
+            # depend on its batch and draws alone.  The steps already queued finish on the clock; it is stopped only while
+            # the state is put back (the drain costs the last step its overlap with the previous one: ~1 % on ms_per_step)
+            sync()
+            p0, pc0 = time.perf_counter(), time.thread_time()
+            with torch.no_grad():
+                trainer.model.load_state_dict(state0)       # in place: version bumps void the packed-weight caches
+            trainer.optimizer.state.clear()
+            sync()
+            t0, c0 = t0 + time.perf_counter() - p0, c0 + time.thread_time() - pc0
+        if it == args.steps - 1 and kernel_events:
             ops.PROFILE = []
             plan = getattr(trainer.model, "_plan", None)
             if hasattr(plan, "profile_next"):       # the whole-network plan times its own launches (events in C)
@@ -659,8 +723,11 @@ def main():
     prof, ops.PROFILE = ops.PROFILE, None
     plan = getattr(trainer.model, "_plan", None)
     plan_used = hasattr(plan, "profile_records")
-    if plan_used and not prof and not args.no_kernel_events:
+    if plan_used and not prof and kernel_events:
         prof = plan_profile_records(plan, ops.PRECISION)
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, loss, parts, n, trainer.model)
     for name, (w, c, k) in getattr(trainer, "_helper_times", {}).items():
         if k:
             log(f"helper thread '{name}': {w / k * 1e3:.2f} ms wall, {c / k * 1e3:.2f} ms CPU per step ({k} steps)")
@@ -696,7 +763,7 @@ def main():
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32" if ops.PRECISION != "bf16x3" else "f32 via bf16x3 split (reduced: ~1.5e-5)",
-        "arithmetic": ops.PRECISION, "data": "synthetic",
+        "arithmetic": ops.PRECISION, "data": "synthetic", "full": args.full,
         "config": {"workload": "configs[2]: GCL training step (finest_contrastive_loss), ResUNetBN2C-32 conv1 k=5, "
                                f"KITTI-shaped ray-cast clouds @0.3 m, bs={args.batch_size} x 7 clouds per GPU, "
                                f"positive groups '{args.group_mode}'",
@@ -717,9 +784,9 @@ def main():
             raise SystemExit(f"--gpus {args.gpus}: the collective ran on {ranks['rccl_ranks']} rank(s) over "
                              f"'{ranks['backend']}' (expected {args.gpus} over '{want}')")
         out["ranks"] = ranks
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         out["secondary"] = secondary_in_child()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(out), flush=True)
     if world > 1:

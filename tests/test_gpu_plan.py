@@ -450,6 +450,41 @@ def test_bench_starts_its_own_ranks():
         assert r.returncode != 0 and "refusing" in r.stderr and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run prints one JSON line with the headline keys, times exactly --steps steps and measures none of
+    the --full figures (roofline, cpu_baseline, secondary); --dump-outputs writes the last timed step's loss (the line's own
+    `config.loss`), its parts and the model's state after the update as float arrays.  A second run with the same arguments
+    has the same inputs exactly and, the dumped step starting from the seeded initial state, the same outputs up to the
+    rounding of the loss backward's float atomics."""
+    out = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GCL_BENCH_SINGLE_DEVICE")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batches", "2",
+           "--dump-outputs"]
+    r = subprocess.run(cmd + [str(out)], env=env, capture_output=True, text=True, timeout=400, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    r2 = subprocess.run(cmd + [str(tmp_path / "again")], env=env, capture_output=True, text=True, timeout=400, cwd=ROOT)
+    assert r2.returncode == 0, r2.stdout[-3000:] + r2.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    rec = json.loads(lines[0])
+    assert all(k in rec for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["full"] is False
+    assert rec["roofline"] is None and "secondary" not in rec and "cpu_baseline" not in rec
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert {"loss.npy", "loss_parts.npy", "active_voxels.npy", "state.conv1.kernel.npy"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert float(files["loss.npy"]) == rec["config"]["loss"]
+    # the last of 2 + 3 steps over two batches in rotation ran on the first batch
+    assert float(files["active_voxels.npy"]) == rec["config"]["voxels_per_batch_rank0"][0]
+    assert all(np.isfinite(a).all() for a in files.values())
+    rec2 = json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec2["config"]["voxels_per_batch_rank0"] == rec["config"]["voxels_per_batch_rank0"]
+    again = {p.name: np.load(p) for p in (tmp_path / "again").iterdir()}
+    assert again.keys() == files.keys() and float(again["active_voxels.npy"]) == float(files["active_voxels.npy"])
+    bad = [k for k in files if not np.allclose(again[k], files[k], rtol=1e-5, atol=1e-6)]
+    assert not bad, [(k, float(np.abs(again[k].astype(np.float64) - files[k]).max())) for k in bad[:5]]
+
+
 def test_frozen_parameter_keeps_the_step_off_the_plan():
     """with one convolution frozen (requires_grad=False, fine-tuning) a training step must not
     go through the plan -- it writes every record's gradient through raw pointers and the trainer seats p.grad for all

@@ -214,6 +214,38 @@ def test_counter_figures_are_quoted_only_for_the_sources_they_were_collected_on(
         assert ("collected on these kernel sources" in r["note"]) == quoted
 
 
+def test_bench_dump_outputs_are_float_arrays_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: what the last timed step computed (loss, its three parts, the voxel count, the model's state
+    after the update) as <name>.npy in float32 / float64 within 64 MB; over the budget, a seeded sample of each large array
+    that takes the same positions in every run."""
+    import importlib.util
+    from gcl_amd.model import load_model
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    model = load_model("ResUNetBN2C")(1, 32, bn_momentum=0.05, normalize_feature=True, conv1_kernel_size=5, D=3)
+    loss, parts = torch.tensor(1.5), (torch.tensor(0.5), torch.tensor(0.25), torch.tensor(0.75))
+    bench.dump_outputs(str(tmp_path / "all"), loss, parts, 530321, model)
+    files = {p.name: np.load(p) for p in (tmp_path / "all").iterdir()}
+    sd = {k: v for k, v in model.state_dict().items() if v.is_floating_point()}
+    assert set(files) == {"loss.npy", "loss_parts.npy", "active_voxels.npy"} | {f"state.{k}.npy" for k in sd}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= bench.DUMP_LIMIT_BYTES == 64 * 1000 * 1000
+    assert float(files["loss.npy"]) == 1.5 and files["loss_parts.npy"].tolist() == [0.5, 0.25, 0.75]
+    assert float(files["active_voxels.npy"]) == 530321
+    assert all(np.array_equal(files[f"state.{k}.npy"], v.numpy()) for k, v in sd.items())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4_000_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, parts, 530321, model)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert a.keys() == files.keys() and sum(x.nbytes for x in a.values()) <= 4_000_000
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    k = "state.block4.conv1.kernel.npy"
+    assert a[k].size < files[k].size and np.isin(a[k], files[k]).all()
+
+
 def test_registration_stage_views_and_host_copies():
     """Host pieces of the one-call registration path (gcl_amd/scripts/SC2_PCR.py) and of the eval loop's copies: the stage
     views carve typed tensors out of ONE byte buffer at the recorded offsets; host_to_device is the identity off the GPU."""

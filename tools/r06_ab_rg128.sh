@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box alternation: range-grouped 128 x 128 weight gradient on / off (GCL_DW_RG128), bench headline only
-A="--steps 30 --warmup 10 --no-cpu-baseline --no-secondary"
+A="--steps 30 --warmup 10 --full --no-cpu-baseline --no-secondary"
 for i in 1 2; do
   for v in 1 0; do
     GCL_DW_RG128=$v python3 bench.py $A 2>/dev/null | python3 -c "

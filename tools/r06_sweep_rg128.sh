@@ -1,5 +1,5 @@
 #!/bin/bash
-A="--steps 30 --warmup 10 --no-cpu-baseline --no-secondary"
+A="--steps 30 --warmup 10 --full --no-cpu-baseline --no-secondary"
 for rep in 1 2; do
 for kb in 0 4400 8800 17600; do
   if [ $kb = 0 ]; then export GCL_DW_RG128=0; else export GCL_DW_RG128=1; export GCL_DW_RG128_KB=$kb; fi

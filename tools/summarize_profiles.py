@@ -2,6 +2,9 @@
 
   gpurun_out/prof_final/*/…_kernel_stats.csv           (rocprofv3 --kernel-trace --stats -- python3 bench.py …)
   gpurun_out/pmc_final{1,2,3}/*/…_counter_collection.csv (separate --pmc passes: SQ_*, FETCH_SIZE, WRITE_SIZE)
+
+Usage: python tools/summarize_profiles.py TAG STEPS [OUT], OUT = the directory `tools/collect_profiles.sh TAG OUT`
+wrote (the CSVs are read from OUT instead of the folder above).
 """
 import collections
 import csv
@@ -16,6 +19,8 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r01_final"
 n_steps_arg = int(sys.argv[2]) if len(sys.argv) > 2 else 5          # steps + warm-up of the profiled command
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+if len(sys.argv) > 3:           # the OUT directory of tools/collect_profiles.sh
+    G = os.path.abspath(sys.argv[3])
 
 
 def short(name):
