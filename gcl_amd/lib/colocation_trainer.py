@@ -32,6 +32,7 @@ DEFAULT_CONFIG = dict(
     pos_thresh=0.1, neg_thresh=1.4, finest_thresh=0.2, pos_weight=1.0, neg_weight=1.0, finest_weight=1.0,
     square_loss=True, block_finest_gradient=False, use_hard_negative=True, use_pair_group_positive_loss=False,
     use_group_circle_loss=False, safe_radius=0.75, voxel_size=0.3,
+    triplet_num_pos=256, triplet_num_hn=512, triplet_num_rand=1024,      # config.py:71-73 (the pair trainers, lib/trainer.py)
 )
 
 

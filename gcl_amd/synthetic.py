@@ -313,6 +313,42 @@ def make_eval_pair(seed, voxel_size=0.3, baseline=10.0, n_boxes=60):
     return out
 
 
+def pair_correspondences(coords0, coords1, T_gt, voxel_size, search_mult=1.5):
+    """int64 [P, 2]: every (row of cloud 0, row of cloud 1) whose voxel centres lie within ``voxel_size * search_mult``
+    of each other once cloud 0 is moved by ``T_gt`` (the matching of lib/data_loaders.py:26-79's datasets, with scipy's
+    cKDTree in place of open3d); sorted by row of cloud 0, then row of cloud 1.  One row may have several partners."""
+    from scipy.spatial import cKDTree
+    T = np.asarray(T_gt, dtype=np.float64)
+    c0 = (np.asarray(coords0, dtype=np.float64) + 0.5) * voxel_size
+    c1 = (np.asarray(coords1, dtype=np.float64) + 0.5) * voxel_size
+    hits = cKDTree(c1).query_ball_point(c0 @ T[:3, :3].T + T[:3, 3], voxel_size * search_mult)
+    rows = [(i, j) for i, h in enumerate(hits) for j in sorted(h)]
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+
+
+def make_train_pair(seed, voxel_size=0.3, baseline=10.0, n_boxes=60, search_mult=1.5, max_points=None):
+    """``collate_pair_fn``-shaped training dict (lib/data_loaders.py:26-79) for one pair of clouds of one scene:
+    ``sinput0_C / _F``, ``sinput1_C / _F``, ``correspondences`` (int64 [P, 2], see ``pair_correspondences``;
+    ``search_mult`` = positive_pair_search_voxel_size_multiplier), ``T_gt``, ``len_batch``, ``pcd0 / pcd1``.
+    ``max_points`` keeps only that many voxels of each cloud, the ones nearest to the point half way between the sensors
+    (small overlapping clouds for tests)."""
+    out = make_eval_pair(seed, voxel_size, baseline, n_boxes)
+    if max_points is not None:          # the voxels nearest to the point half way between the two sensors
+        for k, x_mid in ((0, 0.5 * baseline), (1, -0.5 * baseline)):
+            xyz = out[f"pcd{k}"][0].numpy()
+            if len(xyz) > max_points:
+                d = np.linalg.norm(xyz - np.array([x_mid, 0.0, 0.0]), axis=1)
+                sel = np.sort(np.argsort(d, kind="stable")[:max_points])
+                out[f"pcd{k}"] = (out[f"pcd{k}"][0][sel],)
+                out[f"sinput{k}_C"] = out[f"sinput{k}_C"][sel].contiguous()
+                out[f"sinput{k}_F"] = out[f"sinput{k}_F"][sel].contiguous()
+        out["len_batch"] = [[len(out["sinput0_C"]), len(out["sinput1_C"])]]
+    pairs = pair_correspondences(out["sinput0_C"][:, 1:].numpy(), out["sinput1_C"][:, 1:].numpy(), out["T_gt"].numpy(),
+                                 voxel_size, search_mult)
+    out["correspondences"] = torch.from_numpy(pairs)
+    return out
+
+
 def make_twin_eval_pair(seed, inlier_share=0.3, voxel_size=0.3, shift_voxels=(16, 8, 0), gap_voxels=16, n_boxes=60):
     """An eval pair (keys of ``make_eval_pair``) with a CONTROLLED share of true correspondences, for timing the eval loop on
     registrations that have something to find with an UNTRAINED network (bench.py ``secondary``, configs[4]).

@@ -746,6 +746,55 @@ int gcl_plan_profile_read(void* plan, double* records_host, int32_t max_records)
  * (model/resunet.py:165-171); scratch: double[gcl_bn_scratch_len(n, c)]. */
 int gcl_col_sum(const float* x, int64_t n, int32_t c, double* scratch, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pair-trainer losses (lib/trainer.py: ContrastiveLossTrainer :198-276, TripletLossTrainer :545-592,
+ * HardestTripletLossTrainer :671-744).  F0 [n0, c] and F1 [n1, c] are the features of the two clouds, c <= 64; a
+ * "pair" is int64 (row of F0, row of F1).  Nothing here waits for the host; a row id outside its cloud drops its
+ * triplet / pair instead of being dereferenced.
+ *
+ * Positional keys (util/misc.py:43-55): key(r0, r1) = r0 + r1 * seed in wrapping int64.
+ * gcl_pair_key_table fills `table` (int64 [cap, 2], cap a power of two >= max(64, 2 n_pos)) with the keys of the
+ * n_pos positive pairs (duplicates allowed, n_pos = 0 allowed).  gcl_pair_key_mask probes m candidates:
+ *   b == NULL   candidate t is the pair ap[t] itself;
+ *   b != NULL   candidate t is the row of column `col` of ap[t] paired with rb = b[b_arg[t]] (b_arg NULL: b[t]) on the
+ *               other side, nb = rows in b; b_out (optional) receives rb.
+ * keep[t] = 1 iff the candidate's key is not a positive pair's (np.isin negated, lib/trainer.py:211, :583, :716-719).
+ * ---------------------------------------------------------------------------------------------- */
+int gcl_pair_key_table(const int64_t* pos_pairs, int64_t n_pos, int64_t seed, int64_t* table, int64_t cap, void* stream);
+int gcl_pair_key_mask(const int64_t* ap, int32_t col, const int64_t* b, const int32_t* b_arg, int64_t nb, int32_t m,
+                      int64_t seed, const int64_t* table, int64_t cap, int64_t* b_out, uint8_t* keep, void* stream);
+/* Triplet terms.  Triplet t is the positive pair ap[t] with the negative row neg[t] and tag[t] = side | set << 1:
+ *   side 0  anchor F0[ap[t][0]], positive F1[ap[t][1]], negative F1[neg[t]]
+ *   side 1  anchor F1[ap[t][1]], positive F0[ap[t][0]], negative F0[neg[t]]
+ * term = relu(d(anchor, positive) + margin - d(anchor, negative)), d(x, y) = sqrt(|x - y|^2 + 1e-7) (lib/metrics.py:25).
+ * keep (optional uint8 [m]) selects the triplets of the mean.  work: float [gcl_triplet_scratch_len(m)], kept by the
+ * caller for the backward pass.  out: float [GCL_TRIPLET_OUT]:
+ *   out[0] mean term over the kept triplets (NaN for none), out[1] their number, then for every set s = 0, 1, 2 at
+ *   out[2 + 6 s]: kept, all, mean d_pos over kept, mean d_neg over kept, mean d_pos over all, mean d_neg over all.
+ * fp64 sums in a fixed order in one workgroup: the forward value is bitwise reproducible.
+ * Backward: g = device pointer to the gradient of out[0]; df0 / df1 are caller-zeroed and receive float atomics. */
+#define GCL_TRIPLET_OUT 20
+int64_t gcl_triplet_scratch_len(int32_t m);
+int gcl_triplet_fwd(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* ap,
+                    const int64_t* neg, const uint8_t* tag, const uint8_t* keep, int32_t m, float margin, float* work,
+                    float* out, void* stream);
+int gcl_triplet_bwd(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* ap,
+                    const int64_t* neg, const uint8_t* tag, const uint8_t* keep, int32_t m, const float* work,
+                    const float* out, const float* g, float* df0, float* df1, void* stream);
+/* Pair terms over pairs [m, 2] with d2 = |F0[a] - F1[b]|^2; out = {mean term over the kept pairs (NaN for none), their
+ * number}; work: float [gcl_pair_terms_scratch_len(m)].  Same backward convention; GCL_PAIR_DIST has no backward pass. */
+#define GCL_PAIR_SQ 0        /* d2                                   lib/trainer.py:266 */
+#define GCL_PAIR_SQ_POS 1    /* relu(d2 - thresh)                    :459 */
+#define GCL_PAIR_NEG 2       /* relu(thresh - sqrt(d2 + eps))^2      :269-270 (eps 1e-4) and :460-461 (eps 1e-7) */
+#define GCL_PAIR_DIST 3      /* sqrt(d2 + eps)                       :573 (a statistic) */
+int64_t gcl_pair_terms_scratch_len(int32_t m);
+int gcl_pair_terms_fwd(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* pairs,
+                       const uint8_t* keep, int32_t m, int32_t mode, float thresh, float eps, float* work, float* out,
+                       void* stream);
+int gcl_pair_terms_bwd(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* pairs,
+                       const uint8_t* keep, int32_t m, int32_t mode, float thresh, float eps, const float* work,
+                       const float* out, const float* g, float* df0, float* df1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
