@@ -399,24 +399,35 @@ def test_inference_launch_with_offset_groups(cin, cout):
         assert torch.equal(tall[:na], ya) and torch.equal(tall[na:], yb)
 
 
+# parameter sets of the test below that reach the wide column blocks: (cin, cout, n, use_planes) -> (extent of the cloud,
+# NB the launch dispatches).  Since the 256-workgroup rule of conv_fwd_nb every launch of up to 8064 rows runs NB = 1.
+LDS_DMA_WIDE = {(128, 256, 14000, True): (24, 2), (256, 256, 14000, True): (24, 2), (128, 128, 30000, True): (32, 2),
+                (128, 256, 30000, True): (32, 4), (64, 256, 14000, False): (24, 2), (64, 64, 60000, False): (40, 2),
+                (64, 128, 60000, False): (40, 4)}
+
+
 @pytest.mark.parametrize("cin,cout,n,use_planes", [(128, 128, 3000, True), (256, 256, 1500, True), (128, 256, 700, True),
                                                    (256, 128, 129, True), (128, 128, 1, True), (128, 64, 2500, True),
                                                    (256, 64, 900, True), (128, 32, 600, True), (64, 64, 3000, False),
                                                    (32, 32, 2000, False), (32, 64, 700, False), (64, 128, 1500, False),
-                                                   (96, 64, 300, False), (64, 32, 1, False), (128, 128, 500, False)])
+                                                   (96, 64, 300, False), (64, 32, 1, False), (128, 128, 500, False)]
+                         + list(LDS_DMA_WIDE))
 def test_lds_dma_forward_kernel_is_bitwise_the_register_staged_kernel(cin, cout, n, use_planes):
     """k_conv_fwd_dma (operands staged by `buffer_load ... lds`: no staging registers, no ds_write; missing neighbours read
     zero through the buffer resource; flag GCL_CONV_DMA) against k_conv_fwd_split (flag GCL_CONV_NO_DMA), on plane images and
     on fp32 rows.  Same products added in the same order: y and the BatchNorm column-sum partials are equal bit for bit, with
-    and without the fused epilogue, for every column-block width (NB = 4, 2, 1) and for ragged / single-row launches."""
+    and without the fused epilogue, for every column-block width (NB = 4, 2, 1: the sets of LDS_DMA_WIDE reach 2 and 4, every
+    other set runs NB = 1, and the test asserts which) and for ragged / single-row launches."""
     from gcl_amd import _lib
     import gcl_amd.MinkowskiEngine as ME
     lib = _lib.load()
-    C = random_cloud(cin + n, n=n, extent=14, batch=1) if n > 1 else np.zeros((1, 4), np.int32)
+    extent, nb_claim = LDS_DMA_WIDE.get((cin, cout, n, use_planes), (14, 1))
+    C = random_cloud(cin + n, n=n, extent=extent, batch=1) if n > 1 else np.zeros((1, 4), np.int32)
     mgr = make_mgr(C)
     km = mgr.get_kernel_map(1, 3, 1)
     tbl, order, mask = km.sorted_table()
     n_out, K = len(C), 27
+    assert lib.gcl_conv_fwd_nb(n_out, cout, 4) == nb_claim, (n_out, cout, nb_claim)
     g = torch.Generator().manual_seed(n)
     with torch.cuda.device(DEV):
         x = torch.randn(n_out, cin, generator=g).to(DEV)
