@@ -47,3 +47,30 @@ def pdist_min(A, B, dist_type="L2", rows_a=None, rows_b=None):
                                  1 if dist_type == "L2" else 0, _lib.ptr(scratch), _lib.ptr(dmin), _lib.ptr(arg),
                                  _lib.stream()), "gcl_nn_rowmin")
     return dmin, arg
+
+
+def nn3_min(Q, P, feats=None):
+    """Nearest row of ``P`` [n, 3] for every row of ``Q`` [m, 3]: ``(d2min float32 [m], argmin int32 [m])`` on the device,
+    squared distances in the difference form, ties -> lowest index (generalization_ETH/evaluate.py:110-122: pytorch3d's
+    knn_points with K = 1).  With ``feats`` [n, c] the same native call also returns ``desc = feats[argmin]`` [m, c]."""
+    lib = _lib.require_gpu()
+    Q, P = Q.detach().to(torch.float32).contiguous(), P.detach().to(torch.float32).contiguous()
+    if Q.dim() != 2 or P.dim() != 2 or Q.shape[1] != 3 or P.shape[1] != 3:
+        raise ValueError(f"nn3_min takes [m, 3] and [n, 3] points, got {tuple(Q.shape)} and {tuple(P.shape)}")
+    m, n = Q.shape[0], P.shape[0]
+    d2 = torch.empty(m, dtype=torch.float32, device=Q.device)
+    arg = torch.empty(m, dtype=torch.int32, device=Q.device)
+    desc, c = None, 0
+    if feats is not None:
+        feats = feats.detach().contiguous()
+        if feats.dim() != 2 or feats.shape[0] != n:
+            raise ValueError(f"nn3_min: feats must be [n = {n}, c], got {tuple(feats.shape)}")
+        c = feats.shape[1]
+        desc = torch.empty((m, c), dtype=torch.float32, device=Q.device)
+    if m == 0:
+        return (d2, arg) if feats is None else (d2, arg, desc)
+    ns = lib.gcl_nn3_scratch_len(m, n)
+    scratch = torch.empty(ns, dtype=torch.int32, device=Q.device) if ns else None
+    _lib.check(lib.gcl_nn3_rowmin(_lib.ptr(Q), m, _lib.ptr(P), n, _lib.ptr(feats, torch.float32), c, _lib.ptr(scratch),
+                                  _lib.ptr(d2), _lib.ptr(arg), _lib.ptr(desc), _lib.stream()), "gcl_nn3_rowmin")
+    return (d2, arg) if feats is None else (d2, arg, desc)

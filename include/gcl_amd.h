@@ -22,6 +22,8 @@
  *   find_nn_gpu                                      lib/eval.py:18-48  -> gcl_nn_rowmin
  *   Matcher.estimator (SC2-PCR)                      scripts/test_kitti.py:172-180, scripts/SC2_PCR/SC2_PCR.py
  *        -> gcl_nn_rowmin, gcl_sc2_*
+ *   find_nearest_voxel_feature, calculate_M, inlier ratio   generalization_ETH/evaluate.py:63-77, :110-122, :160-169
+ *        -> gcl_nn3_rowmin, gcl_nn_rowmin, gcl_mutual_match
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless its name ends in _host;
@@ -511,6 +513,29 @@ int gcl_circle_group_bwd(const float* f, int32_t c, const int64_t* index, const 
 int64_t gcl_nn_rowmin_scratch_len(int32_t ma, int32_t mb);
 int gcl_nn_rowmin(const float* a, const int64_t* rows_a, int32_t ma, const float* b, const int64_t* rows_b,
                   int32_t mb, int32_t c, int32_t l2, int32_t* scratch, float* dmin, int32_t* argmin, void* stream);
+
+/* 3-D nearest point (generalization_ETH/evaluate.py:110-122, find_nearest_voxel_feature): for every query q[i]
+ * (float [m, 3]) the row j of p (float [n, 3]) that minimises (qx - px)^2 + (qy - py)^2 + (qz - pz)^2, evaluated in that
+ * DIFFERENCE form in fp32 (never |q|^2 + |p|^2 - 2 q.p, which loses 5 cm voxels at outdoor coordinates); exact search,
+ * ties -> lowest j.  argmin int32 [m]; d2min float [m] (the squared distance) may be NULL.  When feat (float [n, c], any
+ * c >= 1) and desc (float [m, c]) are given -- both or neither -- the same call writes desc[i] = feat[argmin[i]].
+ * Runs as (256-query tiles) x (chunks of p) workgroups, then a merge over the chunks when there are several;
+ * scratch: int32[gcl_nn3_scratch_len(m, n)] (0 for a single chunk: scratch may then be NULL).
+ * m == 0 returns 0 without a launch; n <= 0 is an argument error. */
+int64_t gcl_nn3_scratch_len(int32_t m, int32_t n);
+int gcl_nn3_rowmin(const float* q, int32_t m, const float* p, int32_t n, const float* feat, int32_t c, int32_t* scratch,
+                   float* d2min, int32_t* argmin, float* desc, void* stream);
+/* Mutual filter and inlier count of one fragment pair (generalization_ETH/evaluate.py:63-77 calculate_M, :160-169):
+ * nn01 int32 [m0] = nearest target of every source, nn10 int32 [m1] = nearest source of every target.  pairs
+ * (int32 [m0, 2]) receives every (i, nn01[i]) with nn10[nn01[i]] == i, densely packed in ascending i (the same list
+ * on every run; rows from stats[0] on are left as they were); an entry of nn01 outside [0, m1) is not mutual and is never
+ * dereferenced.  stats int32 [2]: [0] = number of mutual pairs, [1] = how many of them have
+ * |kp0[i] - (R kp1[j] + t)| < tau when T (float [12] on the device, row-major [R | t]) is given -- kp0 float [m0, 3] and
+ * kp1 float [m1, 3] are then required; the TARGET keypoints are moved, as the reference does with gtTrans -- else 0.
+ * `stats` is any int32 pair of the caller's: the pairs of a scene fill one [P, 2] table that is read once.
+ * m0 == 0 writes stats = {0, 0}. */
+int gcl_mutual_match(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32_t m1, const float* kp0, const float* kp1,
+                     const float* T, float tau, int32_t* pairs, int32_t* stats, void* stream);
 
 /* keep[r] = (sel1[r] != sel2[arg[r]]) && the pair {sel1[r], sel2[arg[r]]} shares no positive group
  * (equivalent to the reference's `~np.isin(_neg_hash(...), index_hash)` :521-529: the symmetric key is
