@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GCL_LIB_PATH", os.path.join(CSRC, "libgcl_hip.so"))   # override: diagnostic builds only
-SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip"]
+SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip", "ransac.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gcl_amd.h")
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -157,6 +157,10 @@ SIGNATURES = {
     "gcl_sc2_seed_knn": (_i32, [_vp, _vp, _i32, _vp, _i32, _f32, _i32, _vp, _vp, _vp]),
     "gcl_sc2_seed_trans": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _f32, _vp, _vp, _vp]),
     "gcl_sc2_refine": (_i32, [_vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _vp]),
+    "gcl_ransac_scratch_bytes": (_i64, [_i32, _i32]),
+    "gcl_ransac_default_chunk": (_i32, []),
+    "gcl_ransac_register": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _f32, _i32, _f32, ctypes.c_uint64, _i32, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
     "gcl_group_loss_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
     "gcl_group_loss_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcl_circle_group_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -209,7 +213,7 @@ def source_hash():
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into csrc/libgcl_hip.so (in-tree, so it travels to the GPU box)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "common.h"), HEADER]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kabsch.h"), HEADER]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH

@@ -204,8 +204,9 @@ def evaluate_scene(fragments, keypoints, gt_log, model=None, descriptors=None, v
     reference are DEFINED here: a pair with zero mutual matches has ratio 0, and a scene with zero correct matches has
     ``ave_num_inliers`` 0.0 (a scene without any ground-truth pair has recall NaN, as numpy's 0 / 0 there).
 
-    With a ``Matcher`` (scripts/SC2_PCR.py) every ground-truth pair is also registered by SC2-PCR on its keypoints and
-    descriptors -- the GPU stand-in for open3d's RANSAC (:171-186), which is not built -- and ``pred_log`` holds
+    With a ``matcher`` every ground-truth pair is also registered on its keypoints and descriptors -- by open3d's
+    feature-matching RANSAC as the reference does (:171-186) with ``gcl_amd.lib.ransac.FeatureRansac.eth()``, or by SC2-PCR
+    with a ``Matcher`` (scripts/SC2_PCR.py) -- and ``pred_log`` holds
     ``(id1, id2, inverse of the estimate as 4x4 float64)`` in the reference's log order (:188-196); the estimates leave the
     device in one further copy.
     """

@@ -22,6 +22,9 @@
  *   find_nn_gpu                                      lib/eval.py:18-48  -> gcl_nn_rowmin
  *   Matcher.estimator (SC2-PCR)                      scripts/test_kitti.py:172-180, scripts/SC2_PCR/SC2_PCR.py
  *        -> gcl_nn_rowmin, gcl_sc2_*
+ *   open3d registration_ransac_based_on_feature_matching   scripts/test_kitti.py:171-178,
+ *                                                    generalization_ETH/evaluate.py:171-186
+ *        -> gcl_nn_rowmin, gcl_ransac_register
  *   find_nearest_voxel_feature, calculate_M, inlier ratio   generalization_ETH/evaluate.py:63-77, :110-122, :160-169
  *        -> gcl_nn3_rowmin, gcl_nn_rowmin, gcl_mutual_match
  *
@@ -618,6 +621,34 @@ int gcl_sc2_seed_trans(const float* src, const float* tgt, int32_t n, const int3
                        float* fitness, void* stream);
 int gcl_sc2_refine(const float* src, const float* tgt, int32_t n, float thr, int32_t iterations, double* partial,
                    int32_t* state, float* T, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Feature-matching RANSAC registration for ONE pair (open3d's registration_ransac_based_on_feature_matching on the
+ * correspondences src[i] <-> tgt[i], float [n, 3]; callers scripts/test_kitti.py:171-178 -- ransac_n 4, edge-length
+ * checker 0.9, distance checker and inlier distance one voxel, 4 000 000 iterations -- and
+ * generalization_ETH/evaluate.py:171-186 -- ransac_n 3, 0.05, 50 000).  One call enqueues everything; nothing is read back.
+ * Hypothesis h in [0, max_iteration) is a function of (seed, h) alone (a counter generator in place of open3d's
+ * std::mt19937; csrc/ransac.hip states the draw), so equal inputs give bitwise equal outputs:
+ *   draw ransac_n indices (repeated index: status -3)  ->  CorrespondenceCheckerBasedOnEdgeLength(edge_similarity) on the
+ *   sample (-1; <= 0: off)  ->  TransformationEstimationPointToPoint(false) on the sample, fp64 Kabsch, fp32 [R | t]  ->
+ *   CorrespondenceCheckerBasedOnDistance(check_distance) on the sample (-2; <= 0: off)  ->  inlier count (|R s + t - t'| <
+ *   max_corr_distance, fp32) and sum of squared inlier distances over all n (status = count).
+ * Winner: highest count, then lower sum (IsBetterRANSACThan), then lower h.  Hypotheses are processed in chunks of `chunk`
+ * consecutive ids (0 = gcl_ransac_default_chunk(); values above 2^20 are taken as 2^20); after each chunk, with
+ * 0 < confidence < 1, limit = ceil(log(1 - confidence) / log(1 - (best count / n)^ransac_n)) and a later chunk whose first
+ * id is >= limit does nothing (its hypotheses: status -4) -- a word on the device, no host round trip.  With the stop off
+ * (confidence outside (0, 1)) the result does not depend on `chunk`.
+ * Outputs: trans16 float[16] (row-major [4, 4]); info int32[4] = {winning h or -1, its inlier count, hypotheses covered by
+ * executed chunks, hypotheses scored}; fit float[2] = {count / n, sqrt(sum / count)}; labels float[n] (optional): 1 for the
+ * winner's inliers; hyp_status int32[max_iteration] (optional): the status above, a diagnostic and test hook.  Nothing scored
+ * or best count 0: identity, info[0] = -1, fit = {0, 0}.  scratch: gcl_ransac_scratch_bytes(n, chunk) bytes (ransac_n <= n <= 2^24).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t gcl_ransac_scratch_bytes(int32_t n, int32_t chunk);
+int32_t gcl_ransac_default_chunk(void);
+int gcl_ransac_register(const float* src, const float* tgt, int32_t n, int32_t ransac_n, float edge_similarity,
+                        float check_distance, float max_corr_distance, int32_t max_iteration, float confidence,
+                        uint64_t seed, int32_t chunk, void* scratch, float* trans16, int32_t* info, float* fit,
+                        float* labels, int32_t* hyp_status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native step runtime (round 3): ONE call enqueues a whole pass.
