@@ -490,6 +490,30 @@ struct ConvEpi {
   int residual_ld;          // row pitch of `residual` in floats (a column slice of a wider tensor), 0 = cout
 };
 
+// The residual / gate operand of a wave's NB x 16 output elements, fetched in ONE burst before the first store of the
+// epilogue: stores count on vmcnt as well, so a load between two stores makes its consumer wait for every earlier store too
+// (a load + a full wait per row was 16 * NB dependent trips to memory per wave).  orows[r] < 0: the row does not exist --
+// `row_any` (one that does) is read instead and the caller drops the value.  A lane reads exactly the elements it writes
+// later, so `rbase` may point into the output itself.
+template <int NB>
+__device__ __forceinline__ void epi_fetch_rows(float (&rsd)[NB][16], const int (&orows)[16], int row_any,
+                                               const float* rbase, long long rld) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    int row = orows[r] >= 0 ? orows[r] : row_any;
+    // one row's address at a time: left alone, the compiler forms all sixteen first (32 registers more, spills at NB = 2)
+    asm volatile("" : "+v"(row) : : "memory");
+    const float* rp = rbase + (long long)row * rld;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) rsd[b][r] = rp[b * 32];
+  }
+  // consume the loads HERE, all of them in flight: nothing after this waits on them between two stores
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(rsd[b][r]));
+}
+
 // Epilogue of the four-wave forward kernels (k_conv_fwd_split, k_conv_fwd_dma): un-scale, bias, optional fused inference
 // epilogue, scatter to the original row order, per-workgroup column sums for the BatchNorm that follows.  `tiles` = the
 // workgroup's four wave-private 32 x 32-float A tiles (idle by now: scratch for the column sums).
@@ -508,23 +532,48 @@ __device__ __forceinline__ void conv_fwd_epilogue(f32x16 (&acc)[NB], float* tile
   // column sums of this wave's 32 rows go to its own (now idle) A tile; wave 0 adds the four waves in order and writes
   // ONE partial per workgroup (128 rows) for the BatchNorm that follows (saves its statistics pass over Y)
   float* const ssc = tiles + w * (32 * 32);   // wave w's tile; tiles are 32 x 32 floats apart
+  // every load of the epilogue is issued HERE, before the first store (epi_fetch_rows): per column the bias and the scale,
+  // per element the residual / gate operand, NB x 16 registers (the cross accumulators are dead by now)
+  int orows[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) orows[r] = __shfl(orow_l, (r & 3) + 8 * (r >> 2) + 4 * h);
+  float bvs[NB], cscs[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int col = (nb0 + b) * 32 + i;
-    float bvv = bias ? bias[col] : 0.f;
-    float csc = (EPI && epi.col_scale) ? epi.col_scale[col] * out_scale : out_scale;
-    // consume the (conditional) loads HERE: otherwise every store below waits for all earlier stores (vmcnt(0))
-    asm volatile("v_mov_b32 %0, %1" : "=v"(bvv) : "v"(bvv));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(csc) : "v"(csc));
+    bvs[b] = bias ? bias[col] : 0.f;
+    cscs[b] = (EPI && epi.col_scale) ? epi.col_scale[col] * out_scale : out_scale;
+  }
+  const bool has_rsd = EPI && epi.residual;
+  float rsd[EPI ? NB : 1][16];      // read only where has_rsd, and then only for rows that exist (none in an inactive wave)
+  if (has_rsd && active) {
+    const long long rld = epi.residual_ld ? epi.residual_ld : cout;
+    const int row_any = __shfl(orow_l, 0);      // the wave's first row: it exists whenever the wave is active
+    const float* const rbase = epi.residual + nb0 * 32 + i;
+    // the accumulators are final HERE: otherwise fold_cross is sunk into the row loop and its NB x 16 cross terms stay live
+    // beside the NB x 16 values fetched below
+#pragma unroll
+    for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(acc[b]));
+    epi_fetch_rows<(EPI ? NB : 1)>(rsd, orows, row_any, rbase, rld);
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    asm volatile("v_mov_b32 %0, %1" : "=v"(bvs[b]) : "v"(bvs[b]));
+    asm volatile("v_mov_b32 %0, %1" : "=v"(cscs[b]) : "v"(cscs[b]));
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const int col = (nb0 + b) * 32 + i;
+    const float bvv = bvs[b], csc = cscs[b];
     float s1 = 0.f, s2 = 0.f, lo = 3.0e38f, hi = -3.0e38f;      // column sum, sum of squares, minimum, maximum
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int orow = __shfl(orow_l, (r & 3) + 8 * (r >> 2) + 4 * h);
+      const int orow = orows[r];
       if (orow >= 0) {
         float v = acc[b][r] * csc + bvv;
-        if (EPI && epi.residual) {
-          const float rsd = epi.residual[(long long)orow * (epi.residual_ld ? epi.residual_ld : cout) + col];
-          v = epi.relu == 2 ? (rsd > 0.f ? v : 0.f) : v + rsd;      // relu == 2: threshold_backward, pass v where residual > 0
+        if (has_rsd) {
+          const float rs = rsd[EPI ? b : 0][r];
+          v = epi.relu == 2 ? (rs > 0.f ? v : 0.f) : v + rs;      // relu == 2: threshold_backward, pass v where residual > 0
         }
         if (EPI && epi.relu == 1) v = fmaxf(v, 0.f);
         Y[(long long)orow * cout + col] = v;
@@ -1143,16 +1192,31 @@ __global__ void __launch_bounds__(256) k_conv_groups_sum(const float* __restrict
                                                          const int* __restrict__ w_amax, ConvEpi epi, float* __restrict__ Y) {
   const float out_scale = 1.f / (amax_scale(x_amax) * amax_scale(w_amax));
   const long long total = n * cout;
-  // ILP float4 groups per thread, a grid's width apart (coalesced), all sixteen slab loads in flight before the first sum
+  // ILP float4 groups per thread, a grid's width apart (coalesced).  Every load -- the sixteen slab pieces, and per group
+  // of four columns ONE float4 each of bias, scale and residual -- is in flight before the first sum and the first store
+  // (a load behind a store waits for the store as well: both count on vmcnt).  cout is a multiple of 32, so a group's
+  // column is a multiple of 4; a residual whose base or pitch is not (no caller has one) is read element by element.
   const long long stride = (long long)gridDim.x * 1024;
   const long long e0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-  float4 pp[ILP][4];
+  const bool has_rsd = EPI && epi.residual, has_csc = EPI && epi.col_scale;
+  const long long rld = (EPI && epi.residual_ld) ? epi.residual_ld : cout;
+  const bool rsd_vec = has_rsd && ((reinterpret_cast<unsigned long long>(epi.residual) & 15) == 0) && ((rld & 3) == 0);
+  float4 pp[ILP][4], bv4[ILP], cs4[ILP], rs4[ILP];
 #pragma unroll
   for (int q = 0; q < ILP; ++q) {
     const long long e = e0 + q * stride;
+    bv4[q] = cs4[q] = rs4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (e < total) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) pp[q][g] = *reinterpret_cast<const float4*>(slabs + g * total + e);
+      const long long row = e / cout;
+      const int col = (int)(e - row * cout);
+      if (bias) bv4[q] = *reinterpret_cast<const float4*>(bias + col);
+      if (has_csc) cs4[q] = *reinterpret_cast<const float4*>(epi.col_scale + col);
+      if (has_rsd) {
+        const float* rp = epi.residual + row * rld + col;
+        rs4[q] = rsd_vec ? *reinterpret_cast<const float4*>(rp) : make_float4(rp[0], rp[1], rp[2], rp[3]);
+      }
     }
   }
   float ymax = 0.f;
@@ -1160,21 +1224,18 @@ __global__ void __launch_bounds__(256) k_conv_groups_sum(const float* __restrict
   for (int q = 0; q < ILP; ++q) {
     const long long e = e0 + q * stride;
     if (e < total) {
-      const long long row = e / cout;
-      const int col = (int)(e - row * cout);
       const float4 p0 = pp[q][0], p1 = pp[q][1], p2 = pp[q][2], p3 = pp[q][3];
       const float a[4] = {((p0.x + p1.x) + p2.x) + p3.x, ((p0.y + p1.y) + p2.y) + p3.y, ((p0.z + p1.z) + p2.z) + p3.z,
                           ((p0.w + p1.w) + p2.w) + p3.w};
+      const float bv[4] = {bv4[q].x, bv4[q].y, bv4[q].z, bv4[q].w}, cs[4] = {cs4[q].x, cs4[q].y, cs4[q].z, cs4[q].w};
+      const float rs[4] = {rs4[q].x, rs4[q].y, rs4[q].z, rs4[q].w};
       float v4[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float bvv = bias ? bias[col + j] : 0.f;
-        const float csc = (EPI && epi.col_scale) ? epi.col_scale[col + j] * out_scale : out_scale;
+        const float bvv = bv[j];
+        const float csc = has_csc ? cs[j] * out_scale : out_scale;
         float v = a[j] * csc + bvv;
-        if (EPI && epi.residual) {
-          const float rsd = epi.residual[row * (epi.residual_ld ? epi.residual_ld : cout) + col + j];
-          v = epi.relu == 2 ? (rsd > 0.f ? v : 0.f) : v + rsd;
-        }
+        if (has_rsd) v = epi.relu == 2 ? (rs[j] > 0.f ? v : 0.f) : v + rs[j];
         if (EPI && epi.relu == 1) v = fmaxf(v, 0.f);
         v4[j] = v;
         if (EPI) ymax = fmaxf(ymax, fabsf(v));
@@ -1399,6 +1460,18 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
   int orow_l = -1;
   if ((l < 32) && (row0 + l < n_out)) orow_l = order ? order[row0 + l] : (int)(row0 + l);
   float ymax = 0.f;
+  // as in conv_fwd_epilogue: the residual / gate operand of all NB x 16 elements is fetched before the first store
+  const bool has_rsd = EPI && epi.residual;
+  float rsd[EPI ? NB : 1][16];      // read only where has_rsd, and then only for rows that exist
+  if (has_rsd) {
+    int orows[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) orows[r] = __shfl(orow_l, (r & 3) + 8 * (r >> 2) + 4 * h);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(acc[b]));      // the group sums are final before the fetch
+    epi_fetch_rows<(EPI ? NB : 1)>(rsd, orows, __shfl(orow_l, 0), epi.residual + nb0 * 32 + i,
+                                   epi.residual_ld ? epi.residual_ld : cout);
+  }
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int col = (nb0 + b) * 32 + i;
@@ -1411,9 +1484,9 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
       int orow = __shfl(orow_l, (r & 3) + 8 * (r >> 2) + 4 * h);
       if (orow >= 0) {
         float v = acc[b][r] * csc + bvv;
-        if (EPI && epi.residual) {
-          const float rsd = epi.residual[(long long)orow * (epi.residual_ld ? epi.residual_ld : cout) + col];
-          v = epi.relu == 2 ? (rsd > 0.f ? v : 0.f) : v + rsd;      // relu == 2: threshold_backward, pass v where residual > 0
+        if (has_rsd) {
+          const float rs = rsd[EPI ? b : 0][r];
+          v = epi.relu == 2 ? (rs > 0.f ? v : 0.f) : v + rs;      // relu == 2: threshold_backward, pass v where residual > 0
         }
         if (EPI && epi.relu == 1) v = fmaxf(v, 0.f);
         Y[(long long)orow * cout + col] = v;
@@ -2504,15 +2577,19 @@ __global__ void __launch_bounds__(256) k_conv_generic(const float* __restrict__ 
   float ymax = 0.f;
   if (live) {
     const long long orow = order ? order[r] : r;
+    // the row's residual values before its first store (a load behind a store waits for the store: both count on vmcnt);
+    // columns past the tensor read the tile's first column instead and are dropped
+    float rsd[TC];
+    if (epi.residual) {
+#pragma unroll
+      for (int j = 0; j < TC; ++j) rsd[j] = epi.residual[orow * cout + n0 + (j < ncol ? j : 0)];
+    }
 #pragma unroll
     for (int j = 0; j < TC; ++j) {
       if (j < ncol) {
         const int col = n0 + j;
         float v = acc[j] * (epi.col_scale ? epi.col_scale[col] : 1.f) + (bias ? bias[col] : 0.f);
-        if (epi.residual) {
-          const float rsd = epi.residual[orow * cout + col];
-          v = epi.relu == 2 ? (rsd > 0.f ? v : 0.f) : v + rsd;
-        }
+        if (epi.residual) v = epi.relu == 2 ? (rsd[j] > 0.f ? v : 0.f) : v + rsd[j];
         if (epi.relu == 1) v = fmaxf(v, 0.f);
         Y[orow * cout + col] = v;
         ymax = fmaxf(ymax, fabsf(v));
