@@ -161,6 +161,9 @@ SIGNATURES = {
     "gcl_ransac_default_chunk": (_i32, []),
     "gcl_ransac_register": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _f32, _i32, _f32, ctypes.c_uint64, _i32, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
+    "gcl_ransac_batch_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "gcl_ransac_register_batch": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _f32, _f32, _f32, _i32, _f32, _vp, _i32, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]),
     "gcl_group_loss_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
     "gcl_group_loss_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcl_circle_group_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -171,6 +174,7 @@ SIGNATURES = {
     "gcl_nn3_scratch_len": (_i64, [_i32, _i32]),
     "gcl_nn3_rowmin": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcl_mutual_match": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "gcl_mutual_correspondences": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "gcl_neg_mask": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "gcl_neg_loss_fwd": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
     "gcl_neg_loss_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp]),

@@ -247,6 +247,90 @@ __global__ void __launch_bounds__(1024) k_mutual_match(const int* __restrict__ n
   }
 }
 
+// ---- k_mutual_corr ------------------------------------------------------------------------------------------------------
+// The correspondences a registration with open3d's mutual filter runs on, as point rows, with their number left on the
+// device.  ONE workgroup, as k_mutual_match and for its reasons, in two walks over the sources: the first counts the mutual
+// pairs, the second writes -- the compacted rows (same ballot / LDS placement: dense, ascending in i, no atomic) followed by
+// zero rows when there are at least min_count of them, else every source beside its nearest target (open3d: "too few
+// correspondences after mutual filter, fall back to original correspondences").  Which branch runs is uniform over the
+// workgroup.  A target index outside [0, m1) is never dereferenced: such a row of the fall-back has a zero target.
+__global__ void __launch_bounds__(1024) k_mutual_corr(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10, int m1,
+                                                      const float* __restrict__ xyz0, const float* __restrict__ xyz1,
+                                                      int min_count, float* __restrict__ src, float* __restrict__ tgt,
+                                                      int* __restrict__ count) {
+  __shared__ int wcount[16];
+  __shared__ int base_s;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int mine = 0;
+  for (int i = t; i < m0; i += 1024) {
+    const int j = nn01[i];
+    if ((unsigned)j < (unsigned)m1 && nn10[j] == i) ++mine;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+  if (lane == 0) wcount[w] = mine;
+  __syncthreads();
+  int n_mutual = 0;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) n_mutual += wcount[u];
+  __syncthreads();        // the waves' counts are reused below
+  if (n_mutual < min_count) {
+    for (int i = t; i < m0; i += 1024) {
+      const int j = nn01[i];
+      const bool ok = (unsigned)j < (unsigned)m1;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        src[3 * (long long)i + c] = xyz0[3 * (long long)i + c];
+        tgt[3 * (long long)i + c] = ok ? xyz1[3 * (long long)j + c] : 0.f;
+      }
+    }
+    if (t == 0) {
+      count[0] = m0;
+      count[1] = n_mutual;
+    }
+    return;
+  }
+  if (t == 0) base_s = 0;
+  __syncthreads();
+  for (int i0 = 0; i0 < m0; i0 += 1024) {
+    const int i = i0 + t;
+    int j = -1;
+    bool keep = false;
+    if (i < m0) {
+      j = nn01[i];
+      if ((unsigned)j < (unsigned)m1) keep = nn10[j] == i;
+    }
+    const unsigned long long mk = __ballot(keep);
+    if (lane == 0) wcount[w] = __popcll(mk);
+    __syncthreads();
+    int before = base_s, tile_total = 0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      if (u < w) before += wcount[u];
+      tile_total += wcount[u];
+    }
+    if (keep) {
+      const long long at = before + __popcll(mk & ((1ull << lane) - 1ull));
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        src[3 * at + c] = xyz0[3 * (long long)i + c];
+        tgt[3 * at + c] = xyz1[3 * (long long)j + c];
+      }
+    }
+    __syncthreads();        // everyone has read base_s and the waves' counts
+    if (t == 0) base_s += tile_total;
+    __syncthreads();
+  }
+  for (long long e = 3 * (long long)n_mutual + t; e < 3 * (long long)m0; e += 1024) {
+    src[e] = 0.f;
+    tgt[e] = 0.f;
+  }
+  if (t == 0) {
+    count[0] = n_mutual;
+    count[1] = n_mutual;
+  }
+}
+
 }  // namespace gcl
 
 using namespace gcl;
@@ -296,6 +380,16 @@ int gcl_mutual_match(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32
   GCL_CHECK_ARG(!T || (kp0 && kp1), "gcl_mutual_match: a transformation needs both keypoint arrays (null kp0 / kp1)");
   hipLaunchKernelGGL(k_mutual_match, dim3(1), dim3(1024), 0, (hipStream_t)stream, nn01, m0, nn10, m1, kp0, kp1, T, tau, pairs,
                      stats);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_mutual_correspondences(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32_t m1, const float* xyz0,
+                               const float* xyz1, int32_t min_count, float* src, float* tgt, int32_t* count, void* stream) {
+  GCL_CHECK_ARG(m0 >= 1 && m1 >= 1, "gcl_mutual_correspondences: sizes must be >= 1 (m0 = %d, m1 = %d)", m0, m1);
+  GCL_CHECK_ARG(nn01 && nn10 && xyz0 && xyz1 && src && tgt && count, "gcl_mutual_correspondences: null pointer");
+  hipLaunchKernelGGL(k_mutual_corr, dim3(1), dim3(1024), 0, (hipStream_t)stream, nn01, m0, nn10, m1, xyz0, xyz1, min_count,
+                     src, tgt, count);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

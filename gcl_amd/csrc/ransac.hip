@@ -25,6 +25,14 @@
 // After every chunk k_rs_best updates the best hypothesis and, with 0 < confidence < 1, the id limit
 // ceil(log(1 - confidence) / log(1 - (best count / n)^ransac_n)) in a control block on the device; the kernels of a later
 // chunk that starts at or behind the limit return at once (status -4).  The host enqueues every chunk and never waits.
+//
+// A BATCH of pairs (gcl_ransac_register_batch) runs through the same kernels with the pair as the grid's z dimension: every
+// pair has its own control block and its own slice of the scratch layout (`stride` bytes apart), and the launches of a chunk
+// cover all pairs -- a registration is ~100 dependent launches of a few microseconds, so a batch costs the launches of one
+// pair.  A pair's correspondence count and seed live in its control block (k_rs_init reads the count from the device,
+// clamped to [0, n_cap]), so the pairs of a batch may have different lengths and nothing the host does depends on them; a
+// pair with fewer than ransac_n correspondences starts with limit 0 and is skipped by every chunk.  One pair alone
+// (gcl_ransac_register) is a batch of one: the same kernels, the same arithmetic, the same bits.
 #include "common.h"
 #include "kabsch.h"
 
@@ -40,15 +48,27 @@ constexpr int RS_MAX_CHUNK = 1 << 20;
 constexpr int RS_MAX_N = 1 << 24;           // record indices 2 i + 1 stay far inside an int
 constexpr int RS_SCORE_GRID = 1024;         // score workgroups per range at most, grid-stride above
 constexpr long long RS_NO_LIMIT = 0x7fffffffffffffffll;
+constexpr int RS_MAX_BATCH = 65535;         // the pair is blockIdx.z
+constexpr int RS_SEED_GROUP = 32;           // seeds travel as kernel arguments, this many pairs per k_rs_init launch
 
 struct RsCtrl {
   long long limit;        // a chunk whose first id is >= limit does nothing
+  unsigned long long seed;
+  int n, pad;             // the pair's correspondence count (rows from n on are never read); with limit and seed in the
+                          // block's first 32 bytes: what every kernel reads first comes in one scalar load
   double best_sse;
   int best_h, best_count;
   int covered, scored;
   int n_a, n_b;           // survivors of steps 1-2 / of step 4 in the current chunk
   float best_T[12];
 };
+struct RsSeeds { unsigned long long s[RS_SEED_GROUP]; };
+
+// pair `pair`'s copy of a scratch array (the slices are `stride` bytes apart) / of a [batch, row] output
+template <class T>
+__device__ __forceinline__ T* rs_at(T* p, int pair, size_t stride) {
+  return reinterpret_cast<T*>(reinterpret_cast<size_t>(p) + (size_t)pair * stride);
+}
 
 __device__ __forceinline__ int rs_draw(unsigned long long seed, long long h, int j, int n) {
   unsigned long long z = seed + (unsigned long long)(4 * h + j + 1) * 0x9E3779B97F4A7C15ull;
@@ -72,11 +92,22 @@ __device__ __forceinline__ float rs_dist(const float4& a, const float4& b) {
 }
 
 // control block + the correspondences as 32-byte records {s, 0, t', 0}: two 16-byte loads per drawn sample, whole tiles
-__global__ void __launch_bounds__(256) k_rs_init(const float* __restrict__ src, const float* __restrict__ tgt, int n,
-                                                 float4* __restrict__ pk, RsCtrl* ctrl) {
+// (pairs pair0 .. pair0 + gridDim.z - 1; the count comes from n_dev when given: negative reads as 0, above n_cap as n_cap)
+__global__ void __launch_bounds__(256) k_rs_init(const float* __restrict__ src, const float* __restrict__ tgt, int n_cap,
+                                                 const int* __restrict__ n_dev, int ransac_n, int pair0, RsSeeds seeds,
+                                                 float4* __restrict__ pk, RsCtrl* ctrl, size_t stride) {
+  const int pair = pair0 + blockIdx.z;
+  const int n = n_dev ? min(max(n_dev[pair], 0), n_cap) : n_cap;
+  src += (size_t)pair * n_cap * 3;
+  tgt += (size_t)pair * n_cap * 3;
+  pk = rs_at(pk, pair, stride);
+  ctrl = rs_at(ctrl, pair, stride);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i == 0) {
-    ctrl->limit = RS_NO_LIMIT;
+    ctrl->n = n;
+    ctrl->pad = 0;
+    ctrl->seed = seeds.s[blockIdx.z];
+    ctrl->limit = n < ransac_n ? 0 : RS_NO_LIMIT;      // too few correspondences: nothing is drawn, every chunk is skipped
     ctrl->best_sse = 0.0;
     ctrl->best_h = -1;
     ctrl->best_count = 0;
@@ -93,13 +124,22 @@ __global__ void __launch_bounds__(256) k_rs_init(const float* __restrict__ src, 
 // steps 1-2 for hypothesis h0 + (thread): ballot word per wave, survivor count per workgroup
 template <int RN>
 __global__ void __launch_bounds__(256) k_rs_draw(const RsCtrl* __restrict__ ctrl, long long h0, int m,
-                                                 const float4* __restrict__ pk, int n, unsigned long long seed, float sim,
+                                                 const float4* __restrict__ pk, float sim,
                                                  unsigned long long* __restrict__ mask, int* __restrict__ bcnt,
-                                                 int* __restrict__ hyp_status) {
+                                                 int* __restrict__ hyp_status, size_t stride, long long status_stride) {
+  const int pair = blockIdx.z;
+  ctrl = rs_at(ctrl, pair, stride);
+  pk = rs_at(pk, pair, stride);
+  mask = rs_at(mask, pair, stride);
+  bcnt = rs_at(bcnt, pair, stride);
+  if (hyp_status) hyp_status += (size_t)pair * status_stride;
   const int e = blockIdx.x * 256 + threadIdx.x;
   const bool live = e < m;
   const long long h = h0 + e;
-  if (h0 >= ctrl->limit) {      // uniform over the launch
+  const long long limit = ctrl->limit;
+  const int n = ctrl->n;
+  const unsigned long long seed = ctrl->seed;
+  if (h0 >= limit) {      // uniform over the pair
     if (hyp_status && live) hyp_status[h] = -4;
     return;
   }
@@ -140,12 +180,19 @@ __global__ void __launch_bounds__(256) k_rs_draw(const RsCtrl* __restrict__ ctrl
 
 // ordered compaction of the flagged items 0 .. n_items - 1 (ballot words `mask`, per-workgroup counts `bcnt`): list[] holds
 // them in ascending order, *n_out their number.  A workgroup's offset is the sum of the counts before it (integers: any
-// order of summation), an item's place inside it the number of set bits before its own.
-__global__ void __launch_bounds__(256) k_rs_compact(const RsCtrl* __restrict__ ctrl, long long h0, const int* __restrict__ n_dev,
-                                                    int n_host, const unsigned long long* __restrict__ mask,
-                                                    const int* __restrict__ bcnt, int* __restrict__ list, int* n_out) {
+// order of summation), an item's place inside it the number of set bits before its own.  First pass: the m hypotheses of the
+// chunk -> n_a; second: the n_a survivors -> n_b.
+__global__ void __launch_bounds__(256) k_rs_compact(RsCtrl* ctrl, long long h0, int second, int m,
+                                                    const unsigned long long* __restrict__ mask,
+                                                    const int* __restrict__ bcnt, int* __restrict__ list, size_t stride) {
+  const int pair = blockIdx.z;
+  ctrl = rs_at(ctrl, pair, stride);
+  mask = rs_at(mask, pair, stride);
+  bcnt = rs_at(bcnt, pair, stride);
+  list = rs_at(list, pair, stride);
   if (h0 >= ctrl->limit) return;
-  const int n_items = n_dev ? *n_dev : n_host;
+  const int n_items = second ? ctrl->n_a : m;
+  int* n_out = second ? &ctrl->n_b : &ctrl->n_a;
   const int b = blockIdx.x, t = threadIdx.x;
   if (n_items == 0 && b == 0 && t == 0) *n_out = 0;
   if (b * 256 >= n_items) return;
@@ -169,12 +216,22 @@ __global__ void __launch_bounds__(256) k_rs_compact(const RsCtrl* __restrict__ c
 
 // steps 3-4 for survivor p of the first list (every lane holds one): pose to poses[p], flags of the second compaction
 template <int RN>
-__global__ void __launch_bounds__(256) k_rs_pose(RsCtrl* ctrl, long long h0, const float4* __restrict__ pk, int n,
-                                                 unsigned long long seed, float check2, const int* __restrict__ list_a,
+__global__ void __launch_bounds__(256) k_rs_pose(const RsCtrl* __restrict__ ctrl, long long h0, const float4* __restrict__ pk,
+                                                 float check2, const int* __restrict__ list_a,
                                                  float* __restrict__ poses, unsigned long long* __restrict__ mask,
-                                                 int* __restrict__ bcnt, int* __restrict__ hyp_status) {
+                                                 int* __restrict__ bcnt, int* __restrict__ hyp_status, size_t stride,
+                                                 long long status_stride) {
+  const int pair = blockIdx.z;
+  ctrl = rs_at(ctrl, pair, stride);
+  pk = rs_at(pk, pair, stride);
+  list_a = rs_at(list_a, pair, stride);
+  poses = rs_at(poses, pair, stride);
+  mask = rs_at(mask, pair, stride);
+  bcnt = rs_at(bcnt, pair, stride);
+  if (hyp_status) hyp_status += (size_t)pair * status_stride;
   if (h0 >= ctrl->limit) return;
-  const int n_a = ctrl->n_a;
+  const int n_a = ctrl->n_a, n = ctrl->n;
+  const unsigned long long seed = ctrl->seed;
   if ((int)blockIdx.x * 256 >= n_a) return;
   const int p = blockIdx.x * 256 + threadIdx.x;
   bool pass = false;
@@ -227,11 +284,18 @@ __global__ void __launch_bounds__(256) k_rs_pose(RsCtrl* ctrl, long long h0, con
 // [part * per, (part + 1) * per) from the packed records (20 KB per range at n = 5000, shared by the waves of a CU through
 // its L1), the 64 sums are added by a butterfly
 __global__ void __launch_bounds__(256) k_rs_score_wave(const RsCtrl* __restrict__ ctrl, long long h0,
-                                                       const float4* __restrict__ pk, int n, float thr2,
+                                                       const float4* __restrict__ pk, float thr2,
                                                        const int* __restrict__ list_b, const float* __restrict__ poses,
-                                                       int* __restrict__ pcount, double* __restrict__ psse) {
+                                                       int* __restrict__ pcount, double* __restrict__ psse, size_t stride) {
+  const int pair = blockIdx.z;
+  ctrl = rs_at(ctrl, pair, stride);
+  pk = rs_at(pk, pair, stride);
+  list_b = rs_at(list_b, pair, stride);
+  poses = rs_at(poses, pair, stride);
+  pcount = rs_at(pcount, pair, stride);
+  psse = rs_at(psse, pair, stride);
   if (h0 >= ctrl->limit) return;
-  const int n_b = ctrl->n_b;
+  const int n_b = ctrl->n_b, n = ctrl->n;
   const int lane = threadIdx.x & 63, part = blockIdx.y;
   const int per = (n + RS_PARTS - 1) / RS_PARTS;
   const int i0 = min(n, part * per), i1 = min(n, i0 + per);
@@ -265,14 +329,23 @@ __device__ __forceinline__ bool rs_better(int c, double s, int h, int c2, double
   return c > c2 || (c == c2 && (s < s2 || (s == s2 && h < h2)));
 }
 
-// end of a chunk (one workgroup): the scored hypotheses' totals and statuses, the best of them against the best so far,
+// end of a chunk (one workgroup per pair): the scored hypotheses' totals and statuses, the best of them against the best so far,
 // the counters of info[] and the early-stop limit
-__global__ void __launch_bounds__(1024) k_rs_best(RsCtrl* ctrl, long long h0, int m, int n, int ransac_n, double confidence,
+__global__ void __launch_bounds__(1024) k_rs_best(RsCtrl* ctrl, long long h0, int m, int ransac_n, double confidence,
                                                   const int* __restrict__ list_a, const int* __restrict__ list_b,
                                                   const float* __restrict__ poses, const int* __restrict__ pcount,
-                                                  const double* __restrict__ psse, int* __restrict__ hyp_status) {
+                                                  const double* __restrict__ psse, int* __restrict__ hyp_status, size_t stride,
+                                                  long long status_stride) {
+  const int pair = blockIdx.z;
+  ctrl = rs_at(ctrl, pair, stride);
+  list_a = rs_at(list_a, pair, stride);
+  list_b = rs_at(list_b, pair, stride);
+  poses = rs_at(poses, pair, stride);
+  pcount = rs_at(pcount, pair, stride);
+  psse = rs_at(psse, pair, stride);
+  if (hyp_status) hyp_status += (size_t)pair * status_stride;
   if (h0 >= ctrl->limit) return;
-  const int n_b = ctrl->n_b, t = threadIdx.x;
+  const int n_b = ctrl->n_b, n = ctrl->n, t = threadIdx.x;
   __shared__ int bc[1024], bh[1024], bq[1024];
   __shared__ double bs[1024];
   int c_best = 0, h_best = -1, q_best = 0;
@@ -319,9 +392,19 @@ __global__ void __launch_bounds__(1024) k_rs_best(RsCtrl* ctrl, long long h0, in
   }
 }
 
-// outputs: the [4, 4] transformation, info, fit and the winner's inlier labels (the score's own comparison)
-__global__ void __launch_bounds__(256) k_rs_finish(const RsCtrl* __restrict__ ctrl, const float4* __restrict__ pk, int n,
-                                                   float thr2, float* trans16, int* info, float* fit, float* labels) {
+// outputs: the [4, 4] transformation, info, fit and the winner's inlier labels (the score's own comparison; 0 from the
+// pair's count on)
+__global__ void __launch_bounds__(256) k_rs_finish(const RsCtrl* __restrict__ ctrl, const float4* __restrict__ pk, int n_cap,
+                                                   float thr2, float* trans16, int* info, float* fit, float* labels,
+                                                   size_t stride) {
+  const int pair = blockIdx.z;
+  ctrl = rs_at(ctrl, pair, stride);
+  pk = rs_at(pk, pair, stride);
+  trans16 += (size_t)pair * 16;
+  info += (size_t)pair * 4;
+  fit += (size_t)pair * 2;
+  if (labels) labels += (size_t)pair * n_cap;
+  const int n = ctrl->n;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool found = ctrl->best_h >= 0 && ctrl->best_count > 0;
   if (i < 16) trans16[i] = i < 12 ? (found ? ctrl->best_T[i] : ((i % 5 == 0) ? 1.f : 0.f)) : (i == 15 ? 1.f : 0.f);
@@ -333,11 +416,15 @@ __global__ void __launch_bounds__(256) k_rs_finish(const RsCtrl* __restrict__ ct
     fit[0] = found ? (float)((double)ctrl->best_count / (double)n) : 0.f;
     fit[1] = found ? (float)sqrt(ctrl->best_sse / (double)ctrl->best_count) : 0.f;
   }
-  if (labels && i < n) {
-    float T[12];
+  if (labels && i < n_cap) {
+    float lab = 0.f;
+    if (found && i < n) {
+      float T[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) T[k] = ctrl->best_T[k];
-    labels[i] = (found && rs_resid2(T, pk[2 * i], pk[2 * i + 1]) < thr2) ? 1.f : 0.f;
+      for (int k = 0; k < 12; ++k) T[k] = ctrl->best_T[k];
+      lab = rs_resid2(T, pk[2 * i], pk[2 * i + 1]) < thr2 ? 1.f : 0.f;
+    }
+    labels[i] = lab;
   }
 }
 
@@ -374,20 +461,15 @@ int64_t gcl_ransac_scratch_bytes(int32_t n, int32_t chunk) {
   return (int64_t)rs_layout(n, rs_chunk(chunk)).total;
 }
 
-int gcl_ransac_register(const float* src, const float* tgt, int32_t n, int32_t ransac_n, float edge_similarity,
-                        float check_distance, float max_corr_distance, int32_t max_iteration, float confidence,
-                        uint64_t seed, int32_t chunk, void* scratch, float* trans16, int32_t* info, float* fit, float* labels,
-                        int32_t* hyp_status, void* stream) {
-  GCL_CHECK_ARG(src && tgt && scratch && trans16 && info && fit, "gcl_ransac_register: null pointer");
-  GCL_CHECK_ARG(ransac_n == 3 || ransac_n == 4, "gcl_ransac_register: ransac_n must be 3 or 4, got %d", ransac_n);
-  GCL_CHECK_ARG(n >= ransac_n, "gcl_ransac_register: n = %d correspondences, fewer than ransac_n = %d", n, ransac_n);
-  GCL_CHECK_ARG(n <= RS_MAX_N, "gcl_ransac_register: n = %d correspondences, more than %d", n, RS_MAX_N);
-  GCL_CHECK_ARG(max_iteration >= 1, "gcl_ransac_register: max_iteration must be >= 1, got %d", max_iteration);
-  GCL_CHECK_ARG(max_corr_distance > 0.f, "gcl_ransac_register: max_corr_distance must be > 0");
-  GCL_CHECK_ARG(chunk >= 0, "gcl_ransac_register: chunk must be >= 0 (0 = default), got %d", chunk);
-  hipStream_t st = (hipStream_t)stream;
+// the launches of a batch (one pair: a batch of one).  n_dev: device counts or NULL (n_cap for every pair); seeds: HOST array
+static void rs_enqueue(const float* src, const float* tgt, int batch, int n_cap, const int* n_dev, int ransac_n,
+                       float edge_similarity, float check_distance, float max_corr_distance, int max_iteration,
+                       float confidence, const uint64_t* seeds, int chunk, void* scratch, float* trans16, int* info, float* fit,
+                       float* labels, int* hyp_status, hipStream_t st) {
   const int ch = rs_chunk(chunk);
-  const RsLayout L = rs_layout(n, ch);
+  const RsLayout L = rs_layout(n_cap, ch);
+  const size_t stride = L.total;
+  const long long ss = max_iteration;
   char* base = (char*)scratch;
   RsCtrl* ctrl = (RsCtrl*)(base + L.ctrl);
   float4* pk = (float4*)(base + L.pk);
@@ -399,37 +481,84 @@ int gcl_ransac_register(const float* src, const float* tgt, int32_t n, int32_t r
   double* psse = (double*)(base + L.psse);
   const float thr2 = max_corr_distance * max_corr_distance;
   const float check2 = check_distance > 0.f ? check_distance * check_distance : 0.f;
-  hipLaunchKernelGGL(k_rs_init, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, src, tgt, n, pk, ctrl);
+  const unsigned B = (unsigned)batch;
+  for (int p0 = 0; p0 < batch; p0 += RS_SEED_GROUP) {
+    const int g = std::min(RS_SEED_GROUP, batch - p0);
+    RsSeeds sd;
+    for (int k = 0; k < RS_SEED_GROUP; ++k) sd.s[k] = k < g ? (unsigned long long)seeds[p0 + k] : 0ull;
+    hipLaunchKernelGGL(k_rs_init, dim3((unsigned)cdiv(n_cap, 256), 1, (unsigned)g), dim3(256), 0, st, src, tgt, n_cap, n_dev,
+                       ransac_n, p0, sd, pk, ctrl, stride);
+  }
   for (long long h0 = 0; h0 < max_iteration; h0 += ch) {
     const int m = (int)std::min<long long>(ch, max_iteration - h0);
-    const dim3 grid((unsigned)cdiv(m, 256));
+    const dim3 grid((unsigned)cdiv(m, 256), 1, B);
     if (ransac_n == 3) {
-      hipLaunchKernelGGL(k_rs_draw<3>, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, m, (const float4*)pk, n,
-                         (unsigned long long)seed, edge_similarity, mask, bcnt, hyp_status);
+      hipLaunchKernelGGL(k_rs_draw<3>, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, m, (const float4*)pk, edge_similarity,
+                         mask, bcnt, hyp_status, stride, ss);
     } else {
-      hipLaunchKernelGGL(k_rs_draw<4>, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, m, (const float4*)pk, n,
-                         (unsigned long long)seed, edge_similarity, mask, bcnt, hyp_status);
+      hipLaunchKernelGGL(k_rs_draw<4>, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, m, (const float4*)pk, edge_similarity,
+                         mask, bcnt, hyp_status, stride, ss);
     }
-    hipLaunchKernelGGL(k_rs_compact, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, (const int*)nullptr, m,
-                       (const unsigned long long*)mask, (const int*)bcnt, list_a, &ctrl->n_a);
+    hipLaunchKernelGGL(k_rs_compact, grid, dim3(256), 0, st, ctrl, h0, 0, m, (const unsigned long long*)mask,
+                       (const int*)bcnt, list_a, stride);
     if (ransac_n == 3) {
-      hipLaunchKernelGGL(k_rs_pose<3>, grid, dim3(256), 0, st, ctrl, h0, (const float4*)pk, n, (unsigned long long)seed,
-                         check2, (const int*)list_a, poses, mask, bcnt, hyp_status);
+      hipLaunchKernelGGL(k_rs_pose<3>, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, (const float4*)pk, check2,
+                         (const int*)list_a, poses, mask, bcnt, hyp_status, stride, ss);
     } else {
-      hipLaunchKernelGGL(k_rs_pose<4>, grid, dim3(256), 0, st, ctrl, h0, (const float4*)pk, n, (unsigned long long)seed,
-                         check2, (const int*)list_a, poses, mask, bcnt, hyp_status);
+      hipLaunchKernelGGL(k_rs_pose<4>, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, (const float4*)pk, check2,
+                         (const int*)list_a, poses, mask, bcnt, hyp_status, stride, ss);
     }
-    hipLaunchKernelGGL(k_rs_compact, grid, dim3(256), 0, st, (const RsCtrl*)ctrl, h0, (const int*)&ctrl->n_a, 0,
-                       (const unsigned long long*)mask, (const int*)bcnt, list_b, &ctrl->n_b);
-    hipLaunchKernelGGL(k_rs_score_wave, dim3((unsigned)std::min<long long>(cdiv(m, 4), RS_SCORE_GRID), RS_PARTS), dim3(256), 0, st,
-                       (const RsCtrl*)ctrl, h0, (const float4*)pk, n, thr2, (const int*)list_b, (const float*)poses, pcount,
-                       psse);
-    hipLaunchKernelGGL(k_rs_best, dim3(1), dim3(1024), 0, st, ctrl, h0, m, n, ransac_n, (double)confidence,
+    hipLaunchKernelGGL(k_rs_compact, grid, dim3(256), 0, st, ctrl, h0, 1, m, (const unsigned long long*)mask,
+                       (const int*)bcnt, list_b, stride);
+    hipLaunchKernelGGL(k_rs_score_wave, dim3((unsigned)std::min<long long>(cdiv(m, 4), RS_SCORE_GRID), RS_PARTS, B), dim3(256),
+                       0, st, (const RsCtrl*)ctrl, h0, (const float4*)pk, thr2, (const int*)list_b, (const float*)poses, pcount,
+                       psse, stride);
+    hipLaunchKernelGGL(k_rs_best, dim3(1, 1, B), dim3(1024), 0, st, ctrl, h0, m, ransac_n, (double)confidence,
                        (const int*)list_a, (const int*)list_b, (const float*)poses, (const int*)pcount, (const double*)psse,
-                       hyp_status);
+                       hyp_status, stride, ss);
   }
-  hipLaunchKernelGGL(k_rs_finish, dim3((unsigned)cdiv(std::max(n, 16), 256)), dim3(256), 0, st, (const RsCtrl*)ctrl,
-                     (const float4*)pk, n, thr2, trans16, info, fit, labels);
+  hipLaunchKernelGGL(k_rs_finish, dim3((unsigned)cdiv(std::max(n_cap, 16), 256), 1, B), dim3(256), 0, st, (const RsCtrl*)ctrl,
+                     (const float4*)pk, n_cap, thr2, trans16, info, fit, labels, stride);
+}
+
+int gcl_ransac_register(const float* src, const float* tgt, int32_t n, int32_t ransac_n, float edge_similarity,
+                        float check_distance, float max_corr_distance, int32_t max_iteration, float confidence,
+                        uint64_t seed, int32_t chunk, void* scratch, float* trans16, int32_t* info, float* fit, float* labels,
+                        int32_t* hyp_status, void* stream) {
+  GCL_CHECK_ARG(src && tgt && scratch && trans16 && info && fit, "gcl_ransac_register: null pointer");
+  GCL_CHECK_ARG(ransac_n == 3 || ransac_n == 4, "gcl_ransac_register: ransac_n must be 3 or 4, got %d", ransac_n);
+  GCL_CHECK_ARG(n >= ransac_n, "gcl_ransac_register: n = %d correspondences, fewer than ransac_n = %d", n, ransac_n);
+  GCL_CHECK_ARG(n <= RS_MAX_N, "gcl_ransac_register: n = %d correspondences, more than %d", n, RS_MAX_N);
+  GCL_CHECK_ARG(max_iteration >= 1, "gcl_ransac_register: max_iteration must be >= 1, got %d", max_iteration);
+  GCL_CHECK_ARG(max_corr_distance > 0.f, "gcl_ransac_register: max_corr_distance must be > 0");
+  GCL_CHECK_ARG(chunk >= 0, "gcl_ransac_register: chunk must be >= 0 (0 = default), got %d", chunk);
+  rs_enqueue(src, tgt, 1, n, nullptr, ransac_n, edge_similarity, check_distance, max_corr_distance, max_iteration, confidence,
+             &seed, chunk, scratch, trans16, info, fit, labels, hyp_status, (hipStream_t)stream);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_ransac_batch_scratch_bytes(int32_t batch, int32_t n_cap, int32_t chunk) {
+  if (batch < 1 || batch > RS_MAX_BATCH || n_cap <= 0 || n_cap > RS_MAX_N || chunk < 0) return 0;
+  return (int64_t)batch * (int64_t)rs_layout(n_cap, rs_chunk(chunk)).total;
+}
+
+int gcl_ransac_register_batch(const float* src, const float* tgt, int32_t batch, int32_t n_cap, const int32_t* n_dev,
+                              int32_t ransac_n, float edge_similarity, float check_distance, float max_corr_distance,
+                              int32_t max_iteration, float confidence, const uint64_t* seeds, int32_t chunk, void* scratch,
+                              float* trans16, int32_t* info, float* fit, float* labels, int32_t* hyp_status, void* stream) {
+  GCL_CHECK_ARG(src && tgt && seeds && scratch && trans16 && info && fit, "gcl_ransac_register_batch: null pointer");
+  GCL_CHECK_ARG(batch >= 1 && batch <= RS_MAX_BATCH, "gcl_ransac_register_batch: batch must be in [1, %d], got %d",
+                RS_MAX_BATCH, batch);
+  GCL_CHECK_ARG(ransac_n == 3 || ransac_n == 4, "gcl_ransac_register_batch: ransac_n must be 3 or 4, got %d", ransac_n);
+  GCL_CHECK_ARG(n_cap >= ransac_n, "gcl_ransac_register_batch: n_cap = %d correspondences, fewer than ransac_n = %d", n_cap,
+                ransac_n);
+  GCL_CHECK_ARG(n_cap <= RS_MAX_N, "gcl_ransac_register_batch: n_cap = %d correspondences, more than %d", n_cap, RS_MAX_N);
+  GCL_CHECK_ARG(max_iteration >= 1, "gcl_ransac_register_batch: max_iteration must be >= 1, got %d", max_iteration);
+  GCL_CHECK_ARG(max_corr_distance > 0.f, "gcl_ransac_register_batch: max_corr_distance must be > 0");
+  GCL_CHECK_ARG(chunk >= 0, "gcl_ransac_register_batch: chunk must be >= 0 (0 = default), got %d", chunk);
+  rs_enqueue(src, tgt, batch, n_cap, n_dev, ransac_n, edge_similarity, check_distance, max_corr_distance, max_iteration,
+             confidence, seeds, chunk, scratch, trans16, info, fit, labels, hyp_status, (hipStream_t)stream);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -8,6 +8,12 @@ Putative correspondences are every source row paired with its feature-nearest ta
 stop, all on the device).  Minimal samples come from a counter generator keyed by ``seed`` in place of open3d's
 ``std::mt19937``: a seeded run is reproducible bit for bit.  Nothing leaves the device until the caller reads the result.
 
+A BATCH of pairs goes through ``ransac_correspondences_batch`` (``gcl_ransac_register_batch``: the launches of one pair,
+every pair's correspondence count read on the device), and open3d's ``mutual_filter=True`` through
+``registration_ransac_based_on_mutual_feature_matching``: two ``pdist_min`` calls, ``gcl_mutual_correspondences`` (the mutual
+pairs as point rows, or open3d's fall-back to all of them, with the count left on the device) and a registration on that
+count.
+
 ``FeatureRansac`` speaks ``Matcher.estimator``'s calling convention (scripts/SC2_PCR.py), so
 ``eval_pairs(model, pairs, FeatureRansac.kitti(voxel_size))`` and ``evaluate_scene(..., matcher=FeatureRansac.eth())`` run
 the reference's two RANSAC configurations through the loops that already exist.
@@ -37,6 +43,19 @@ class RegistrationResult:
     @property
     def inlier_rmse(self):
         return self.fit[1]
+
+
+class BatchRegistrationResult:
+    """Device tensors of a batch of registrations: ``transformation`` [B, 4, 4], ``fit`` [B, 2] (fitness, inlier rmse),
+    ``info`` int32 [B, 4], ``labels`` float32 [B, n] (0 from a pair's count on), ``counts`` int32 [B] (the device counts the
+    pairs ran on, None: n for every pair), ``hyp_status`` int32 [B, max_iteration] or None, and the correspondences
+    ``src_corr`` / ``tgt_corr`` [B, n, 3] as passed.  ``count`` / ``n_mutual`` (device scalars) are set by the mutual-filter
+    registration of one pair."""
+
+    def __init__(self, transformation, fit, info, labels, counts, src_corr, tgt_corr, hyp_status=None):
+        self.transformation, self.fit, self.info, self.labels, self.counts = transformation, fit, info, labels, counts
+        self.src_corr, self.tgt_corr, self.hyp_status = src_corr, tgt_corr, hyp_status
+        self.count = self.n_mutual = None
 
 
 def _draw_seed(seed):
@@ -81,6 +100,93 @@ def ransac_correspondences(src, tgt, max_correspondence_distance, ransac_n=4, ed
                               buf[off_labels:off_labels + 4 * n].view(torch.float32), src, tgt, status)
 
 
+def ransac_correspondences_batch(src, tgt, max_correspondence_distance, ransac_n=4, edge_length_similarity=0.9,
+                                 checker_distance=None, max_iteration=4000000, confidence=0.999, counts=None, seeds=None,
+                                 chunk=0, want_status=False):
+    """RANSAC on B sets of correspondences ``src[b, i] <-> tgt[b, i]`` (device tensors [B, n, 3]) in ONE call with the
+    launches of one pair.  ``counts`` (device int32 [B], optional): pair b runs on its first ``counts[b]`` rows, read on the
+    device (rows beyond are never read; fewer than ``ransac_n``: identity, info[0] = -1).  ``seeds``: B integers, or None:
+    drawn from ``np.random`` in pair order.  A pair's result is bitwise what ``ransac_correspondences`` gives for its rows
+    and seed.
+
+    Memory: the scratch is the single-pair layout times B (``gcl_ransac_batch_scratch_bytes``): about 40 MB per pair at the
+    default chunk."""
+    lib = _lib.require_gpu()
+    src, tgt = src.detach().to(torch.float32).contiguous(), tgt.detach().to(torch.float32).contiguous()
+    if src.dim() != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape != tgt.shape:
+        raise ValueError(f"correspondences must be two [B, n, 3] tensors, got {tuple(src.shape)} and {tuple(tgt.shape)}")
+    B, n, dev = src.shape[0], src.shape[1], src.device
+    if counts is not None:
+        if counts.dtype != torch.int32 or counts.shape != (B,) or counts.device != dev:
+            raise ValueError(f"counts must be a device int32 tensor [{B}], got {counts.dtype} {tuple(counts.shape)}")
+        counts = counts.contiguous()
+    if checker_distance is None:
+        checker_distance = max_correspondence_distance
+    max_iteration = int(max_iteration)
+    if chunk == 0:
+        chunk = min(lib.gcl_ransac_default_chunk(), max(256, (max_iteration + 255) // 256 * 256))
+    seeds = [_draw_seed(None) for _ in range(B)] if seeds is None else [_draw_seed(s) for s in seeds]
+    if len(seeds) != B:
+        raise ValueError(f"{B} pairs but {len(seeds)} seeds")
+    seed_arr = (ctypes.c_uint64 * B)(*seeds)
+    trans = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    fit = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, n), dtype=torch.float32, device=dev)
+    status = torch.empty((B, max_iteration), dtype=torch.int32, device=dev) if want_status else None
+    scratch = torch.empty(max(lib.gcl_ransac_batch_scratch_bytes(B, n, chunk), 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.gcl_ransac_register_batch(_lib.ptr(src), _lib.ptr(tgt), B, n, _lib.ptr(counts), int(ransac_n),
+                                             float(edge_length_similarity), float(checker_distance),
+                                             float(max_correspondence_distance), max_iteration, float(confidence), seed_arr,
+                                             int(chunk), _lib.ptr(scratch), _lib.ptr(trans), _lib.ptr(info), _lib.ptr(fit),
+                                             _lib.ptr(labels), _lib.ptr(status), _lib.stream()),
+               "gcl_ransac_register_batch")
+    return BatchRegistrationResult(trans, fit, info, labels, counts, src, tgt, status)
+
+
+def mutual_correspondences(xyz0, xyz1, F0, F1, min_count, src_out=None, tgt_out=None, count_out=None):
+    """open3d's correspondence set under ``mutual_filter=True`` on the device: the feature 1-NN both ways (two ``pdist_min``
+    calls) and ``gcl_mutual_correspondences``.  Returns ``(src [N0, 3], tgt [N0, 3], count int32 [2])``: the mutual pairs as
+    point rows in ascending source order with zero rows behind them and count = (their number, their number), or -- fewer
+    than ``min_count`` of them -- every source beside its nearest target and count = (N0, number of mutual pairs).  The
+    three outputs may be given (slices of a batch's buffers)."""
+    lib = _lib.require_gpu()
+    xyz0, xyz1 = xyz0.detach().to(torch.float32).contiguous(), xyz1.detach().to(torch.float32).contiguous()
+    m0, m1, dev = xyz0.shape[0], xyz1.shape[0], xyz0.device
+    _, nn01 = pdist_min(F0, F1, "SquareL2")
+    _, nn10 = pdist_min(F1, F0, "SquareL2")
+    src = torch.empty((m0, 3), dtype=torch.float32, device=dev) if src_out is None else src_out
+    tgt = torch.empty((m0, 3), dtype=torch.float32, device=dev) if tgt_out is None else tgt_out
+    count = torch.empty(2, dtype=torch.int32, device=dev) if count_out is None else count_out
+    if tuple(src.shape) != (m0, 3) or tuple(tgt.shape) != (m0, 3) or tuple(count.shape) != (2,):
+        raise ValueError("mutual_correspondences: outputs must be [N0, 3], [N0, 3] and [2]")
+    _lib.check(lib.gcl_mutual_correspondences(_lib.ptr(nn01, torch.int32), m0, _lib.ptr(nn10, torch.int32), m1, _lib.ptr(xyz0),
+                                              _lib.ptr(xyz1), int(min_count), _lib.ptr(src, torch.float32),
+                                              _lib.ptr(tgt, torch.float32), _lib.ptr(count, torch.int32), _lib.stream()),
+               "gcl_mutual_correspondences")
+    return src, tgt, count
+
+
+def registration_ransac_based_on_mutual_feature_matching(xyz0, xyz1, F0, F1, max_correspondence_distance=0.3, ransac_n=4,
+                                                         edge_length_similarity=0.9, checker_distance=None,
+                                                         max_iteration=4000000, confidence=0.999, seed=None):
+    """open3d's ``registration_ransac_based_on_feature_matching(..., mutual_filter=True)`` (its default since 0.13) for one
+    pair: a source is kept when its feature-nearest target has it as ITS nearest source; with fewer than ``ransac_n`` such
+    pairs open3d falls back to every source with its nearest target.  The number of correspondences never leaves the
+    device: the registration reads it there.  Returns a ``BatchRegistrationResult`` of one pair (``[1, ...]`` tensors, zero
+    rows beyond the count) whose ``count`` and ``n_mutual`` are device scalars."""
+    _lib.require_gpu()
+    dev = xyz0.device
+    src = torch.empty((1, xyz0.shape[0], 3), dtype=torch.float32, device=dev)
+    tgt = torch.empty_like(src)
+    cnt = torch.empty((1, 2), dtype=torch.int32, device=dev)
+    mutual_correspondences(xyz0, xyz1, F0, F1, ransac_n, src[0], tgt[0], cnt[0])
+    res = ransac_correspondences_batch(src, tgt, max_correspondence_distance, ransac_n, edge_length_similarity,
+                                       checker_distance, max_iteration, confidence, cnt[:, 0].contiguous(), [_draw_seed(seed)])
+    res.count, res.n_mutual = cnt[0, 0], cnt[0, 1]
+    return res
+
+
 def registration_ransac_based_on_feature_matching(xyz0, xyz1, F0, F1, mutual_filter=False, max_correspondence_distance=0.3,
                                                   ransac_n=4, edge_length_similarity=0.9, checker_distance=None,
                                                   max_iteration=4000000, confidence=0.999, seed=None):
@@ -88,8 +194,9 @@ def registration_ransac_based_on_feature_matching(xyz0, xyz1, F0, F1, mutual_fil
     estimation is point-to-point without scaling and the checkers are the two the reference passes (edge length,
     distance; ``checker_distance`` None = ``max_correspondence_distance``, as in both of its call sites)."""
     if mutual_filter:
-        raise NotImplementedError("mutual_filter=True is not built: the number of correspondences would have to live on "
-                                  "the device (the reference passes False at both call sites)")
+        raise NotImplementedError("mutual_filter=True is not served by this function: call "
+                                  "registration_ransac_based_on_mutual_feature_matching, which keeps the number of "
+                                  "correspondences on the device (the reference passes False at both call sites)")
     _lib.require_gpu()
     _, arg = pdist_min(F0, F1, "SquareL2")
     tgt = xyz1.to(torch.float32)[arg.long()]
@@ -98,7 +205,10 @@ def registration_ransac_based_on_feature_matching(xyz0, xyz1, F0, F1, mutual_fil
 
 
 class FeatureRansac:
-    """The RANSAC branch as a ``Matcher``: ``estimator`` has ``Matcher.estimator``'s contract, batch size 1.
+    """The RANSAC branch as a ``Matcher``: ``estimator`` has ``Matcher.estimator``'s contract for any batch size.  One pair
+    without the mutual filter is one ``gcl_ransac_register`` call; a batch, or ``mutual_filter=True`` (open3d's default since
+    0.13; the reference passes False), is ONE ``gcl_ransac_register_batch`` call behind the pairs' 1-NN searches, and the
+    returned tensors are [B, ...] with zero rows beyond a pair's correspondence count.
 
     NOTE on ``confidence``: the default everywhere here, ``kitti()`` and ``eth()`` included, is open3d's own default 0.999,
     which stops a run once enough hypotheses have been drawn for the best inlier share found (0.3 ms instead of 0.8 ms per
@@ -108,31 +218,66 @@ class FeatureRansac:
     ``confidence=1.0``."""
 
     def __init__(self, max_correspondence_distance, ransac_n=4, edge_length_similarity=0.9, checker_distance=None,
-                 max_iteration=4000000, confidence=0.999, seed=None):
+                 max_iteration=4000000, confidence=0.999, seed=None, mutual_filter=False):
         self.max_correspondence_distance, self.ransac_n = float(max_correspondence_distance), int(ransac_n)
         self.edge_length_similarity = float(edge_length_similarity)
         self.checker_distance = self.max_correspondence_distance if checker_distance is None else float(checker_distance)
         self.max_iteration, self.confidence, self.seed = int(max_iteration), float(confidence), seed
+        self.mutual_filter = bool(mutual_filter)
         self.last = None
 
+    accepts_batch = True      # scripts/eval_batch.eval_pairs(..., batch_registration=True) asks for this
+
+    def draw_seed(self):
+        """The seed of the next registration (``np.random`` when none was given): what ``estimator`` draws per pair."""
+        return _draw_seed(self.seed)
+
     @classmethod
-    def kitti(cls, voxel_size, confidence=0.999, seed=None):
+    def kitti(cls, voxel_size, confidence=0.999, seed=None, mutual_filter=False):
         """scripts/test_kitti.py:170-177: ransac_n 4, both distances one voxel, 4 000 000 iterations.  (The reference's
         second criterion argument, 10000, is ``max_validation`` of older open3d; open3d >= 0.13 reads it as a confidence
         and clamps it to 1, i.e. no early stop: pass ``confidence=1.0`` for that behaviour.)"""
-        return cls(voxel_size * 1.0, 4, 0.9, None, 4000000, confidence, seed)
+        return cls(voxel_size * 1.0, 4, 0.9, None, 4000000, confidence, seed, mutual_filter)
 
     @classmethod
-    def eth(cls, confidence=0.999, seed=None):
+    def eth(cls, confidence=0.999, seed=None, mutual_filter=False):
         """generalization_ETH/evaluate.py:180-186: ransac_n 3, both distances 0.05, 50 000 iterations."""
-        return cls(0.05, 3, 0.9, 0.05, 50000, confidence, seed)
+        return cls(0.05, 3, 0.9, 0.05, 50000, confidence, seed, mutual_filter)
 
-    def estimator(self, src_keypts, tgt_keypts, src_features, tgt_features):
+    def estimator(self, src_keypts, tgt_keypts, src_features, tgt_features, seeds=None):
+        """``seeds``: one per pair, for a caller that has drawn them already (``draw_seed``, in its own order of host
+        draws); None: drawn here, in pair order."""
         _lib.require_gpu()
-        if src_keypts.shape[0] != 1:
-            raise NotImplementedError("batch size 1 only (as Matcher.estimator)")
-        res = registration_ransac_based_on_feature_matching(
-            src_keypts[0], tgt_keypts[0], src_features[0], tgt_features[0], False, self.max_correspondence_distance,
-            self.ransac_n, self.edge_length_similarity, self.checker_distance, self.max_iteration, self.confidence, self.seed)
+        B = src_keypts.shape[0]
+        if B < 1:
+            raise ValueError("estimator needs at least one pair")
+        if seeds is not None and len(seeds) != B:
+            raise ValueError(f"{B} pairs but {len(seeds)} seeds")
+        if B == 1 and not self.mutual_filter:
+            res = registration_ransac_based_on_feature_matching(
+                src_keypts[0], tgt_keypts[0], src_features[0], tgt_features[0], False, self.max_correspondence_distance,
+                self.ransac_n, self.edge_length_similarity, self.checker_distance, self.max_iteration, self.confidence,
+                self.seed if seeds is None else seeds[0])
+            self.last = res
+            return res.transformation[None], res.labels[None], res.src_corr[None], res.tgt_corr[None]
+        dev = src_keypts.device
+        src = torch.empty((B, src_keypts.shape[1], 3), dtype=torch.float32, device=dev)
+        tgt = torch.empty_like(src)
+        cnt = torch.empty((B, 2), dtype=torch.int32, device=dev) if self.mutual_filter else None
+        for b in range(B):
+            if self.mutual_filter:
+                mutual_correspondences(src_keypts[b], tgt_keypts[b], src_features[b], tgt_features[b], self.ransac_n, src[b],
+                                       tgt[b], cnt[b])
+            else:
+                _, arg = pdist_min(src_features[b], tgt_features[b], "SquareL2")
+                src[b] = src_keypts[b]
+                tgt[b] = tgt_keypts[b].to(torch.float32)[arg.long()]
+        if seeds is None:
+            seeds = [self.draw_seed() for _ in range(B)]
+        res = ransac_correspondences_batch(src, tgt, self.max_correspondence_distance, self.ransac_n,
+                                           self.edge_length_similarity, self.checker_distance, self.max_iteration,
+                                           self.confidence, None if cnt is None else cnt[:, 0].contiguous(), seeds)
+        if cnt is not None:
+            res.count, res.n_mutual = cnt[:, 0], cnt[:, 1]
         self.last = res
-        return res.transformation[None], res.labels[None], res.src_corr[None], res.tgt_corr[None]
+        return res.transformation, res.labels, res.src_corr, res.tgt_corr

@@ -24,7 +24,7 @@
  *        -> gcl_nn_rowmin, gcl_sc2_*
  *   open3d registration_ransac_based_on_feature_matching   scripts/test_kitti.py:171-178,
  *                                                    generalization_ETH/evaluate.py:171-186
- *        -> gcl_nn_rowmin, gcl_ransac_register
+ *        -> gcl_nn_rowmin, gcl_ransac_register, gcl_ransac_register_batch, gcl_mutual_correspondences
  *   find_nearest_voxel_feature, calculate_M, inlier ratio   generalization_ETH/evaluate.py:63-77, :110-122, :160-169
  *        -> gcl_nn3_rowmin, gcl_nn_rowmin, gcl_mutual_match
  *
@@ -539,6 +539,16 @@ int gcl_nn3_rowmin(const float* q, int32_t m, const float* p, int32_t n, const f
  * m0 == 0 writes stats = {0, 0}. */
 int gcl_mutual_match(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32_t m1, const float* kp0, const float* kp1,
                      const float* T, float tau, int32_t* pairs, int32_t* stats, void* stream);
+/* The correspondences of a registration under open3d's mutual filter (registration_ransac_based_on_feature_matching with
+ * mutual_filter = true), as point rows, their number left on the device.  nn01 / nn10 as gcl_mutual_match takes them (an
+ * entry outside the range is never mutual and never dereferenced), xyz0 float [m0, 3], xyz1 float [m1, 3].  Let M be the
+ * pairs (i, nn01[i]) with nn10[nn01[i]] == i in ascending i.  |M| >= min_count: row k of src / tgt (float [m0, 3]) is
+ * xyz0[i_k] / xyz1[j_k], rows from |M| on are zero, count (int32 [2]) = {|M|, |M|}.  Otherwise open3d's fall-back to the
+ * original correspondences: row i is xyz0[i] / xyz1[nn01[i]] (a zero target row where nn01[i] is out of range) and
+ * count = {m0, |M|}.  count[0] is what gcl_ransac_register_batch takes as a pair's n_dev entry, and src / tgt / count may be
+ * slices of a batch's buffers: nothing is read back.  Ordered compaction by one workgroup: the same list on every run. */
+int gcl_mutual_correspondences(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32_t m1, const float* xyz0,
+                               const float* xyz1, int32_t min_count, float* src, float* tgt, int32_t* count, void* stream);
 
 /* keep[r] = (sel1[r] != sel2[arg[r]]) && the pair {sel1[r], sel2[arg[r]]} shares no positive group
  * (equivalent to the reference's `~np.isin(_neg_hash(...), index_hash)` :521-529: the symmetric key is
@@ -649,6 +659,26 @@ int gcl_ransac_register(const float* src, const float* tgt, int32_t n, int32_t r
                         float check_distance, float max_corr_distance, int32_t max_iteration, float confidence,
                         uint64_t seed, int32_t chunk, void* scratch, float* trans16, int32_t* info, float* fit,
                         float* labels, int32_t* hyp_status, void* stream);
+/* The same registration for a BATCH of pairs in the launches of one: src / tgt float [batch, n_cap, 3], every kernel takes
+ * the pair as a grid dimension, the chunk loop is enqueued once for all pairs.  Pair b runs on its first n_b correspondences,
+ * n_b = n_dev[b] read ON THE DEVICE (device int32 [batch]; a negative value reads as 0, one above n_cap as n_cap; NULL: n_cap
+ * for every pair) -- the host never knows it, so it may be the count gcl_mutual_correspondences has just written.  Rows at or
+ * beyond n_b are never read.  seeds is a HOST array [batch] (copied into the launch arguments).  Outputs per pair:
+ * trans16 [batch, 16], info [batch, 4], fit [batch, 2] (count / n_b), labels [batch, n_cap] (optional; 0 from n_b on),
+ * hyp_status [batch, max_iteration] (optional).  For n_b >= ransac_n every output of pair b is bitwise what
+ * gcl_ransac_register gives for those n_b correspondences and seeds[b], whatever else is in the batch and whatever n_cap is
+ * (gcl_ransac_register IS a batch of one).  The confidence stop is per pair: a pair past its own limit does nothing in later
+ * chunks (status -4) while the others go on.  n_b < ransac_n (possible only with n_dev): nothing is drawn; identity,
+ * info = {-1, 0, 0, 0}, fit = {0, 0}, labels 0, every status -4.
+ * SCRATCH FOOTPRINT: gcl_ransac_batch_scratch_bytes(batch, n_cap, chunk) = batch x gcl_ransac_scratch_bytes(n_cap, chunk):
+ * every pair has its own control block and its own slice of the single-pair layout, ~ 150 bytes per hypothesis of a chunk,
+ * i.e. about 40 MB PER PAIR at the default chunk of 262 144 (320 MB for 8 pairs); a smaller chunk shrinks it in proportion.
+ * 1 <= batch <= 65535, ransac_n <= n_cap <= 2^24; the query returns 0 for arguments outside these ranges. */
+int64_t gcl_ransac_batch_scratch_bytes(int32_t batch, int32_t n_cap, int32_t chunk);
+int gcl_ransac_register_batch(const float* src, const float* tgt, int32_t batch, int32_t n_cap, const int32_t* n_dev,
+                              int32_t ransac_n, float edge_similarity, float check_distance, float max_corr_distance,
+                              int32_t max_iteration, float confidence, const uint64_t* seeds, int32_t chunk, void* scratch,
+                              float* trans16, int32_t* info, float* fit, float* labels, int32_t* hyp_status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native step runtime (round 3): ONE call enqueues a whole pass.
