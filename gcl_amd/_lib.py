@@ -153,6 +153,9 @@ SIGNATURES = {
     "gcl_sc2_register_scratch_bytes": (_i64, [_i32]),
     "gcl_sc2_register": (_i32, [_vp, _vp, _i32, _f32, _i32, _f32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp]),
+    "gcl_sc2_register_batch_scratch_bytes": (_i64, [_i32, _i32]),
+    "gcl_sc2_register_batch": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f32, _i32, _f32, _i32, _i32, _f32, _f32, _i32, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gcl_sc2_local_max": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp]),
     "gcl_sc2_seed_knn": (_i32, [_vp, _vp, _i32, _vp, _i32, _f32, _i32, _vp, _vp, _vp]),
     "gcl_sc2_seed_trans": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _f32, _vp, _vp, _vp]),

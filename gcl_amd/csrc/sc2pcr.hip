@@ -10,6 +10,8 @@
 // k2 = 20, 20 x 20 power iteration, weighted Kabsch with a 3 x 3 Jacobi SVD) runs as one wavefront per seed.
 // Ties (argsort / argmax of equal values, unspecified in the reference) go to the LOWEST index; per-seed power
 // iterations always run num_iterations steps (see oracle/sc2pcr_oracle.py).
+// A BATCH of pairs (gcl_sc2_register_batch) runs the same kernel bodies with the pair as the grid's z dimension; see the
+// kernels behind the bodies, below.
 #include "common.h"
 #include "kabsch.h"
 
@@ -88,9 +90,9 @@ __device__ __forceinline__ float sc_first_order(const P3& si, const P3& ti, cons
 // owns the words that START in it, and holds the up to 63 columns beyond its end that such a word needs.
 constexpr int SB_ROWS = 16;
 constexpr int SB_PER_MAX = SC_MAXN / SC_CHUNKS;
-__global__ void __launch_bounds__(256) k_sc_sparse_build(const float* __restrict__ src, const float* __restrict__ tgt, int n,
-                                                         float d2_thre, int* count, ScEntry* entries, float tight_thr,
-                                                         unsigned long long* bits) {
+__device__ __forceinline__ void sc_sparse_build(const float* __restrict__ src, const float* __restrict__ tgt, int n,
+                                                float d2_thre, int* count, ScEntry* entries, float tight_thr,
+                                                unsigned long long* bits) {
   __shared__ float cs[6][SB_PER_MAX + 128];
   const int per = (n + SC_CHUNKS - 1) / SC_CHUNKS;
   const int j0 = blockIdx.y * per, j1 = min(n, j0 + per);
@@ -142,9 +144,9 @@ __global__ void __launch_bounds__(256) k_sc_sparse_build(const float* __restrict
 // two-kernel form writes.  When the test sets `done` the other workgroups of that launch may still write a (never read)
 // partial; x then stays at the converged vector as in the reference's `break` (:181).
 template <bool FIRST>
-__global__ void __launch_bounds__(SC_TILE) k_sc_matvec_folded(int n, float* x, int* done, const float* __restrict__ prev,
-                                                              float* __restrict__ partial, const int* __restrict__ count,
-                                                              const ScEntry* __restrict__ entries) {
+__device__ __forceinline__ void sc_matvec_folded(int n, float* x, int* done, const float* __restrict__ prev,
+                                                 float* __restrict__ partial, const int* __restrict__ count,
+                                                 const ScEntry* __restrict__ entries) {
   if (*done) return;
   __shared__ float xs[SC_MAXN];
   __shared__ float red[1024];
@@ -273,8 +275,8 @@ __global__ void __launch_bounds__(1024) k_sc_normalize(const float* __restrict__
 // writer stores 0).  Workgroup (bx, y) takes row tile bx against column tile (bx + y) mod tiles, y = 0 .. tiles / 2: every
 // unordered pair of tiles exactly once (y = 0: the columns behind the row only; y = tiles / 2 of an even count: the lower
 // half of bx only), one tile pair per workgroup so that the launch balances.
-__global__ void __launch_bounds__(SC_TILE) k_sc_local_max(const float* __restrict__ src, const float* __restrict__ conf,
-                                                          int n, float radius, int* is_max) {
+__device__ __forceinline__ void sc_local_max(const float* __restrict__ src, const float* __restrict__ conf, int n,
+                                             float radius, int* is_max) {
   __shared__ float ts[SC_TILE][4];
   const int n_tiles = (n + SC_TILE - 1) / SC_TILE;
   const int y = blockIdx.y;
@@ -427,10 +429,10 @@ __global__ void __launch_bounds__(256) k_sc_seed_knn(const float* __restrict__ s
 // the values go to vals[seed][column] (uint16: a count is <= n <= 8192) and k_sc_seed_topk makes the same selection from them.
 // Integers throughout: the k1 lists are those of k_sc_seed_knn (tests: one call == staged calls, bit for bit).
 constexpr int SK_TS = 16;
-__global__ void __launch_bounds__(256) k_sc_seed_sc2(const float* __restrict__ src, const float* __restrict__ tgt,
-                                                     const unsigned long long* __restrict__ bits, int n, int words,
-                                                     const long long* __restrict__ seeds, int n_seeds, float d_thre,
-                                                     unsigned short* __restrict__ vals) {
+__device__ __forceinline__ void sc_seed_sc2(const float* __restrict__ src, const float* __restrict__ tgt,
+                                            const unsigned long long* __restrict__ bits, int n, int words,
+                                            const long long* __restrict__ seeds, int n_seeds, float d_thre,
+                                            unsigned short* __restrict__ vals) {
   __shared__ unsigned short out[SK_TS][SB_PER_MAX];
   __shared__ unsigned short lst[SB_PER_MAX], hm[SB_PER_MAX];
   __shared__ float sp[SK_TS][6];
@@ -536,7 +538,7 @@ __device__ __forceinline__ unsigned sc_wave_umax(unsigned v) {
   const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
   return max(max(a, b), max(c, d));
 }
-__global__ void __launch_bounds__(64) k_sc_seed_topk(const unsigned short* __restrict__ vals, int n, int k1, int* knn) {
+__device__ __forceinline__ void sc_seed_topk(const unsigned short* __restrict__ vals, int n, int k1, int* knn) {
   __shared__ unsigned short row[SC_MAXN];
   const int lane = threadIdx.x;
   const unsigned short* g = vals + (size_t)blockIdx.x * n;
@@ -568,9 +570,9 @@ __global__ void __launch_bounds__(64) k_sc_seed_topk(const unsigned short* __res
 // ---- 3 x 3 SVD (one-sided Jacobi, fp64) and the weighted Kabsch solution (common.py:7-45): kabsch_from_H, csrc/kabsch.h ----
 
 // ---- per seed: local consensus, power iteration, weighted transformation (:60-147), one wave per seed ---------
-__global__ void __launch_bounds__(64) k_sc_seed_trans(const float* __restrict__ src, const float* __restrict__ tgt,
-                                                      const int* __restrict__ knn, int k1, int k2, float d_thre,
-                                                      int num_iterations, float* trans) {
+__device__ __forceinline__ void sc_seed_trans(const float* __restrict__ src, const float* __restrict__ tgt,
+                                              const int* __restrict__ knn, int k1, int k2, float d_thre,
+                                              int num_iterations, float* trans) {
   __shared__ float ps[32][3], pt[32][3], fs[32][3], ft[32][3], xv[32];
   __shared__ unsigned rowbits[32];
   const int lane = threadIdx.x, s = blockIdx.x;
@@ -723,6 +725,33 @@ __global__ void k_sc_refine_solve(const double* __restrict__ partial, int* state
   kabsch_from_H(H, ca, cb, T);
 }
 
+// |T p - q|^2 with the contraction spelt out (contraction off), for the BATCH kernels of the inlier count and the refinement: the
+// single-pair kernels k_sc_fitness and k_sc_refine_all leave `T[0] * p.x + T[1] * p.y + ...` to the compiler, and which product it
+// rounds before the fma differs between a kernel and the same source inlined into another -- a residual then differs in its
+// last bit, a point within rounding of the threshold changes sides.  So those two kernels (and k_sc_seed_trans, for its Kabsch
+// step) keep their own source, untouched, and the batch kernels compute what THEY were compiled to (read off their gfx950 code):
+//   `packed` (all of a thread's points in k_sc_fitness but an odd last one):
+//     x = fma(T2, pz, fma(T0, px, T1 py)) + T3 - qx,  y, z alike,  d2 = fma(dz, dz, fma(dx, dx, dy dy))
+//   otherwise (that odd last point; every point of k_sc_refine_all):
+//     x = fma(pz, T2, fma(py, T1, T0 px)) + T3 - qx,  y = ((fma(T4, px, T5 py) + T6 pz) + T7) - qy,
+//     z = fma(pz, T10, fma(px, T8, T9 py)) + T11 - qz,  d2 = fma(dy, dy, dx dx) + dz dz
+// A compiler that builds those two kernels differently needs the forms read off again; tests/test_gpu_sc2_batch.py compares
+// the batch's fitness counts, hypotheses and transformations with the single call's bit for bit.
+__device__ __forceinline__ float sc_residual2(const float* T, const P3& p, const P3& q, bool packed) {
+#pragma clang fp contract(off)
+  float x, y, z;
+  if (packed) {
+    x = __builtin_fmaf(T[2], p.z, __builtin_fmaf(T[0], p.x, T[1] * p.y));
+    y = __builtin_fmaf(T[6], p.z, __builtin_fmaf(T[4], p.x, T[5] * p.y));
+    z = __builtin_fmaf(T[10], p.z, __builtin_fmaf(T[8], p.x, T[9] * p.y));
+  } else {
+    x = __builtin_fmaf(p.z, T[2], __builtin_fmaf(p.y, T[1], T[0] * p.x));
+    y = __builtin_fmaf(T[4], p.x, T[5] * p.y) + T[6] * p.z;
+    z = __builtin_fmaf(p.z, T[10], __builtin_fmaf(p.x, T[8], T[9] * p.y));
+  }
+  const float dx = (x + T[3]) - q.x, dy = (y + T[7]) - q.y, dz = (z + T[11]) - q.z;
+  return packed ? __builtin_fmaf(dz, dz, __builtin_fmaf(dx, dx, dy * dy)) : __builtin_fmaf(dy, dy, dx * dx) + dz * dz;
+}
 // The whole refinement in ONE launch (round 5): a single 1024-thread workgroup runs the iterations and stops at convergence
 // (the two-kernel form launched 2 x 20 kernels per registration, most of them no-ops behind the `done` flag once the inlier
 // count stands still: 0.3 ms of dependent launches per pair).  A thread owns points t, t + 1024, ... and sums their 17
@@ -730,6 +759,273 @@ __global__ void k_sc_refine_solve(const double* __restrict__ partial, int* state
 // in wave order by thread 0 -- a fixed order, so the result is reproducible; it is NOT the summation order of the two-kernel
 // form (64 blocks of 256, a halving tree each): the fp64 sums may differ in their last bits, the fp32 transformation
 // practically never (tests/test_gpu_parity.py compares the two forms on the golden problems).
+__device__ __forceinline__ void sc_refine_all(const float* __restrict__ src, const float* __restrict__ tgt, int n,
+                                              float thr, int iterations, int* state, float* T) {
+  __shared__ double ws[16][RF_TERMS];
+  __shared__ float Ts[12];
+  __shared__ int done;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (t < 12) Ts[t] = T[t];
+  if (t == 0) done = 0;
+  int prev = 0;      // thread 0's
+  __syncthreads();
+  for (int it = 0; it < iterations; ++it) {
+    double acc[RF_TERMS];
+#pragma unroll
+    for (int k = 0; k < RF_TERMS; ++k) acc[k] = 0;
+    for (int j = t; j < n; j += 1024) {
+      const P3 p = ld3(src, j), q = ld3(tgt, j);
+      const float d = sqrtf(sc_residual2(Ts, p, q, false));      // k_sc_refine_all's contraction of the residual, spelt out
+      if (d < thr) {
+        const float r = d / thr;
+        const double wgt = 1.f / (1.f + r * r);
+        const double a[3] = {p.x, p.y, p.z}, b[3] = {q.x, q.y, q.z};
+        acc[0] += wgt;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { acc[1 + c] += wgt * a[c]; acc[4 + c] += wgt * b[c]; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int k = 0; k < 3; ++k) acc[7 + 3 * i + k] += wgt * a[i] * b[k];
+        acc[16] += 1.0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < RF_TERMS; ++k) {
+      double v = acc[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) ws[w][k] = v;
+    }
+    __syncthreads();
+    if (t == 0) {
+      double s[RF_TERMS];
+      for (int k = 0; k < RF_TERMS; ++k) {
+        double v = 0;
+        for (int u = 0; u < 16; ++u) v += ws[u][k];
+        s[k] = v;
+      }
+      const int cnt = (int)s[16];
+      if (abs(cnt - prev) < 1) {      // :266-267
+        done = 1;
+      } else {
+        prev = cnt;
+        const double sw = s[0] + 1e-6;      // common.py:22-23
+        double ca[3], cb[3], H[9];
+        for (int c = 0; c < 3; ++c) { ca[c] = s[1 + c] / sw; cb[c] = s[4 + c] / sw; }
+        for (int i = 0; i < 3; ++i)
+          for (int k = 0; k < 3; ++k)
+            H[3 * i + k] = s[7 + 3 * i + k] - ca[i] * s[4 + k] - s[1 + i] * cb[k] + s[0] * ca[i] * cb[k];
+        float Tn[12];
+        kabsch_from_H(H, ca, cb, Tn);
+        for (int k = 0; k < 12; ++k) Ts[k] = Tn[k];
+      }
+    }
+    __syncthreads();
+    if (done) break;
+  }
+  if (t < 12) T[t] = Ts[t];
+  if (t == 0) { state[0] = done; state[1] = prev; }
+}
+
+// ---- one call per registration (round 5): what scripts/SC2_PCR.py did between the stages, on the device ------------------------
+__device__ __forceinline__ void sc_reg_init(float* conf, int* is_max, int* rank, int* done, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    conf[i] = 1.f;
+    is_max[i] = 1;
+    rank[i] = 0;
+  }
+  if (i == 0) *done = 0;
+}
+
+// seeds = the n_seeds first of argsort(-(conf * is_max), stable) (:56-58): value descending, index ascending.  By RANK: the
+// place of correspondence i is the number of correspondences ordered before it -- n^2 comparisons spread over the chip
+// (row tiles x SC_CHUNKS column chunks, integer atomics: any order gives the same count) -- then seeds[rank[i]] = i.  (A
+// bitonic sort in LDS by one workgroup was the first form: 111 us; torch's sort took 45 us in four launches.)  NaN last, as
+// torch.sort places it.
+__device__ __forceinline__ unsigned sc_seed_key(const float* __restrict__ conf, const int* __restrict__ is_max, int i) {
+  float v = conf[i] * (float)is_max[i];
+  if (v == 0.f) v = 0.f;                                                // -0 and +0 are one value to the reference's sort
+  const unsigned b = __float_as_uint(v);
+  const unsigned asc = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);     // ascending in v
+  return (v != v) ? 0xFFFFFFFFu : ~asc;                                 // ascending key = descending value
+}
+__device__ __forceinline__ void sc_seed_rank(const float* __restrict__ conf, const int* __restrict__ is_max, int n,
+                                             int* rank) {
+  __shared__ unsigned tk[SC_TILE];
+  const int i = blockIdx.x * SC_TILE + threadIdx.x;
+  const bool ok = i < n;
+  const unsigned ki = ok ? sc_seed_key(conf, is_max, i) : 0u;
+  const int per = (n + SC_CHUNKS - 1) / SC_CHUNKS;
+  const int j0 = blockIdx.y * per, j1 = min(n, j0 + per);
+  int before = 0;
+  for (int jb = j0; jb < j1; jb += SC_TILE) {
+    __syncthreads();
+    if (jb + (int)threadIdx.x < j1) tk[threadIdx.x] = sc_seed_key(conf, is_max, jb + threadIdx.x);
+    __syncthreads();
+    const int m = min(SC_TILE, j1 - jb);
+    for (int q = 0; q < m; ++q) {
+      const unsigned kj = tk[q];
+      before += (kj < ki || (kj == ki && jb + q < i)) ? 1 : 0;
+    }
+  }
+  if (ok && before) atomicAdd(&rank[i], before);
+}
+__device__ __forceinline__ void sc_seed_place(const int* __restrict__ rank, int n, int n_seeds,
+                                              long long* __restrict__ seeds) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && rank[i] < n_seeds) seeds[rank[i]] = i;
+}
+
+// best = lowest index of the maximum fitness (torch.sort(-fitness, stable)[1][0]); T = that seed's [R | t]
+__device__ __forceinline__ void sc_best(const float* __restrict__ fitness, const float* __restrict__ trans, int n_seeds,
+                                        int* best_out, float* T) {
+  __shared__ float bv[256];
+  __shared__ int bi[256];
+  float v = -INFINITY;
+  int ix = 0x7fffffff;
+  for (int i = threadIdx.x; i < n_seeds; i += 256) {      // ascending i per thread: the first maximum is the lowest index
+    const float f = fitness[i];
+    if (ix == 0x7fffffff || f > v) { v = f; ix = i; }
+  }
+  bv[threadIdx.x] = v;
+  bi[threadIdx.x] = ix;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const float v2 = bv[threadIdx.x + o];
+      const int i2 = bi[threadIdx.x + o];
+      if (i2 != 0x7fffffff && (bi[threadIdx.x] == 0x7fffffff || v2 > bv[threadIdx.x] ||
+                               (v2 == bv[threadIdx.x] && i2 < bi[threadIdx.x]))) {
+        bv[threadIdx.x] = v2;
+        bi[threadIdx.x] = i2;
+      }
+    }
+    __syncthreads();
+  }
+  const int best = bi[0];
+  if (threadIdx.x == 0) *best_out = best;
+  if (threadIdx.x < 12) T[threadIdx.x] = trans[(size_t)best * 12 + threadIdx.x];
+}
+
+// the [4, 4] transformation and the inlier labels |R s + t - t'| < thr of Matcher.estimator (:404-409)
+__device__ __forceinline__ void sc_finish(const float* __restrict__ src, const float* __restrict__ tgt, int n,
+                                          const float* __restrict__ T, float thr, float* out16, float* labels) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 16) out16[i] = i < 12 ? T[i] : (i == 15 ? 1.f : 0.f);
+  if (i >= n) return;
+  const P3 s = ld3(src, i), g = ld3(tgt, i);
+  const float wx = T[0] * s.x + T[1] * s.y + T[2] * s.z + T[3] - g.x;
+  const float wy = T[4] * s.x + T[5] * s.y + T[6] * s.z + T[7] - g.y;
+  const float wz = T[8] * s.x + T[9] * s.y + T[10] * s.z + T[11] - g.z;
+  labels[i] = sqrtf(wx * wx + wy * wy + wz * wz) < thr ? 1.f : 0.f;
+}
+
+// ---- the kernels of the default one-call form: each body above as the single-pair kernel it was, and once more for a BATCH ------
+// A single-pair kernel is its body with the arguments it always had -- except k_sc_fitness, k_sc_seed_trans and k_sc_refine_all,
+// which keep their own source above (see sc_residual2 for why); sc_seed_trans and sc_refine_all serve the batch alone.  The batch kernels (gcl_sc2_register_batch) run the SAME bodies with the pair as the grid's z dimension: a launch is sized for
+// n_cap correspondences and max(n_seeds) seeds, every workgroup reads its own pair's n / n_seeds from the control block -- a
+// BY-VALUE kernel argument filled from the caller's host arrays: no copy on the stream, no read-back -- points the body at the
+// pair's rows, scratch slot and output rows, and returns at once when it lies beyond the pair's own extent.  Inside the body
+// per, words and the tile counts come from that n as in a single call, so a pair's results do not depend on its neighbours.
+__global__ void __launch_bounds__(256) k_sc_sparse_build(const float* __restrict__ src, const float* __restrict__ tgt, int n,
+                                                         float d2_thre, int* count, ScEntry* entries, float tight_thr,
+                                                         unsigned long long* bits) {
+  sc_sparse_build(src, tgt, n, d2_thre, count, entries, tight_thr, bits);
+}
+template <bool FIRST>
+__global__ void __launch_bounds__(SC_TILE) k_sc_matvec_folded(int n, float* x, int* done, const float* __restrict__ prev,
+                                                              float* __restrict__ partial, const int* __restrict__ count,
+                                                              const ScEntry* __restrict__ entries) {
+  sc_matvec_folded<FIRST>(n, x, done, prev, partial, count, entries);
+}
+__global__ void __launch_bounds__(SC_TILE) k_sc_local_max(const float* __restrict__ src, const float* __restrict__ conf,
+                                                          int n, float radius, int* is_max) {
+  sc_local_max(src, conf, n, radius, is_max);
+}
+__global__ void __launch_bounds__(256) k_sc_seed_sc2(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                     const unsigned long long* __restrict__ bits, int n, int words,
+                                                     const long long* __restrict__ seeds, int n_seeds, float d_thre,
+                                                     unsigned short* __restrict__ vals) {
+  sc_seed_sc2(src, tgt, bits, n, words, seeds, n_seeds, d_thre, vals);
+}
+__global__ void __launch_bounds__(64) k_sc_seed_topk(const unsigned short* __restrict__ vals, int n, int k1, int* knn) {
+  sc_seed_topk(vals, n, k1, knn);
+}
+// the single-pair kernel as it always was: its sums of products are left to the compiler, whose choices differ between
+// this kernel and the body inlined into the batch kernel (see k_scb_fitness), so the two do not share source
+__global__ void __launch_bounds__(64) k_sc_seed_trans(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                      const int* __restrict__ knn, int k1, int k2, float d_thre,
+                                                      int num_iterations, float* trans) {
+  __shared__ float ps[32][3], pt[32][3], fs[32][3], ft[32][3], xv[32];
+  __shared__ unsigned rowbits[32];
+  const int lane = threadIdx.x, s = blockIdx.x;
+  if (lane < k1) {
+    const int r = knn[s * k1 + lane];
+    for (int a = 0; a < 3; ++a) { ps[lane][a] = src[3 * r + a]; pt[lane][a] = tgt[3 * r + a]; }
+  }
+  __syncthreads();
+  unsigned rb = 0;
+  if (lane < k1)
+    for (int b = 0; b < k1; ++b) {
+      const float cd = fabsf(dist3(P3{ps[lane][0], ps[lane][1], ps[lane][2]}, P3{ps[b][0], ps[b][1], ps[b][2]}) -
+                             dist3(P3{pt[lane][0], pt[lane][1], pt[lane][2]}, P3{pt[b][0], pt[b][1], pt[b][2]}));
+      rb |= (unsigned)(cd < d_thre) << b;
+    }
+  if (lane < 32) rowbits[lane] = lane < k1 ? rb : 0u;
+  __syncthreads();
+  // local second-order score (:97) and its k2 largest (value desc, index asc): rank = position in the fine list
+  const int score = lane < k1 ? __popc(rowbits[0] & rb) : -1;
+  int rank = 0;
+  for (int c = 0; c < k1; ++c) {
+    const int sc = __popc(rowbits[0] & rowbits[c]);
+    rank += (sc > score || (sc == score && c < lane)) ? 1 : 0;
+  }
+  if (lane < k1 && rank < k2)
+    for (int a = 0; a < 3; ++a) { fs[rank][a] = ps[lane][a]; ft[rank][a] = pt[lane][a]; }
+  __syncthreads();
+  // soft 20 x 20 measure with zero diagonal (:119-131); lane p keeps row p
+  float M[32];
+#pragma unroll
+  for (int q = 0; q < 32; ++q) {
+    float m = 0.f;
+    if (lane < k2 && q < k2 && q != lane) {
+      const float cd = fabsf(dist3(P3{fs[lane][0], fs[lane][1], fs[lane][2]}, P3{fs[q][0], fs[q][1], fs[q][2]}) -
+                             dist3(P3{ft[lane][0], ft[lane][1], ft[lane][2]}, P3{ft[q][0], ft[q][1], ft[q][2]}));
+      m = fmaxf(1.f - cd * cd / (d_thre * d_thre), 0.f);
+    }
+    M[q] = m;
+  }
+  float x = lane < k2 ? 1.f : 0.f;
+  for (int it = 0; it < num_iterations; ++it) {
+    if (lane < 32) xv[lane] = x;
+    __syncthreads();
+    float y = 0.f;
+#pragma unroll
+    for (int q = 0; q < 32; ++q) y += M[q] * xv[q];
+    const float nrm = sqrtf(wave_sum(lane < k2 ? y * y : 0.f));
+    x = lane < k2 ? y / (nrm + 1e-6f) : 0.f;
+    __syncthreads();
+  }
+  const float w = x / (wave_sum(x) + 1e-6f);                      // :132
+  // weighted Kabsch (common.py:18-33): fp32 centroids and covariance like the reference, SVD in fp64
+  const float sw = wave_sum(w) + 1e-6f;
+  float a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+  if (lane < k2)
+    for (int c = 0; c < 3; ++c) { a[c] = fs[lane][c]; b[c] = ft[lane][c]; }
+  float ca[3], cb[3];
+  for (int c = 0; c < 3; ++c) { ca[c] = wave_sum(a[c] * w) / sw; cb[c] = wave_sum(b[c] * w) / sw; }
+  double H[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) H[3 * i + j] = (double)wave_sum(lane < k2 ? (a[i] - ca[i]) * w * (b[j] - cb[j]) : 0.f);
+  if (lane == 0) {
+    const double cad[3] = {ca[0], ca[1], ca[2]}, cbd[3] = {cb[0], cb[1], cb[2]};
+    kabsch_from_H(H, cad, cbd, trans + 12 * s);
+  }
+}
+// the single-pair kernel as it always was: its sums of products are left to the compiler, whose choices differ between
+// this kernel and the body inlined into the batch kernel (see k_scb_fitness), so the two do not share source
 __global__ void __launch_bounds__(1024) k_sc_refine_all(const float* __restrict__ src, const float* __restrict__ tgt, int n,
                                                         float thr, int iterations, int* state, float* T) {
   __shared__ double ws[16][RF_TERMS];
@@ -801,98 +1097,153 @@ __global__ void __launch_bounds__(1024) k_sc_refine_all(const float* __restrict_
   if (t < 12) T[t] = Ts[t];
   if (t == 0) { state[0] = done; state[1] = prev; }
 }
-
-// ---- one call per registration (round 5): what scripts/SC2_PCR.py did between the stages, on the device ------------------------
-__global__ void k_sc_reg_init(float* conf, int* is_max, int* rank, int* done, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    conf[i] = 1.f;
-    is_max[i] = 1;
-    rank[i] = 0;
-  }
-  if (i == 0) *done = 0;
-}
-
-// seeds = the n_seeds first of argsort(-(conf * is_max), stable) (:56-58): value descending, index ascending.  By RANK: the
-// place of correspondence i is the number of correspondences ordered before it -- n^2 comparisons spread over the chip
-// (row tiles x SC_CHUNKS column chunks, integer atomics: any order gives the same count) -- then seeds[rank[i]] = i.  (A
-// bitonic sort in LDS by one workgroup was the first form: 111 us; torch's sort took 45 us in four launches.)  NaN last, as
-// torch.sort places it.
-__device__ __forceinline__ unsigned sc_seed_key(const float* __restrict__ conf, const int* __restrict__ is_max, int i) {
-  float v = conf[i] * (float)is_max[i];
-  if (v == 0.f) v = 0.f;                                                // -0 and +0 are one value to the reference's sort
-  const unsigned b = __float_as_uint(v);
-  const unsigned asc = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);     // ascending in v
-  return (v != v) ? 0xFFFFFFFFu : ~asc;                                 // ascending key = descending value
-}
+__global__ void k_sc_reg_init(float* conf, int* is_max, int* rank, int* done, int n) { sc_reg_init(conf, is_max, rank, done, n); }
 __global__ void __launch_bounds__(SC_TILE) k_sc_seed_rank(const float* __restrict__ conf, const int* __restrict__ is_max, int n,
                                                           int* rank) {
-  __shared__ unsigned tk[SC_TILE];
-  const int i = blockIdx.x * SC_TILE + threadIdx.x;
-  const bool ok = i < n;
-  const unsigned ki = ok ? sc_seed_key(conf, is_max, i) : 0u;
-  const int per = (n + SC_CHUNKS - 1) / SC_CHUNKS;
-  const int j0 = blockIdx.y * per, j1 = min(n, j0 + per);
-  int before = 0;
-  for (int jb = j0; jb < j1; jb += SC_TILE) {
-    __syncthreads();
-    if (jb + (int)threadIdx.x < j1) tk[threadIdx.x] = sc_seed_key(conf, is_max, jb + threadIdx.x);
-    __syncthreads();
-    const int m = min(SC_TILE, j1 - jb);
-    for (int q = 0; q < m; ++q) {
-      const unsigned kj = tk[q];
-      before += (kj < ki || (kj == ki && jb + q < i)) ? 1 : 0;
-    }
-  }
-  if (ok && before) atomicAdd(&rank[i], before);
+  sc_seed_rank(conf, is_max, n, rank);
 }
 __global__ void k_sc_seed_place(const int* __restrict__ rank, int n, int n_seeds, long long* __restrict__ seeds) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && rank[i] < n_seeds) seeds[rank[i]] = i;
+  sc_seed_place(rank, n, n_seeds, seeds);
 }
-
-// best = lowest index of the maximum fitness (torch.sort(-fitness, stable)[1][0]); T = that seed's [R | t]
 __global__ void __launch_bounds__(256) k_sc_best(const float* __restrict__ fitness, const float* __restrict__ trans, int n_seeds,
                                                  int* best_out, float* T) {
-  __shared__ float bv[256];
-  __shared__ int bi[256];
-  float v = -INFINITY;
-  int ix = 0x7fffffff;
-  for (int i = threadIdx.x; i < n_seeds; i += 256) {      // ascending i per thread: the first maximum is the lowest index
-    const float f = fitness[i];
-    if (ix == 0x7fffffff || f > v) { v = f; ix = i; }
-  }
-  bv[threadIdx.x] = v;
-  bi[threadIdx.x] = ix;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      const float v2 = bv[threadIdx.x + o];
-      const int i2 = bi[threadIdx.x + o];
-      if (i2 != 0x7fffffff && (bi[threadIdx.x] == 0x7fffffff || v2 > bv[threadIdx.x] ||
-                               (v2 == bv[threadIdx.x] && i2 < bi[threadIdx.x]))) {
-        bv[threadIdx.x] = v2;
-        bi[threadIdx.x] = i2;
-      }
-    }
-    __syncthreads();
-  }
-  const int best = bi[0];
-  if (threadIdx.x == 0) *best_out = best;
-  if (threadIdx.x < 12) T[threadIdx.x] = trans[(size_t)best * 12 + threadIdx.x];
+  sc_best(fitness, trans, n_seeds, best_out, T);
 }
-
-// the [4, 4] transformation and the inlier labels |R s + t - t'| < thr of Matcher.estimator (:404-409)
 __global__ void k_sc_finish(const float* __restrict__ src, const float* __restrict__ tgt, int n, const float* __restrict__ T,
                             float thr, float* out16, float* labels) {
+  sc_finish(src, tgt, n, T, thr, out16, labels);
+}
+
+constexpr int SC_GROUP = 32;      // pairs per launch sequence of the batch entry (a longer batch: one sequence per 32 pairs)
+struct ScBatch {
+  const float* src;               // [pairs, n_cap, 3], from the group's first pair on, as every pointer below
+  const float* tgt;
+  char* scratch;                  // pair b's slot: scratch + b * slot
+  size_t slot;
+  size_t o_partial, o_partial2, o_done, o_count, o_entries, o_is_max, o_rank, o_bits, o_T, o_state;      // slabs of a slot
+  float* conf;                    // [pairs, n_cap]
+  long long* seeds;               // [pairs, S]
+  int* knn;                       // [pairs, S, k1]
+  float* seed_trans;              // [pairs, S, 12]
+  float* fitness;                 // [pairs, S]
+  int* best;                      // [pairs]
+  float* trans16;                 // [pairs, 16]
+  float* labels;                  // [pairs, n_cap]
+  int n_cap, S, k1;
+  int n[SC_GROUP], ns[SC_GROUP];  // the pairs' own counts and seed counts
+};
+struct ScPair {
+  const float* src;
+  const float* tgt;
+  char* base;
+  float* conf;
+  int n, ns;
+};
+__device__ __forceinline__ ScPair sc_pair(const ScBatch& B) {
+  const int b = blockIdx.z;
+  return ScPair{B.src + (size_t)b * B.n_cap * 3, B.tgt + (size_t)b * B.n_cap * 3, B.scratch + (size_t)b * B.slot,
+                B.conf + (size_t)b * B.n_cap, B.n[b], B.ns[b]};
+}
+__global__ void k_scb_reg_init(const ScBatch B) {
+  const ScPair P = sc_pair(B);
+  if ((int)(blockIdx.x * blockDim.x) >= P.n) return;
+  sc_reg_init(P.conf, (int*)(P.base + B.o_is_max), (int*)(P.base + B.o_rank), (int*)(P.base + B.o_done), P.n);
+}
+__global__ void __launch_bounds__(256) k_scb_sparse_build(const ScBatch B, float d2_thre, float tight_thr) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x * SB_ROWS >= P.n) return;
+  sc_sparse_build(P.src, P.tgt, P.n, d2_thre, (int*)(P.base + B.o_count), (ScEntry*)(P.base + B.o_entries), tight_thr,
+                  (unsigned long long*)(P.base + B.o_bits));
+}
+// prev / out: the two partial buffers of a slot, by offset (they alternate from product to product)
+template <bool FIRST>
+__global__ void __launch_bounds__(SC_TILE) k_scb_matvec_folded(const ScBatch B, size_t o_prev, size_t o_out) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x * SC_TILE >= P.n) return;
+  sc_matvec_folded<FIRST>(P.n, P.conf, (int*)(P.base + B.o_done), (const float*)(P.base + o_prev), (float*)(P.base + o_out),
+                          (const int*)(P.base + B.o_count), (const ScEntry*)(P.base + B.o_entries));
+}
+__global__ void __launch_bounds__(1024) k_scb_normalize(const ScBatch B, size_t o_last) {
+  const ScPair P = sc_pair(B);
+  int* done = (int*)(P.base + B.o_done);
+  if (*done) return;
+  __shared__ float red[1024];
+  __shared__ int allc;
+  sc_normalize_by(threadIdx.x, 1024, (const float*)(P.base + o_last), P.n, P.conf, done, red, &allc);
+}
+__global__ void __launch_bounds__(SC_TILE) k_scb_local_max(const ScBatch B, float radius) {
+  const ScPair P = sc_pair(B);
+  const int n_tiles = (P.n + SC_TILE - 1) / SC_TILE;
+  if ((int)blockIdx.x >= n_tiles || (int)blockIdx.y > n_tiles / 2) return;      // a single call's grid: n_tiles x (n_tiles / 2 + 1)
+  sc_local_max(P.src, P.conf, P.n, radius, (int*)(P.base + B.o_is_max));
+}
+__global__ void __launch_bounds__(SC_TILE) k_scb_seed_rank(const ScBatch B) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x * SC_TILE >= P.n) return;
+  sc_seed_rank(P.conf, (const int*)(P.base + B.o_is_max), P.n, (int*)(P.base + B.o_rank));
+}
+__global__ void k_scb_seed_place(const ScBatch B) {
+  const ScPair P = sc_pair(B);
+  if ((int)(blockIdx.x * blockDim.x) >= P.n) return;
+  sc_seed_place((const int*)(P.base + B.o_rank), P.n, P.ns, B.seeds + (size_t)blockIdx.z * B.S);
+}
+// the uint16 second-order rows take the place of the entry slab, as in the single call
+__global__ void __launch_bounds__(256) k_scb_seed_sc2(const ScBatch B, float d_thre) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x * SK_TS >= P.ns) return;
+  sc_seed_sc2(P.src, P.tgt, (const unsigned long long*)(P.base + B.o_bits), P.n, (P.n + 63) / 64,
+              B.seeds + (size_t)blockIdx.z * B.S, P.ns, d_thre, (unsigned short*)(P.base + B.o_entries));
+}
+__global__ void __launch_bounds__(64) k_scb_seed_topk(const ScBatch B) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x >= P.ns) return;
+  sc_seed_topk((const unsigned short*)(P.base + B.o_entries), P.n, B.k1, B.knn + (size_t)blockIdx.z * B.S * B.k1);
+}
+__global__ void __launch_bounds__(64) k_scb_seed_trans(const ScBatch B, int k2, float d_thre, int num_iterations) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x >= P.ns) return;
+  sc_seed_trans(P.src, P.tgt, B.knn + (size_t)blockIdx.z * B.S * B.k1, B.k1, k2, d_thre, num_iterations,
+                B.seed_trans + (size_t)blockIdx.z * B.S * 12);
+}
+// the inlier count of k_sc_fitness, by sc_residual2: a thread's points t, t + 256, ... in pairs, an odd last one on its own
+__global__ void __launch_bounds__(256) k_scb_fitness(const ScBatch B, float thr) {
+  const ScPair P = sc_pair(B);
+  if ((int)blockIdx.x >= P.ns) return;
+  __shared__ int red[256];
+  __shared__ float Ts[12];
+  const int t = threadIdx.x;
+  if (t < 12) Ts[t] = B.seed_trans[((size_t)blockIdx.z * B.S + blockIdx.x) * 12 + t];
+  __syncthreads();
+  const int trips = t < P.n ? (P.n - 1 - t) / 256 + 1 : 0, packed = trips & ~1;
+  int cnt = 0;
+  for (int k = 0; k < trips; ++k) {
+    const int j = t + 256 * k;
+    cnt += sqrtf(sc_residual2(Ts, ld3(P.src, j), ld3(P.tgt, j), k < packed)) < thr;
+  }
+  red[t] = cnt;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (t == 0) B.fitness[(size_t)blockIdx.z * B.S + blockIdx.x] = (float)red[0];
+}
+__global__ void __launch_bounds__(256) k_scb_best(const ScBatch B) {
+  const ScPair P = sc_pair(B);
+  sc_best(B.fitness + (size_t)blockIdx.z * B.S, B.seed_trans + (size_t)blockIdx.z * B.S * 12, P.ns, B.best + blockIdx.z,
+          (float*)(P.base + B.o_T));
+}
+// one workgroup per pair, each with its own iteration count: a pair that has converged leaves, the others go on
+__global__ void __launch_bounds__(1024) k_scb_refine_all(const ScBatch B, float thr, int iterations) {
+  const ScPair P = sc_pair(B);
+  sc_refine_all(P.src, P.tgt, P.n, thr, iterations, (int*)(P.base + B.o_state), (float*)(P.base + B.o_T));
+}
+__global__ void k_scb_finish(const ScBatch B, float thr) {
+  const ScPair P = sc_pair(B);
+  float* labels = B.labels + (size_t)blockIdx.z * B.n_cap;
+  sc_finish(P.src, P.tgt, P.n, (const float*)(P.base + B.o_T), thr, B.trans16 + (size_t)blockIdx.z * 16, labels);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 16) out16[i] = i < 12 ? T[i] : (i == 15 ? 1.f : 0.f);
-  if (i >= n) return;
-  const P3 s = ld3(src, i), g = ld3(tgt, i);
-  const float wx = T[0] * s.x + T[1] * s.y + T[2] * s.z + T[3] - g.x;
-  const float wy = T[4] * s.x + T[5] * s.y + T[6] * s.z + T[7] - g.y;
-  const float wz = T[8] * s.x + T[9] * s.y + T[10] * s.z + T[11] - g.z;
-  labels[i] = sqrtf(wx * wx + wy * wy + wz * wz) < thr ? 1.f : 0.f;
+  if (i >= P.n && i < B.n_cap) labels[i] = 0.f;      // beyond the pair's count: no correspondence, no inlier
 }
 
 }  // namespace gcl
@@ -1032,12 +1383,16 @@ int gcl_sc2_seed_trans(const float* src, const float* tgt, int32_t n, const int3
   return GCL_OK;
 }
 
+static bool sc_refine_one_launch() {      // GCL_SC2_REFINE_ONE_LAUNCH=0: the two-kernel form, 2 x iterations launches
+  static const int on = [] { const char* e = getenv("GCL_SC2_REFINE_ONE_LAUNCH"); return e ? atoi(e) : 1; }();
+  return on != 0;
+}
+
 int gcl_sc2_refine(const float* src, const float* tgt, int32_t n, float thr, int32_t iterations, double* partial,
                    int32_t* state, float* T, void* stream) {
   GCL_CHECK_ARG(src && tgt && partial && state && T && n > 0 && iterations >= 0, "gcl_sc2_refine: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  static const int one_launch = [] { const char* e = getenv("GCL_SC2_REFINE_ONE_LAUNCH"); return e ? atoi(e) : 1; }();
-  if (one_launch) {
+  if (sc_refine_one_launch()) {
     hipLaunchKernelGGL(k_sc_refine_all, dim3(1), dim3(1024), 0, st, src, tgt, n, thr, iterations, state, T);
     GCL_CHECK_LAUNCH();
     return GCL_OK;
@@ -1117,6 +1472,122 @@ int gcl_sc2_register(const float* src, const float* tgt, int32_t n, float d_thre
   if (rc != GCL_OK) return rc;
   hipLaunchKernelGGL(k_sc_finish, dim3((unsigned)cdiv(std::max(n, 16), 256)), dim3(256), 0, st, src, tgt, n, (const float*)T,
                      inlier_thresh, trans16, labels);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+// ---- a batch of pairs in the launches of one registration ----------------------------------------------------------------------
+// A pair's slot is the single-pair layout at n_cap with every slab on a 256-byte boundary (the second partial buffer, which
+// the single layout places right behind the entries, gets a slab of its own); it is never smaller than
+// gcl_sc2_register_scratch_bytes(n_cap), so that the per-pair loop below can hand a slot to gcl_sc2_register.
+struct ScBatchLayout { size_t partial, partial2, done, count, entries, is_max, rank, bits, T, state, total; };
+static ScBatchLayout sc_batch_layout(int n_cap) {
+  ScBatchLayout L;
+  size_t o = 0;
+  L.partial = o;  o += sc_up256((size_t)SC_CHUNKS * n_cap * 4);
+  L.partial2 = o; o += sc_up256((size_t)SC_CHUNKS * n_cap * 4);
+  L.done = o;     o += 256;
+  L.count = o;    o += sc_up256((size_t)SC_CHUNKS * n_cap * 4);
+  L.entries = o;  o += sc_up256((size_t)SC_CHUNKS * n_cap * cdiv(n_cap, SC_CHUNKS) * sizeof(ScEntry));
+  L.is_max = o;   o += sc_up256((size_t)n_cap * 4);
+  L.rank = o;     o += sc_up256((size_t)n_cap * 4);
+  L.bits = o;     o += sc_up256((size_t)n_cap * ((n_cap + 63) / 64) * 8);
+  L.T = o;        o += 256;
+  L.state = o;    o += 256;
+  L.total = std::max(o, sc_up256(sc_reg_layout(n_cap).total));
+  return L;
+}
+
+int64_t gcl_sc2_register_batch_scratch_bytes(int32_t batch, int32_t n_cap) {
+  if (batch <= 0 || n_cap <= 0 || n_cap > SC_MAXN) return 0;
+  return (int64_t)batch * (int64_t)sc_batch_layout(n_cap).total;
+}
+
+int gcl_sc2_register_batch(const float* src, const float* tgt, int32_t batch, int32_t n_cap, const int32_t* counts,
+                           const int32_t* n_seeds, float d_thre, int32_t num_iterations, float nms_radius, int32_t k1,
+                           int32_t k2, float inlier_thresh, float refine_thr, int32_t refine_iters, void* scratch, float* conf,
+                           int64_t* seeds, int32_t* knn, float* seed_trans, float* fitness, int32_t* best, float* trans16,
+                           float* labels, void* stream) {
+  GCL_CHECK_ARG(src && tgt && counts && n_seeds && scratch && conf && seeds && knn && seed_trans && fitness && best && trans16 &&
+                    labels,
+                "gcl_sc2_register_batch: null pointer");
+  GCL_CHECK_ARG(batch >= 1, "gcl_sc2_register_batch: batch must be >= 1, got %d", batch);
+  GCL_CHECK_ARG(n_cap >= 1 && n_cap <= SC_MAXN, "gcl_sc2_register_batch: need 1 <= n_cap <= %d, got %d", SC_MAXN, n_cap);
+  GCL_CHECK_ARG(d_thre > 0 && num_iterations >= 0 && refine_iters >= 0,
+                "gcl_sc2_register_batch: need d_thre > 0, num_iterations >= 0, refine_iters >= 0");
+  GCL_CHECK_ARG(k1 >= 1 && k1 <= 32 && k2 >= 1 && k2 <= k1, "gcl_sc2_register_batch: need 1 <= k2 <= k1 <= 32, got k1 = %d, k2 = %d",
+                k1, k2);
+  int S = 0;
+  for (int b = 0; b < batch; ++b) {
+    GCL_CHECK_ARG(n_seeds[b] >= 1 && n_seeds[b] <= counts[b] && counts[b] <= n_cap,
+                  "gcl_sc2_register_batch: pair %d needs 1 <= n_seeds (%d) <= counts (%d) <= n_cap (%d)", b, n_seeds[b], counts[b],
+                  n_cap);
+    GCL_CHECK_ARG(k1 <= counts[b], "gcl_sc2_register_batch: k1 = %d, but pair %d has counts = %d correspondences", k1, b,
+                  counts[b]);
+    S = std::max(S, n_seeds[b]);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const ScBatchLayout L = sc_batch_layout(n_cap);
+  if (!sc_folded_normalize() || !sc_seed_blocked() || !sc_refine_one_launch() || num_iterations == 0) {
+    // not the default forms: the single call per pair, on the pair's slot and output rows
+    for (int b = 0; b < batch; ++b) {
+      float* lab = labels + (size_t)b * n_cap;
+      const int rc = gcl_sc2_register(src + (size_t)b * n_cap * 3, tgt + (size_t)b * n_cap * 3, counts[b], d_thre, num_iterations,
+                                      nms_radius, n_seeds[b], k1, k2, inlier_thresh, refine_thr, refine_iters,
+                                      (char*)scratch + (size_t)b * L.total, conf + (size_t)b * n_cap, seeds + (size_t)b * S,
+                                      knn + (size_t)b * S * k1, seed_trans + (size_t)b * S * 12, fitness + (size_t)b * S, best + b,
+                                      trans16 + (size_t)b * 16, lab, stream);
+      if (rc != GCL_OK) return rc;
+      if (counts[b] < n_cap) GCL_CHECK_HIP(hipMemsetAsync(lab + counts[b], 0, (size_t)(n_cap - counts[b]) * sizeof(float), st));
+    }
+    return GCL_OK;
+  }
+  const float d2 = d_thre * d_thre;
+  for (int g0 = 0; g0 < batch; g0 += SC_GROUP) {
+    const int G = std::min(SC_GROUP, batch - g0);
+    ScBatch B;
+    B.src = src + (size_t)g0 * n_cap * 3;
+    B.tgt = tgt + (size_t)g0 * n_cap * 3;
+    B.scratch = (char*)scratch + (size_t)g0 * L.total;
+    B.slot = L.total;
+    B.o_partial = L.partial; B.o_partial2 = L.partial2; B.o_done = L.done; B.o_count = L.count; B.o_entries = L.entries;
+    B.o_is_max = L.is_max; B.o_rank = L.rank; B.o_bits = L.bits; B.o_T = L.T; B.o_state = L.state;
+    B.conf = conf + (size_t)g0 * n_cap;
+    B.seeds = (long long*)seeds + (size_t)g0 * S;
+    B.knn = knn + (size_t)g0 * S * k1;
+    B.seed_trans = seed_trans + (size_t)g0 * S * 12;
+    B.fitness = fitness + (size_t)g0 * S;
+    B.best = best + g0;
+    B.trans16 = trans16 + (size_t)g0 * 16;
+    B.labels = labels + (size_t)g0 * n_cap;
+    B.n_cap = n_cap; B.S = S; B.k1 = k1;
+    int Sg = 0;
+    for (int b = 0; b < SC_GROUP; ++b) {
+      B.n[b] = b < G ? counts[g0 + b] : 0;
+      B.ns[b] = b < G ? n_seeds[g0 + b] : 0;
+      Sg = std::max(Sg, B.ns[b]);
+    }
+    const unsigned z = (unsigned)G, tiles = (unsigned)cdiv(n_cap, SC_TILE);
+    const dim3 rows(tiles, SC_CHUNKS, z);
+    hipLaunchKernelGGL(k_scb_reg_init, dim3((unsigned)cdiv(n_cap, 256), 1, z), dim3(256), 0, st, B);
+    hipLaunchKernelGGL(k_scb_sparse_build, dim3((unsigned)cdiv(n_cap, SB_ROWS), SC_CHUNKS, z), dim3(256), 0, st, B, d2,
+                       d_thre * 0.5f);
+    const size_t buf[2] = {L.partial, L.partial2};
+    hipLaunchKernelGGL(k_scb_matvec_folded<true>, rows, dim3(SC_TILE), 0, st, B, buf[1], buf[0]);
+    for (int it = 1; it < num_iterations; ++it)
+      hipLaunchKernelGGL(k_scb_matvec_folded<false>, rows, dim3(SC_TILE), 0, st, B, buf[(it - 1) & 1], buf[it & 1]);
+    hipLaunchKernelGGL(k_scb_normalize, dim3(1, 1, z), dim3(1024), 0, st, B, buf[(num_iterations - 1) & 1]);
+    hipLaunchKernelGGL(k_scb_local_max, dim3(tiles, tiles / 2 + 1, z), dim3(SC_TILE), 0, st, B, nms_radius);
+    hipLaunchKernelGGL(k_scb_seed_rank, rows, dim3(SC_TILE), 0, st, B);
+    hipLaunchKernelGGL(k_scb_seed_place, dim3((unsigned)cdiv(n_cap, 256), 1, z), dim3(256), 0, st, B);
+    hipLaunchKernelGGL(k_scb_seed_sc2, dim3((unsigned)cdiv(Sg, SK_TS), SC_CHUNKS, z), dim3(256), 0, st, B, d_thre);
+    hipLaunchKernelGGL(k_scb_seed_topk, dim3((unsigned)Sg, 1, z), dim3(64), 0, st, B);
+    hipLaunchKernelGGL(k_scb_seed_trans, dim3((unsigned)Sg, 1, z), dim3(64), 0, st, B, k2, d_thre, num_iterations);
+    hipLaunchKernelGGL(k_scb_fitness, dim3((unsigned)Sg, 1, z), dim3(256), 0, st, B, inlier_thresh);
+    hipLaunchKernelGGL(k_scb_best, dim3(1, 1, z), dim3(256), 0, st, B);
+    hipLaunchKernelGGL(k_scb_refine_all, dim3(1, 1, z), dim3(1024), 0, st, B, refine_thr, refine_iters);
+    hipLaunchKernelGGL(k_scb_finish, dim3((unsigned)cdiv(std::max(n_cap, 16), 256), 1, z), dim3(256), 0, st, B, inlier_thresh);
+  }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

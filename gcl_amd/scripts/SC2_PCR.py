@@ -1,13 +1,16 @@
 """SC2-PCR registration back-end on the MI355X kernels (interface of scripts/SC2_PCR/SC2_PCR.py: class ``Matcher``).
 
 ``Matcher(**config_KITTI.json).estimator(src_keypts, tgt_keypts, src_features, tgt_features)`` as called by the eval
-loop (scripts/test_kitti.py:172-180), batch size 1 (the reference asserts it too, :42, :249).  Putative
+loop (scripts/test_kitti.py:172-180); ``Matcher`` registers one pair per call (the reference asserts it too, :42, :249),
+``BatchMatcher`` below takes [B, n, 3] and registers the B pairs in the launches of one (gcl_sc2_register_batch).  Putative
 correspondences come from ``gcl_nn_rowmin`` (the reference's argmin of sqrt(2 - 2 f.g) over L2-normalised features
 is the argmin of |f - g|^2); the registration itself is ONE C-ABI call (include/gcl_amd.h, gcl_sc2_register; with
 ``GCL_SC2_ONE_CALL=0`` the five staged calls with three small torch steps in between -- a stable sort for the seeds, an
 argmax, the inlier labels -- that it replaced: same kernels, same results).  Nothing leaves the device until the caller
 reads the result.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -149,3 +152,174 @@ class Matcher:
         distance = torch.sum((warped - tgt_corr) ** 2, dim=-1) ** 0.5
         pred_labels = (distance < self.inlier_threshold).float()
         return pred_trans, pred_labels, src_corr, tgt_corr
+
+
+MAX_CORRESPONDENCES = 8192      # SC_MAXN of csrc/sc2pcr.hip: the scratch size functions answer 0 beyond it
+
+
+def split_batch(n_pairs, pair_bytes, max_batch_bytes):
+    """Consecutive sub-batches [(b0, b1), ...] of ``n_pairs`` pairs whose scratch (``pair_bytes`` each) stays within
+    ``max_batch_bytes``; a sub-batch has at least one pair, whatever the limit.  Pure host arithmetic."""
+    per = max(1, int(max_batch_bytes) // max(1, int(pair_bytes)))
+    return [(b0, min(n_pairs, b0 + per)) for b0 in range(0, n_pairs, per)]
+
+
+class _BatchStages:
+    """``BatchMatcher.last``: ``last[b][name]`` is pair b's view of stage ``name`` (the names of ``Matcher.last``), cut to the
+    pair's own extent; the views are made when asked for."""
+
+    def __init__(self, pairs):
+        self._pairs = pairs          # per pair: (dict name -> [pairs of its sub-batch, ...] tensor, row, n, n_seeds)
+
+    def __len__(self):
+        return len(self._pairs)
+
+    def __getitem__(self, b):
+        views, row, n, n_seeds = self._pairs[b]
+
+        class _One:
+            def __getitem__(_, name):
+                v = views[name][row]
+                if name == "out":
+                    return v.view(1, 4, 4)
+                if name == "labels":
+                    return v[:n].view(1, n)
+                if name == "conf":
+                    return v[:n]
+                return v if name == "best" else v[:n_seeds]
+
+            def keys(_):
+                return views.keys()
+
+        return _One()
+
+
+class BatchMatcher(Matcher):
+    """``Matcher`` for a batch of pairs: ``SC2_PCR`` / ``estimator`` take [B, n, ...] tensors and make ONE
+    ``gcl_sc2_register_batch`` call -- the launches of one registration with the pair as the grids' z dimension -- whose
+    results equal ``Matcher``'s on every pair alone bit for bit.  SCRATCH: ~ 8 n^2 bytes per pair (528 MB at n = 8000); a batch
+    that would need more than ``max_batch_bytes`` runs as consecutive sub-batches on one scratch block."""
+
+    accepts_batch = True             # scripts/eval_batch.eval_pairs(..., batch_registration=True) asks for these two
+    draw_takes_sizes = True
+
+    def __init__(self, *args, max_batch_bytes=8 << 30, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.max_batch_bytes = int(max_batch_bytes)
+        self.last = None
+
+    def draw_seed(self, n_src, n_tgt):
+        """The host draws ``Matcher.match_pair`` makes for one pair with ``n_src`` / ``n_tgt`` feature rows, in its order:
+        None for ``num_node == 'all'``, else the (source rows, target rows) for ``estimator(seeds=...)``."""
+        if self.num_node == "all":
+            return None
+        return np.random.choice(n_src, self.num_node), np.random.choice(n_tgt, self.num_node)
+
+    def plan(self, n_cap, counts=None, n_pairs=None):
+        """Host half of ``SC2_PCR``: per pair the count after the ``max_points`` cut and ``int(n * ratio)`` seeds, and the
+        batch's (k1, k2).  Raises ``ValueError`` for a pair without a seed and for a batch whose pairs disagree on the
+        reference's ``k1 > n -> (4, 4)`` rule (:75-77): one call has one k1."""
+        if counts is None:
+            counts = [n_cap] * n_pairs
+        counts = [int(c) for c in counts]
+        if n_pairs is not None and len(counts) != n_pairs:
+            raise ValueError(f"{n_pairs} pairs but {len(counts)} counts")
+        if any(c < 0 or c > n_cap for c in counts):
+            raise ValueError(f"counts must lie in [0, {n_cap}], got {counts}")
+        if min(n_cap, self.max_points) > MAX_CORRESPONDENCES:
+            raise ValueError(f"a registration takes at most {MAX_CORRESPONDENCES} correspondences per pair; got {n_cap} with "
+                             f"max_points = {self.max_points}: lower max_points")
+        counts = [min(c, self.max_points) for c in counts]
+        n_seeds = [int(c * self.ratio) for c in counts]
+        if min(n_seeds) < 1:
+            raise ValueError(f"too few correspondences for SC2-PCR: counts {counts} give {n_seeds} seeds")
+        small = [self.k1 > c for c in counts]
+        if any(small) and not all(small):
+            raise ValueError(f"pairs with fewer than k1 = {self.k1} correspondences use (k1, k2) = (4, 4) and cannot share a "
+                             f"call with pairs that do not: counts {counts}; register the two groups separately")
+        k1, k2 = (4, 4) if small[0] else (self.k1, self.k2)
+        return counts, n_seeds, k1, k2
+
+    def SC2_PCR(self, src_keypts, tgt_keypts, counts=None):
+        B = src_keypts.shape[0]
+        if B < 1:
+            raise ValueError("SC2_PCR needs at least one pair")
+        counts, n_seeds, k1, k2 = self.plan(src_keypts.shape[1], counts, B)      # refusals before any GPU work
+        lib = _lib.require_gpu()
+        src = src_keypts[:, :self.max_points].to(torch.float32).contiguous()
+        tgt = tgt_keypts[:, :self.max_points].to(torch.float32).contiguous()
+        n_cap, dev, st = src.shape[1], src.device, _lib.stream()
+        thr = 0.10 if self.inlier_threshold == 0.10 else 1.2
+        subs = split_batch(B, lib.gcl_sc2_register_batch_scratch_bytes(1, n_cap), self.max_batch_bytes)
+        # ONE output block: out and labels for the whole batch, then every sub-batch's stages at its own S = max(n_seeds)
+        fields, off = [], 0
+
+        def place(count, dtype):
+            nonlocal off
+            at = off
+            off += (count * dtype.itemsize + 255) // 256 * 256
+            return at, count, dtype
+
+        head = dict(out=place(B * 16, torch.float32), labels=place(B * n_cap, torch.float32),
+                    conf=place(B * n_cap, torch.float32), best=place(B, torch.int32))
+        for b0, b1 in subs:
+            S, nb = max(n_seeds[b0:b1]), b1 - b0
+            fields.append((S, dict(seeds=place(nb * S, torch.int64), knn=place(nb * S * k1, torch.int32),
+                                   seed_trans=place(nb * S * 12, torch.float32), fitness=place(nb * S, torch.float32))))
+        buf = torch.empty(off, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(lib.gcl_sc2_register_batch_scratch_bytes(max(b1 - b0 for b0, b1 in subs), n_cap),
+                              dtype=torch.uint8, device=dev)
+        view = lambda f, *shape: buf[f[0]:f[0] + f[1] * f[2].itemsize].view(f[2]).view(*shape)
+        out, labels = view(head["out"], B, 16), view(head["labels"], B, n_cap)
+        conf, best = view(head["conf"], B, n_cap), view(head["best"], B)
+        c_counts, c_seeds = (ctypes.c_int32 * B)(*counts), (ctypes.c_int32 * B)(*n_seeds)
+        i32 = ctypes.sizeof(ctypes.c_int32)
+        pairs = []
+        for (b0, b1), (S, f) in zip(subs, fields):
+            nb = b1 - b0
+            v = dict(out=out[b0:b1], labels=labels[b0:b1], conf=conf[b0:b1], best=best[b0:b1],
+                     seeds=view(f["seeds"], nb, S), knn=view(f["knn"], nb, S, k1),
+                     seed_trans=view(f["seed_trans"], nb, S, 12), fitness=view(f["fitness"], nb, S))
+            _lib.check(lib.gcl_sc2_register_batch(
+                _lib.ptr(src[b0:b1]), _lib.ptr(tgt[b0:b1]), nb, n_cap, ctypes.byref(c_counts, b0 * i32),
+                ctypes.byref(c_seeds, b0 * i32), float(self.d_thre), int(self.num_iterations), float(self.nms_radius),
+                k1, k2, float(self.inlier_threshold), thr, 20, _lib.ptr(scratch), _lib.ptr(v["conf"]), _lib.ptr(v["seeds"]),
+                _lib.ptr(v["knn"]), _lib.ptr(v["seed_trans"]), _lib.ptr(v["fitness"]), _lib.ptr(v["best"]),
+                _lib.ptr(v["out"]), _lib.ptr(v["labels"]), st), "gcl_sc2_register_batch")
+            pairs += [(v, b - b0, counts[b], n_seeds[b]) for b in range(b0, b1)]
+        self.last = _BatchStages(pairs)
+        self.counts = counts
+        self._labels = labels
+        return out.view(B, 4, 4)
+
+    def estimator(self, src_keypts, tgt_keypts, src_features, tgt_features, seeds=None):
+        """``Matcher.estimator`` on [B, N, ...] tensors: one feature 1-NN per pair, ONE registration call.  ``seeds``: per
+        pair what ``draw_seed`` returned, for a caller that made the draws already (in its own order of host draws); None:
+        drawn here, in pair order -- the draws of B ``Matcher.estimator`` calls in a row."""
+        B = src_keypts.shape[0]
+        N_src, N_tgt = src_features.shape[1], tgt_features.shape[1]
+        if seeds is None:
+            seeds = [self.draw_seed(N_src, N_tgt) for _ in range(B)]
+        if len(seeds) != B:
+            raise ValueError(f"{B} pairs but {len(seeds)} seeds")
+        n = N_src if self.num_node == "all" else int(self.num_node)
+        self.plan(n, None, B)                                                    # refusals before any GPU work
+        dev = src_features.device
+        src_corr = torch.empty((B, n, 3), dtype=src_keypts.dtype, device=dev)
+        tgt_corr = torch.empty((B, n, 3), dtype=tgt_keypts.dtype, device=dev)
+        for b in range(B):                                                       # Matcher.match_pair with the given draws
+            sel = seeds[b]
+            src_sel, tgt_sel = (None, None) if sel is None else (host_to_device(sel[0], dev), host_to_device(sel[1], dev))
+            _, arg = pdist_min(src_features[b], tgt_features[b], "SquareL2", rows_a=src_sel, rows_b=tgt_sel)
+            arg = arg.long()
+            src_corr[b] = src_keypts[b] if src_sel is None else src_keypts[b, src_sel]
+            tgt_corr[b] = tgt_keypts[b, tgt_sel[arg] if tgt_sel is not None else arg]
+        pred_trans = self.SC2_PCR(src_corr, tgt_corr)
+        if n <= self.max_points:                                                 # made by the registration call itself
+            return pred_trans, self._labels, src_corr, tgt_corr
+        labels = torch.empty((B, n), dtype=torch.float32, device=dev)
+        for b in range(B):                                                       # Matcher.estimator's own expression, per pair
+            T, sc, tc = pred_trans[b:b + 1], src_corr[b:b + 1], tgt_corr[b:b + 1]
+            warped = sc @ T[:, :3, :3].transpose(1, 2) + T[:, None, :3, 3]
+            labels[b] = (torch.sum((warped - tc) ** 2, dim=-1) ** 0.5 < self.inlier_threshold).float()[0]
+        return pred_trans, labels, src_corr, tgt_corr

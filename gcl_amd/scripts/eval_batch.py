@@ -4,8 +4,9 @@
 ``batch_registration`` is true: then the ``batch_pairs`` pairs of a chunk, which already share one forward pass, are also
 registered by one ``matcher.estimator`` call on [B, n_points, ...] tensors instead of one call per pair.  The per-pair loop
 is bound by the enqueuing thread (a registration is ~100 dependent launches of a few microseconds); a matcher
-that takes a batch (``gcl_amd.lib.ransac.FeatureRansac``: ``gcl_ransac_register_batch``) makes the launches of one
-registration for the whole chunk and returns the same transformations bit for bit.
+that takes a batch (``gcl_amd.lib.ransac.FeatureRansac``: ``gcl_ransac_register_batch``; ``gcl_amd.scripts.SC2_PCR.BatchMatcher``:
+``gcl_sc2_register_batch``) makes the launches of one registration for the whole chunk and returns the same transformations
+bit for bit.
 
 Everything else is the loop of ``test_kitti.eval_pairs`` and uses its pieces: the same forward passes
 (``forward_clouds_stream``), the same host draws in the same per-pair order (``DeferredCorr``, ``random_sample`` twice, then
@@ -31,8 +32,8 @@ def eval_pairs(model, pairs, matcher, device=None, batch_pairs=1, subsample_size
         return TK.eval_pairs(model, pairs, matcher, device=device, batch_pairs=batch_pairs, subsample_size=subsample_size,
                              n_points=n_points, rte_thresh=rte_thresh, rre_thresh=rre_thresh, collect=collect)
     if not (getattr(matcher, "accepts_batch", False) and hasattr(matcher, "draw_seed")):
-        raise ValueError("batch_registration needs a matcher whose estimator takes a batch of pairs (FeatureRansac); "
-                         f"{type(matcher).__name__} registers one pair per call")
+        raise ValueError("batch_registration needs a matcher whose estimator takes a batch of pairs (FeatureRansac, "
+                         f"BatchMatcher); {type(matcher).__name__} registers one pair per call")
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     model.eval()
     success_meter, rte_meter, rre_meter = TK.AverageMeter(), TK.AverageMeter(), TK.AverageMeter()
@@ -82,7 +83,9 @@ def eval_pairs(model, pairs, matcher, device=None, batch_pairs=1, subsample_size
                 xyz1s, F1s = TK.random_sample(xyz1.numpy(), F1, n_points)
                 t0 = time.perf_counter()
                 held.append((host_to_device(xyz0s, dev), host_to_device(xyz1s, dev), F0s, F1s))
-                seeds.append(matcher.draw_seed())
+                # a matcher whose draws depend on the two sizes (BatchMatcher: num_node rows of each) is handed them
+                seeds.append(matcher.draw_seed(len(F0s), len(F1s)) if getattr(matcher, "draw_takes_sizes", False)
+                             else matcher.draw_seed())
                 t_reg += time.perf_counter() - t0
             t0 = time.perf_counter()
             T_est, _, _, _ = matcher.estimator(*(torch.stack([h[k] for h in held]) for k in range(4)), seeds=seeds)

@@ -623,6 +623,32 @@ int gcl_sc2_register(const float* src, const float* tgt, int32_t n, float d_thre
                      int32_t n_seeds, int32_t k1, int32_t k2, float inlier_thresh, float refine_thr, int32_t refine_iters,
                      void* scratch, float* conf, int64_t* seeds, int32_t* knn, float* seed_trans, float* fitness,
                      int32_t* best, float* trans16, float* labels, void* stream);
+/* A BATCH of pairs in the launches of ONE registration (the reference asserts bs == 1; its Matcher is written for
+ * [bs, num_corr, 3]).  src / tgt: [batch, n_cap, 3] on the device; pair b uses rows 0 .. counts[b] - 1 of its block and
+ * wants n_seeds[b] seeds.  counts / n_seeds are HOST arrays [batch]: they travel to the kernels as a by-value argument (no
+ * copy on the stream, no read-back, no synchronisation).  Every launch of gcl_sc2_register's default forms is made once, with
+ * the pair as the grid's z dimension and grids sized for n_cap and S = max(n_seeds); a workgroup reads its own pair's n,
+ * derives that pair's chunk length, word count and tile counts, and returns at once when it lies beyond them.  The early
+ * exits (the power iteration's `done`, the refinement's convergence) are per pair.  More than 32 pairs: one such launch
+ * sequence per 32.
+ * CONTRACT: for every pair, every output is bit for bit what gcl_sc2_register writes for that pair alone, whatever the
+ * other pairs of the batch are and in whatever order.  With GCL_SC2_FOLDED_NORMALIZE=0, GCL_SC2_SEED_BLOCKED=0,
+ * GCL_SC2_REFINE_ONE_LAUNCH=0 or num_iterations = 0 the call IS a loop of gcl_sc2_register over the pairs.
+ * Outputs: trans16 float[batch, 16], labels float[batch, n_cap] (0 from a pair's count on), conf float[batch, n_cap],
+ * seeds int64[batch, S], knn int32[batch, S, k1], seed_trans float[batch, S, 12], fitness float[batch, S], best int32[batch];
+ * entries beyond a pair's own extent are unspecified, except labels.
+ * Needs 1 <= n_seeds[b] <= counts[b] <= n_cap <= 8192, batch >= 1, k1 <= min(counts), no null pointer: checked before any
+ * GPU call (GCL_ERR_ARG, gcl_last_error).
+ * scratch: gcl_sc2_register_batch_scratch_bytes(batch, n_cap) bytes = batch slots of the single-pair layout at n_cap, every
+ * slot and every slab in it on a 256-byte boundary (0 for batch <= 0, n_cap <= 0 or n_cap > 8192); may hold anything, the call
+ * initialises what it reads.  SCRATCH FOOTPRINT: ~ 8 n_cap^2 bytes of address space PER PAIR -- 528 MB at n = 8000, 4.2 GB for
+ * 8 such pairs -- of which, as in the single call, only the non-zero entries are ever touched. */
+int64_t gcl_sc2_register_batch_scratch_bytes(int32_t batch, int32_t n_cap);
+int gcl_sc2_register_batch(const float* src, const float* tgt, int32_t batch, int32_t n_cap, const int32_t* counts,
+                           const int32_t* n_seeds, float d_thre, int32_t num_iterations, float nms_radius, int32_t k1,
+                           int32_t k2, float inlier_thresh, float refine_thr, int32_t refine_iters, void* scratch, float* conf,
+                           int64_t* seeds, int32_t* knn, float* seed_trans, float* fitness, int32_t* best, float* trans16,
+                           float* labels, void* stream);
 int gcl_sc2_local_max(const float* src, const float* conf, int32_t n, float radius, int32_t* is_max, void* stream);
 int gcl_sc2_seed_knn(const float* src, const float* tgt, int32_t n, const int64_t* seeds, int32_t n_seeds,
                      float d_thre, int32_t k1, uint64_t* bits, int32_t* knn, void* stream);
