@@ -463,6 +463,153 @@ static int nn_chunk_rows(int ma, int mb) {
 // scratch (32-bit words): the interleaved copy of B, then the chunks' partial (minimum, index) pairs
 static long long nn_interleaved_words(int mb, int c) { return (long long)cdiv(mb, 2) * 2 * c; }
 
+// ---- the same search at ANY width 1 <= c <= 128 (gcl_nn_rowmin_any) -----------------------------------------------------
+// The channels are zero-padded up to CP = the next multiple of 8, in the interleaved copy of B and in the A registers: a
+// padded channel adds fma(0, 0, acc), which is exact, so the result is that of the c real channels.  SUMMATION ORDER, for
+// every width: ONE chain per (A row, B row) over ascending channels, d2 = (a_0 - b_0)^2 rounded, then
+// d2 = fma(a_k - b_k, a_k - b_k, d2) for k = 1 .. c - 1 -- at c = 16 / 32 / 64 bitwise what k_nn_rowmin gives.
+// k_nn_rowmin's (a, a) register pairs would take 256 VGPRs at 128 channels, so here a thread holds its A row as SINGLE floats
+// (CP VGPRs, register pair k = channels 2k and 2k + 1) and the packed subtraction broadcasts one half of the pair into both
+// of its halves through op_sel (nn_chain8w): the same two packed instructions per channel, in nn_chain8's order, so the same
+// wait states hold.  B still arrives two rows at a time through scalar loads and the loop touches no LDS.  Grid, chunks,
+// partial results and the merge are k_nn_rowmin's (k_nn_merge is shared).
+// Measured on an MI355X, 5000 x 5000 (profiles/sc2_bench_probe.txt): 51 us at 32 channels (k_nn_rowmin: 44), 51 at 33, 58 at
+// 40, 92 at 64, 145 at 96, 201 at 128.
+__global__ void __launch_bounds__(256) k_nn_interleave_pad(const float* __restrict__ b, const long long* __restrict__ rows_b,
+                                                           int mb, int c, int cp, float* __restrict__ bi) {
+  const int per = 256 / cp;                                              // row pairs per workgroup (cp <= 128: at least 2)
+  const int lp = (int)threadIdx.x / cp, ch = (int)threadIdx.x % cp;      // one (row pair, padded channel) per thread
+  const long long p = (long long)blockIdx.x * per + lp;
+  if (lp >= per || 2 * p >= mb) return;
+  float v0 = 0.f, v1 = 0.f;                                              // padding, and an odd count's last partner
+  if (ch < c) {
+    v0 = b[(rows_b ? rows_b[2 * p] : 2 * p) * c + ch];
+    if (2 * p + 1 < mb) v1 = b[(rows_b ? rows_b[2 * p + 1] : 2 * p + 1) * c + ch];
+  }
+  *reinterpret_cast<nn_f2*>(bi + 2 * (p * cp + ch)) = nn_f2{v0, v1};
+}
+
+// nn_chain8 with a[k] = the channels (2k, 2k + 1) of the A row: low half broadcast by op_sel:[0,0] op_sel_hi:[0,1], high half
+// by op_sel:[1,0] op_sel_hi:[1,1]
+#define NN_SUBL(D, A, B) "v_pk_add_f32 " D ", " A ", " B " op_sel:[0,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]\n"
+#define NN_SUBH(D, A, B) "v_pk_add_f32 " D ", " A ", " B " op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n"
+template <bool FIRST>
+__device__ __forceinline__ void nn_chain8w(nn_f2& acc, const nn_f2* a, const nn_f2* b) {
+  nn_f2 d0, d1;
+  if (FIRST)
+    asm volatile(NN_SUBL("%[d0]", "%[a0]", "%[b0]") NN_SUBH("%[d1]", "%[a0]", "%[b1]")
+                 "v_pk_mul_f32 %[acc], %[d0], %[d0]\n"
+                 NN_SUBL("%[d0]", "%[a1]", "%[b2]") NN_FMA("%[d1]") NN_SUBH("%[d1]", "%[a1]", "%[b3]") NN_FMA("%[d0]")
+                 NN_SUBL("%[d0]", "%[a2]", "%[b4]") NN_FMA("%[d1]") NN_SUBH("%[d1]", "%[a2]", "%[b5]") NN_FMA("%[d0]")
+                 NN_SUBL("%[d0]", "%[a3]", "%[b6]") NN_FMA("%[d1]") NN_SUBH("%[d1]", "%[a3]", "%[b7]") NN_FMA("%[d0]")
+                 "s_nop 0\n" NN_FMA("%[d1]")
+                 : [acc] "=&v"(acc), [d0] "=&v"(d0), [d1] "=&v"(d1)
+                 : [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [b0] "s"(b[0]), [b1] "s"(b[1]),
+                   [b2] "s"(b[2]), [b3] "s"(b[3]), [b4] "s"(b[4]), [b5] "s"(b[5]), [b6] "s"(b[6]), [b7] "s"(b[7]));
+  else
+    asm volatile(NN_SUBL("%[d0]", "%[a0]", "%[b0]") NN_SUBH("%[d1]", "%[a0]", "%[b1]") NN_FMA("%[d0]")
+                 NN_SUBL("%[d0]", "%[a1]", "%[b2]") NN_FMA("%[d1]") NN_SUBH("%[d1]", "%[a1]", "%[b3]") NN_FMA("%[d0]")
+                 NN_SUBL("%[d0]", "%[a2]", "%[b4]") NN_FMA("%[d1]") NN_SUBH("%[d1]", "%[a2]", "%[b5]") NN_FMA("%[d0]")
+                 NN_SUBL("%[d0]", "%[a3]", "%[b6]") NN_FMA("%[d1]") NN_SUBH("%[d1]", "%[a3]", "%[b7]") NN_FMA("%[d0]")
+                 "s_nop 0\n" NN_FMA("%[d1]")
+                 : [acc] "+v"(acc), [d0] "=&v"(d0), [d1] "=&v"(d1)
+                 : [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2]), [a3] "v"(a[3]), [b0] "s"(b[0]), [b1] "s"(b[1]),
+                   [b2] "s"(b[2]), [b3] "s"(b[3]), [b4] "s"(b[4]), [b5] "s"(b[5]), [b6] "s"(b[6]), [b7] "s"(b[7]));
+}
+
+// One row pair's two distances.  The interleaved row (2 CP dwords through scalar loads) does not fit the 102 SGPRs of a wave
+// beyond 40 channels -- left to itself the compiler fetches the whole row first and parks the overflow in VGPR lanes (as
+// k_nn_rowmin<64> does, 63 spilled SGPRs; that form measured 137 us at 64 channels against 92 here) -- so from 48 channels
+// on the row is taken in groups of 16 channels (32 SGPRs), one group in flight while the previous one runs its chain: the
+// empty asm statements pin the order (wait for group g - 1, issue the loads of group g, chain of group g - 1) and add no
+// instruction.  Up to 40 channels the whole row is one group (grouping there cost 4 - 12 us when tried: the wait before
+// every group is exposed).
+template <int CP>
+__device__ __forceinline__ nn_f2 nn_row_dist(const nn_f2* __restrict__ row, const nn_f2* av) {
+  constexpr int GS = CP > 40 ? 16 : CP;
+  constexpr int G = (CP + GS - 1) / GS;
+  nn_f2 bv[G][GS], acc;
+#pragma unroll
+  for (int g = 0; g <= G; ++g) {
+    if (g > 0) asm volatile("" ::"s"(bv[g - 1][0]));                 // group g - 1 has arrived before group g is asked for
+    if (g < G) {
+      int off = GS * g;
+      asm volatile("" : "+s"(off));
+      const nn_f2* __restrict__ r = row + off;
+#pragma unroll
+      for (int k = 0; k < GS; ++k)
+        if (GS * g + k < CP) bv[g][k] = r[k];
+    }
+    if (g > 0) {
+#pragma unroll
+      for (int k = 0; k < GS; k += 8) {
+        const int ch = GS * (g - 1) + k;                               // first channel of this chain step
+        if (ch >= CP) continue;
+        if (ch == 0) nn_chain8w<true>(acc, av, bv[0]);
+        else nn_chain8w<false>(acc, av + ch / 2, bv[g - 1] + k);
+      }
+    }
+  }
+  asm volatile("s_nop 0" : "+v"(acc));      // the last packed write before the compiler's own reads of acc
+  return acc;
+}
+
+template <int CP>
+__global__ void __launch_bounds__(256) k_nn_rowmin_any(const float* __restrict__ a, const long long* __restrict__ rows_a,
+                                                       int ma, int c, const float* __restrict__ bi_, int mb, int chunk,
+                                                       int l2, float* __restrict__ out_v, int* __restrict__ out_i) {
+  __shared__ float rv[4][NN_TA];
+  __shared__ int ri[4][NN_TA];
+  const nn_f2* __restrict__ bi = reinterpret_cast<const nn_f2*>(bi_);
+  const int t = threadIdx.x, ar = t & 63, cg = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int arow = blockIdx.x * NN_TA + ar;
+  nn_f2 av[CP / 2];                                                    // (a_2k, a_2k+1): CP VGPRs
+  {
+    const long long src = (arow < ma) ? (rows_a ? rows_a[arow] : (long long)arow) : -1;
+#pragma unroll
+    for (int k = 0; k < CP / 2; ++k)
+      av[k] = nn_f2{(src >= 0 && 2 * k < c) ? a[src * c + 2 * k] : 0.f, (src >= 0 && 2 * k + 1 < c) ? a[src * c + 2 * k + 1] : 0.f};
+  }
+  float best = INFINITY;
+  int besti = 0;
+  const int jb = blockIdx.y * chunk;
+  const int je = (jb + chunk < mb) ? jb + chunk : mb;
+  for (int p = jb / 2 + cg; 2 * p < je; p += 4) {       // ascending within a thread: strict < keeps the lowest index
+    const nn_f2 acc = nn_row_dist<CP>(bi + (long long)p * CP, av);
+    if (acc.x < best) {
+      best = acc.x;
+      besti = 2 * p;
+    }
+    if (2 * p + 1 < je && acc.y < best) {
+      best = acc.y;
+      besti = 2 * p + 1;
+    }
+  }
+  rv[cg][ar] = best;
+  ri[cg][ar] = besti;
+  __syncthreads();
+  if (cg == 0 && arow < ma) {                           // k_nn_rowmin's epilogue
+    float bv = rv[0][ar];
+    int bix = ri[0][ar];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      float v = rv[w][ar];
+      int i2 = ri[w][ar];
+      if (v < bv || (v == bv && i2 < bix)) {
+        bv = v;
+        bix = i2;
+      }
+    }
+    if (gridDim.y == 1) {
+      out_v[arow] = l2 ? sqrtf(bv + 1e-7f) : bv;
+      out_i[arow] = bix;
+    } else {
+      out_v[(long long)blockIdx.y * ma + arow] = bv;
+      out_i[(long long)blockIdx.y * ma + arow] = bix;
+    }
+  }
+}
+
 // ---- negative-pair mask ---------------------------------------------------------------------------------
 __global__ void k_table_fill2(Slot* t, long long cap) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -700,6 +847,61 @@ int gcl_nn_rowmin(const float* a, const int64_t* rows_a, int32_t ma, const float
   else if (c == 32) LAUNCH_NN(32);
   else LAUNCH_NN(64);
 #undef LAUNCH_NN
+  if (n_chunks > 1)
+    hipLaunchKernelGGL(k_nn_merge, dim3((unsigned)cdiv(ma, 256)), dim3(256), 0, st, (const float*)pv, (const int*)pi, ma,
+                       n_chunks, l2, dmin, argmin);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_nn_rowmin_any_scratch_len(int32_t ma, int32_t mb, int32_t c) {
+  if (ma <= 0 || mb <= 0 || c < 1 || c > 128) return 0;
+  const int chunk = nn_chunk_rows(ma, mb);
+  const long long n_chunks = cdiv(mb, chunk);
+  return nn_interleaved_words(mb, (int)cdiv(c, 8) * 8) + (n_chunks > 1 ? 2 * n_chunks * (long long)ma : 0);
+}
+
+int gcl_nn_rowmin_any(const float* a, const int64_t* rows_a, int32_t ma, const float* b, const int64_t* rows_b,
+                      int32_t mb, int32_t c, int32_t l2, int32_t* scratch, float* dmin, int32_t* argmin, void* stream) {
+  GCL_CHECK_ARG(a && b && dmin && argmin, "gcl_nn_rowmin_any: null pointer");
+  GCL_CHECK_ARG(ma > 0 && mb > 0, "gcl_nn_rowmin_any: empty input");
+  GCL_CHECK_ARG(c >= 1 && c <= 128, "gcl_nn_rowmin_any: feature width must lie in 1 .. 128 (got %d)", c);
+  GCL_CHECK_ARG(scratch, "gcl_nn_rowmin_any: scratch (int32[gcl_nn_rowmin_any_scratch_len]) is required");
+  hipStream_t st = (hipStream_t)stream;
+  const int cp = (int)cdiv(c, 8) * 8;
+  const int chunk = nn_chunk_rows(ma, mb);
+  const int n_chunks = (int)cdiv(mb, chunk);
+  dim3 grid((unsigned)cdiv(ma, NN_TA), (unsigned)n_chunks);
+  float* bi = (float*)scratch;
+  int32_t* part = scratch + nn_interleaved_words(mb, cp);
+  float* pv = n_chunks > 1 ? (float*)part : dmin;
+  int* pi = n_chunks > 1 ? part + (long long)n_chunks * ma : argmin;
+  hipLaunchKernelGGL(k_nn_interleave_pad, dim3((unsigned)cdiv(cdiv(mb, 2), 256 / cp)), dim3(256), 0, st, b,
+                     (const long long*)rows_b, mb, c, cp, bi);
+#define LAUNCH_NN_ANY(CC)                                                                                          \
+  case CC:                                                                                                         \
+    hipLaunchKernelGGL(k_nn_rowmin_any<CC>, grid, dim3(256), 0, st, a, (const long long*)rows_a, ma, c, (const float*)bi, \
+                       mb, chunk, l2, pv, pi);                                                                     \
+    break
+  switch (cp) {
+    LAUNCH_NN_ANY(8);
+    LAUNCH_NN_ANY(16);
+    LAUNCH_NN_ANY(24);
+    LAUNCH_NN_ANY(32);
+    LAUNCH_NN_ANY(40);
+    LAUNCH_NN_ANY(48);
+    LAUNCH_NN_ANY(56);
+    LAUNCH_NN_ANY(64);
+    LAUNCH_NN_ANY(72);
+    LAUNCH_NN_ANY(80);
+    LAUNCH_NN_ANY(88);
+    LAUNCH_NN_ANY(96);
+    LAUNCH_NN_ANY(104);
+    LAUNCH_NN_ANY(112);
+    LAUNCH_NN_ANY(120);
+    LAUNCH_NN_ANY(128);
+  }
+#undef LAUNCH_NN_ANY
   if (n_chunks > 1)
     hipLaunchKernelGGL(k_nn_merge, dim3((unsigned)cdiv(ma, 256)), dim3(256), 0, st, (const float*)pv, (const int*)pi, ma,
                        n_chunks, l2, dmin, argmin);

@@ -40,12 +40,16 @@ def pdist_min(A, B, dist_type="L2", rows_a=None, rows_b=None):
     mb = B.shape[0] if rows_b is None else rows_b.shape[0]
     dmin = torch.empty(ma, dtype=torch.float32, device=A.device)
     arg = torch.empty(ma, dtype=torch.int32, device=A.device)
-    ns = lib.gcl_nn_rowmin_scratch_len(ma, mb)
+    c = A.shape[1]
+    if c in (16, 32, 64):                      # the widths of the networks: the kernel instantiated for exactly that width
+        ns, fn, name = lib.gcl_nn_rowmin_scratch_len(ma, mb), lib.gcl_nn_rowmin, "gcl_nn_rowmin"
+    else:                                      # any other width up to 128 (an FPFH descriptor has 33 channels)
+        ns, fn, name = lib.gcl_nn_rowmin_any_scratch_len(ma, mb, c), lib.gcl_nn_rowmin_any, "gcl_nn_rowmin_any"
     scratch = torch.empty(ns, dtype=torch.int32, device=A.device) if ns else None
-    _lib.check(lib.gcl_nn_rowmin(_lib.ptr(A, torch.float32), _lib.ptr(rows_a, torch.int64), ma,
-                                 _lib.ptr(B, torch.float32), _lib.ptr(rows_b, torch.int64), mb, A.shape[1],
-                                 1 if dist_type == "L2" else 0, _lib.ptr(scratch), _lib.ptr(dmin), _lib.ptr(arg),
-                                 _lib.stream()), "gcl_nn_rowmin")
+    _lib.check(fn(_lib.ptr(A, torch.float32), _lib.ptr(rows_a, torch.int64), ma,
+                  _lib.ptr(B, torch.float32), _lib.ptr(rows_b, torch.int64), mb, c,
+                  1 if dist_type == "L2" else 0, _lib.ptr(scratch), _lib.ptr(dmin), _lib.ptr(arg),
+                  _lib.stream()), name)
     return dmin, arg
 
 

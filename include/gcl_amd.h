@@ -27,6 +27,9 @@
  *        -> gcl_nn_rowmin, gcl_ransac_register, gcl_ransac_register_batch, gcl_mutual_correspondences
  *   find_nearest_voxel_feature, calculate_M, inlier ratio   generalization_ETH/evaluate.py:63-77, :110-122, :160-169
  *        -> gcl_nn3_rowmin, gcl_nn_rowmin, gcl_mutual_match
+ *   eval_KITTI_per_pair, eval_3DMatch_scene (SC2-PCR benchmark)   scripts/SC2_PCR/test_KITTI.py:18-85,
+ *                                                    test_3DMatch.py:18-76, evaluate_metric.py
+ *        -> gcl_nn_rowmin / gcl_nn_rowmin_any (any descriptor width), gcl_sc2_register_batch, gcl_registration_stats
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless its name ends in _host;
@@ -516,6 +519,17 @@ int gcl_circle_group_bwd(const float* f, int32_t c, const int64_t* index, const 
 int64_t gcl_nn_rowmin_scratch_len(int32_t ma, int32_t mb);
 int gcl_nn_rowmin(const float* a, const int64_t* rows_a, int32_t ma, const float* b, const int64_t* rows_b,
                   int32_t mb, int32_t c, int32_t l2, int32_t* scratch, float* dmin, int32_t* argmin, void* stream);
+/* The same search at ANY width 1 <= c <= 128 (another c is an argument error): same arguments, same difference form in
+ * fp32, same tie rule, same l2.  The channels are zero-padded to the next multiple of 8 in the interleaved copy and in the
+ * A registers (a padded channel adds fma(0, 0, acc): exact).  Summation order: one chain per (row, column) over ascending
+ * channels, d2 = (a_0 - b_0)^2 rounded, then d2 = fma(a_k - b_k, a_k - b_k, d2), k = 1 .. c - 1 -- at c = 16 / 32 / 64 the
+ * order of gcl_nn_rowmin, bit for bit; that entry stays the one for those widths (lib/metrics.py::pdist_min dispatches;
+ * it is ~12 % faster at 32 channels).  A thread keeps its A row as single floats, which is what lets 128 channels fit
+ * (csrc/loss.hip, k_nn_rowmin_any).
+ * scratch: int32[gcl_nn_rowmin_any_scratch_len(ma, mb, c)], always required (0 for empty input or c out of range). */
+int64_t gcl_nn_rowmin_any_scratch_len(int32_t ma, int32_t mb, int32_t c);
+int gcl_nn_rowmin_any(const float* a, const int64_t* rows_a, int32_t ma, const float* b, const int64_t* rows_b,
+                      int32_t mb, int32_t c, int32_t l2, int32_t* scratch, float* dmin, int32_t* argmin, void* stream);
 
 /* 3-D nearest point (generalization_ETH/evaluate.py:110-122, find_nearest_voxel_feature): for every query q[i]
  * (float [m, 3]) the row j of p (float [n, 3]) that minimises (qx - px)^2 + (qy - py)^2 + (qz - pz)^2, evaluated in that
@@ -705,6 +719,27 @@ int gcl_ransac_register_batch(const float* src, const float* tgt, int32_t batch,
                               int32_t ransac_n, float edge_similarity, float check_distance, float max_corr_distance,
                               int32_t max_iteration, float confidence, const uint64_t* seeds, int32_t chunk, void* scratch,
                               float* trans16, int32_t* info, float* fit, float* labels, int32_t* hyp_status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Registration statistics of a BATCH of pairs in one launch: the scoring of the reference's SC2-PCR benchmark loops
+ * (scripts/SC2_PCR/test_KITTI.py:46-69, test_3DMatch.py:46-73; evaluate_metric.py TransformationLoss / ClassificationLoss).
+ * src_corr / tgt_corr float [batch, n_cap, 3]; pair b has n_b = counts[b] correspondences, read ON THE DEVICE (device int32
+ * [batch], clamped to [0, n_cap]; NULL: n_cap for every pair; the convention of gcl_ransac_register_batch's n_dev) -- rows
+ * at or beyond n_b are never read.  pred_trans / gt_trans float [batch, 16] (row-major [4, 4]).  re_thre in degrees,
+ * te_thre in centimetres.  stats double [batch, 10]:
+ *   0 success (RE < re_thre and TE < te_thre)      1 RE (deg) = acos(clamp((trace(R^T R_gt) - 1) / 2, -1, 1)) 180 / pi
+ *   2 TE (cm) = 100 |t - t_gt|                      3 #gt inliers: |R_gt p + t_gt - q| < inlier_threshold, the distance
+ *   4 column 3 / n_b                                  in fp32 as sum(d^2) ** 0.5
+ *   5 #gt inliers among the predicted inliers (the same expression under pred_trans)
+ *   6 precision = col 5 / #predicted   7 recall = col 5 / col 3   8 F1 = 2 col 5 / (#predicted + col 3)   (0 / 0 -> 0)
+ *   9 mean over the pair of |R p + t - q| under pred_trans (TransformationLoss's RMSE), in fp64
+ * RE, TE and the ratios are formed in fp64 from the fp32 matrices and the integer counts; n_b = 0 gives 0 in columns 3 - 9.
+ * pred_labels / gt_labels float [batch, n_cap] (each optional): the two labels, 0 from n_b on.
+ * One workgroup per pair, fixed-order reduction: the same table on every run.  batch == 0 returns 0 without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+int gcl_registration_stats(const float* src_corr, const float* tgt_corr, int32_t batch, int32_t n_cap, const int32_t* counts,
+                           const float* pred_trans, const float* gt_trans, float inlier_threshold, float re_thre,
+                           float te_thre, double* stats, float* pred_labels, float* gt_labels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Native step runtime (round 3): ONE call enqueues a whole pass.
