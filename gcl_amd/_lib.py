@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GCL_LIB_PATH", os.path.join(CSRC, "libgcl_hip.so"))   # override: diagnostic builds only
-SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip", "ransac.hip", "regstats.hip"]
+SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip", "ransac.hip", "regstats.hip", "fpfh.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gcl_amd.h")
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -195,11 +195,17 @@ SIGNATURES = {
     "gcl_pair_terms_fwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "gcl_pair_terms_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "gcl_fpfh_cell_keys": (_i32, [_vp, _i64, _vp, _i32, _f32, _vp, _vp]),
+    "gcl_fpfh_neighbours": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
+    "gcl_fpfh_normals": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "gcl_fpfh_spfh": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "gcl_fpfh_combine": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 PAIR_CHUNK = 128   # GCL_PAIR_CHUNK
 TRIPLET_OUT = 20   # GCL_TRIPLET_OUT
 PAIR_SQ, PAIR_SQ_POS, PAIR_NEG, PAIR_DIST = 0, 1, 2, 3      # GCL_PAIR_*
+FPFH_MAX_NN, FPFH_MAX_CLOUDS, FPFH_BINS = 128, 32767, 33     # GCL_FPFH_*
 
 _lib = None
 

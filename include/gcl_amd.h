@@ -942,6 +942,41 @@ int gcl_pair_terms_bwd(const float* f0, int64_t n0, const float* f1, int64_t n1,
                        const uint8_t* keep, int32_t m, int32_t mode, float thresh, float eps, const float* work,
                        const float* out, const float* g, float* df0, float* df1, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FPFH descriptors (csrc/fpfh.hip): what open3d's estimate_normals + compute_fpfh_feature give, made on the device for
+ * the `descriptor: fpfh` arm of the SC2-PCR benchmark (scripts/SC2_PCR/dataset.py:66-74 only loads them).  xyz [n, 3]
+ * is a concatenation of n_clouds clouds; offsets (DEVICE int64 [n_clouds + 1], ascending, offsets[0] = 0,
+ * offsets[n_clouds] = n) gives their rows, and a point's neighbours come from its own cloud only.  All arithmetic is fp64.
+ *
+ * gcl_fpfh_cell_keys: keys[i] = (cloud, cx, cy, cz) of point i on a grid whose edge is just above `radius`.  The caller
+ * sorts them ascending (ties in any order) and passes the sorted keys and the permutation (`order[s]` = row of the
+ * s-th key) to gcl_fpfh_neighbours with the SAME radius.
+ * gcl_fpfh_neighbours: idx[i] = the rows of the <= max_nn nearest points with d2 <= r2 (the point itself included) in
+ * ascending (d2, row) order, -1 behind them; cnt[i] their number.  d2 = (dx dx + dy dy) + dz dz with every operation
+ * rounded on its own, r2 = double(radius)^2.  Exact for any number of in-radius candidates.
+ * gcl_fpfh_normals: the unit eigenvector of the smallest eigenvalue of the covariance of the cnt[i] listed points,
+ * turned towards viewpoint (float [n_clouds, 3], NULL: the origin); (0, 0, 1) for fewer than 3 points.
+ * gcl_fpfh_spfh: spfh [n, 33] from the list entries 1 .. cnt - 1 (open3d's ComputePairFeatures, 11 bins per feature,
+ * integer counts times 100 / (cnt - 1)).
+ * gcl_fpfh_combine: fpfh [n, 33] = per feature 100 / sum times the sum over the entries 1 .. cnt - 1 with d2 != 0 of
+ * spfh[entry] / d2, plus spfh[i]; normalize != 0: each row divided by (its 2-norm + 1e-6).  fpfh must not alias spfh.
+ * An idx entry outside [0, n) is skipped, never dereferenced; cnt is clamped to [0, max_nn].  None of the calls needs
+ * scratch memory or waits for the host.
+ * ---------------------------------------------------------------------------------------------- */
+#define GCL_FPFH_MAX_NN 128
+#define GCL_FPFH_MAX_CLOUDS 32767
+#define GCL_FPFH_BINS 33
+int gcl_fpfh_cell_keys(const float* xyz, int64_t n, const int64_t* offsets, int32_t n_clouds, float radius, int64_t* keys,
+                       void* stream);
+int gcl_fpfh_neighbours(const float* xyz, int64_t n, const int64_t* offsets, int32_t n_clouds, const int64_t* sorted_keys,
+                        const int64_t* order, float radius, int32_t max_nn, int32_t* idx, int32_t* cnt, void* stream);
+int gcl_fpfh_normals(const float* xyz, int64_t n, const int32_t* idx, const int32_t* cnt, int32_t max_nn,
+                     const float* viewpoint, const int64_t* offsets, int32_t n_clouds, float* normals, void* stream);
+int gcl_fpfh_spfh(const float* xyz, const float* normals, int64_t n, const int32_t* idx, const int32_t* cnt, int32_t max_nn,
+                  float* spfh, void* stream);
+int gcl_fpfh_combine(const float* xyz, const float* spfh, int64_t n, const int32_t* idx, const int32_t* cnt, int32_t max_nn,
+                     int32_t normalize, float* fpfh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
