@@ -99,6 +99,7 @@ SIGNATURES = {
     "gcl_conv_bwd_weight_bounds": (_i32, [_vp, ctypes.POINTER(_i64), _i32, _i64, _vp, _vp]),
     "gcl_conv_bwd_weight_rg": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, ctypes.POINTER(_i64), _i32, _i32, _i32, _i32, _vp,
                                       _vp, _vp, _vp, _vp, _vp]),
+    "gcl_conv_bwd_weight_launch_shape": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, ctypes.POINTER(_i32)]),
     "gcl_conv_bwd_weight_rows_scratch_len": (_i64, [_i32, _i32, _i32, _i64]),
     "gcl_conv_bwd_weight_rows": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcl_presence_bits": (_i32, [_vp, _i32, _i64, _vp, _vp]),

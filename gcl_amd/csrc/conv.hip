@@ -2043,16 +2043,18 @@ __global__ void __launch_bounds__(256, 2) k_conv_bwd_weight_wg128(const float* _
 #undef GCLW_GATHER
 }
 
-__global__ void __launch_bounds__(256) k_bwd_weight_reduce(const float* __restrict__ slabs, SegOffW seg, int per,
+// T: the slab type -- float for the MFMA kernels, double for the generic kernel (whose result may be ONE cancelling sum)
+template <typename T>
+__global__ void __launch_bounds__(256) k_bwd_weight_reduce(const T* __restrict__ slabs, SegOffW seg, int per,
                                                            long long mat, float* dw) {
   const int k = blockIdx.y;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= mat) return;
-  float s = 0.f;
+  T s = 0;
   if (seg.off[k + 1] > seg.off[k]) {
     long long first = seg.off[k] / GCL_PAIR_CHUNK, last = seg.off[k + 1] / GCL_PAIR_CHUNK - 1;
     long long lo = first / per, hi = last / per;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;     // four slab loads in flight; fixed summation order
+    T s0 = 0, s1 = 0, s2 = 0, s3 = 0;     // four slab loads in flight; fixed summation order
     long long bx = lo;
     for (; bx + 3 <= hi; bx += 4) {
       s0 += slabs[(bx + k) * mat + e];
@@ -2063,7 +2065,7 @@ __global__ void __launch_bounds__(256) k_bwd_weight_reduce(const float* __restri
     for (; bx <= hi; ++bx) s0 += slabs[(bx + k) * mat + e];
     s = (s0 + s1) + (s2 + s3);
   }
-  dw[(long long)k * mat + e] = s;
+  dw[(long long)k * mat + e] = (float)s;
 }
 
 // RG mode: dw[k] = sum over the row ranges j of slab (j K + k), in order (four loads in flight, fixed tree)
@@ -2260,6 +2262,55 @@ static int bwd_weight_wgs(long long n_chunks) {
   if (w < 1) w = 1;
   if (w > cap) w = cap;
   return (int)w;
+}
+
+// Every host-side decision of a weight-gradient launch (gcl_conv_bwd_weight_rg launches what this says and nothing else;
+// gcl_conv_bwd_weight_launch_shape exports it, so that a test can pin a case to its kernel instance without a GPU).
+//   path: the kernel family (GCL_DW_PATH_*); ta x tb: the channel tile of a workgroup (the template arguments; 16 x 16 for
+//   the generic kernel, 128 x 128 for wg128); W workgroups in x, `per` chunks of 128 pairs each; stiles: channel tiles of
+//   the XCD-swizzled 1-D grid of cdiv(W, 8) * 8 * stiles workgroups (0: the 2-D grid W x tiles); rr, nr: rows per range
+//   and ranges of the range-grouped mode (grid cdiv(nr, 8) * 8 * K), else 0.
+struct DwLaunch {
+  int path, ta, tb, W, per, stiles, rr, nr;
+};
+static DwLaunch dw_launch_shape(int K, int ca, int cb, int prec, int planes_arg, int sorted_side, long long n_sorted,
+                                long long nc) {
+  const bool legacy_dw = (planes_arg & 2) != 0;      // bit 1 of `planes`: the 64 x 64-block kernel for this launch (tests)
+  const int planes = planes_arg & 1;
+  DwLaunch s = {GCL_DW_PATH_NONE, 0, 0, 0, 0, 0, 0, 0};
+  s.W = bwd_weight_wgs(nc);
+  s.per = (int)cdiv(nc > 0 ? nc : 1, s.W);
+  if ((ca % 32) != 0 || (cb % 32) != 0) {     // generic shapes: exact-fp32 VALU kernel, same slabs + ordered reduction
+    s.ta = s.tb = 16;
+    if (nc > 0) s.path = GCL_DW_PATH_GENERIC;
+    return s;
+  }
+  if (nc <= 0) return s;                      // no pairs: the reduce alone writes the zeros
+  if (dw_rg_shape(K, ca, cb, prec, planes, sorted_side, n_sorted)) {
+    s.path = GCL_DW_PATH_RG;
+    s.ta = ca;
+    s.tb = cb;
+    s.rr = dw_range_rows(n_sorted, K);
+    s.nr = (int)cdiv(n_sorted, s.rr);
+    return s;
+  }
+  static const int dwswz = [] { const char* e = getenv("GCL_DW_SWIZZLE"); return e ? atoi(e) : 1; }();
+  // plane images with Ca, Cb multiples of 128: one 128 x 128 block per workgroup, rows gathered once and shared by its four
+  // waves (k_conv_bwd_weight_wg128; GCL_DW_WG128=0 / bit 1 of `planes`: the 64 x 64 kernel)
+  static const int wg128 = [] { const char* e = getenv("GCL_DW_WG128"); return e ? atoi(e) : 1; }();
+  int tiles;
+  if (prec == 4 && planes && wg128 && !legacy_dw && ca % 128 == 0 && cb % 128 == 0) {
+    s.path = GCL_DW_PATH_WG128;
+    s.ta = s.tb = 128;
+    tiles = (ca / 128) * (cb / 128);
+  } else {
+    s.path = prec == 0 ? GCL_DW_PATH_F32 : (planes ? GCL_DW_PATH_PLANES : GCL_DW_PATH_SPLIT);
+    s.ta = (ca % 64 == 0) ? 64 : 32;
+    s.tb = (cb % 64 == 0) ? 64 : 32;
+    tiles = (ca / s.ta) * (cb / s.tb);
+  }
+  s.stiles = (dwswz && tiles > 1 && s.path != GCL_DW_PATH_F32) ? tiles : 0;      // the exact-f32 kernel keeps the 2-D grid
+  return s;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2605,12 +2656,15 @@ __global__ void __launch_bounds__(256) k_conv_generic(const float* __restrict__ 
 
 // weight gradient for generic shapes: workgroup = (range of 128-pair chunks, 16 x 16 tile of dW); thread (i, j) keeps
 // one element.  Per chunk the 128 x 16 pieces of both operands are staged in LDS.  Same slab / ordered-reduction scheme
-// as the MFMA kernels (k_bwd_weight_reduce), so the result is deterministic.
+// as the MFMA kernels (k_bwd_weight_reduce), so the result is deterministic.  Accumulators and slabs are fp64 (products of
+// two floats are exact there): with Ca = Cb = 1 a whole dW[k] is one sum of products of either sign, and an fp32 sum
+// loses to cancellation what the per-operator bound asks of it (2e-4 instead of 2e-6 on 300 pairs); the one rounding to
+// fp32 is the reduce's.
 __global__ void __launch_bounds__(256) k_conv_bwd_weight_generic(const float* __restrict__ A, const float* __restrict__ B,
                                                                  const int* __restrict__ pair_a,
                                                                  const int* __restrict__ pair_b, SegOffW seg, int K,
                                                                  int ca, int cb, long long n_chunks, int per,
-                                                                 float* slabs) {
+                                                                 double* slabs) {
   __shared__ float As[GCL_PAIR_CHUNK][17], Bs[GCL_PAIR_CHUNK][17];
   const int t = threadIdx.x, i = t >> 4, j = t & 15;
   const int tiles_b = (cb + 15) / 16;
@@ -2619,12 +2673,12 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_generic(const float* __
   const long long c1 = (c0 + per < n_chunks) ? c0 + per : n_chunks;
   if (c0 >= c1) return;
   const long long mat = (long long)ca * cb;
-  float acc = 0.f;
+  double acc = 0.;
   int kcur = 0;
   while (seg.off[kcur + 1] <= c0 * GCL_PAIR_CHUNK) ++kcur;
   auto flush = [&](int k) {
     if (ca0 + i < ca && cb0 + j < cb) slabs[(long long)(blockIdx.x + k) * mat + (long long)(ca0 + i) * cb + cb0 + j] = acc;
-    acc = 0.f;
+    acc = 0.;
   };
   for (long long c = c0; c < c1; ++c) {
     const long long pbase = c * GCL_PAIR_CHUNK;
@@ -2641,7 +2695,7 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_generic(const float* __
     }
     __syncthreads();
 #pragma unroll 8
-    for (int p = 0; p < GCL_PAIR_CHUNK; ++p) acc = fmaf(As[p][i], Bs[p][j], acc);
+    for (int p = 0; p < GCL_PAIR_CHUNK; ++p) acc = fma((double)As[p][i], (double)Bs[p][j], acc);
   }
   flush(kcur);
 }
@@ -2974,6 +3028,7 @@ int gcl_conv_fwd_fused_ld(const float* x, int64_t n_in, int32_t x_is_planes, con
 int64_t gcl_conv_bwd_weight_scratch_len(int32_t K, int32_t ca, int32_t cb, int64_t n_pairs_padded, int64_t n_sorted_rows) {
   long long nc = n_pairs_padded / GCL_PAIR_CHUNK;
   long long len = (long long)(bwd_weight_wgs(nc) + K) * ca * cb;
+  if ((ca % 32) != 0 || (cb % 32) != 0) return 2 * len + 2;      // generic shapes: fp64 slabs, aligned inside the scratch
   // range-grouped mode (one slab per (row range, offset) + the cell limits): reserved only for the shapes dw_rg_shape can
   // select -- the C >= 128 layers always take the classic path and would otherwise reserve ~100 MB each for nothing
   if (n_sorted_rows >= 32768 && K > 1 && K <= 27 && (ca == 32 || ca == 64) && (cb == 32 || cb == 64)) {
@@ -3016,24 +3071,26 @@ int gcl_conv_bwd_weight_rg(const float* a, int64_t n_a, const float* b, int64_t 
                            int32_t ca, int32_t cb, int32_t prec, const int32_t* a_amax, const int32_t* b_amax,
                            float* scratch, float* dw, const int32_t* rg_bounds, void* stream) {
   GCL_CHECK_ARG(a && b && pair_a && pair_b && seg_off_host && scratch && dw, "gcl_conv_bwd_weight: null pointer");
-  const bool legacy_dw = (planes & 2) != 0;      // bit 1 of `planes`: the 64 x 64-block kernel for this launch (tests)
+  const int planes_arg = planes;                 // bit 1: the 64 x 64-block kernel for this launch (dw_launch_shape)
   planes &= 1;
   GCL_CHECK_ARG(K >= 1 && K <= 125, "gcl_conv_bwd_weight: bad K");
   GCL_CHECK_ARG(ca > 0 && cb > 0, "gcl_conv_bwd_weight: channel counts (%d, %d) must be positive", ca, cb);
   GCL_CHECK_ARG(prec_ok(prec), "gcl_conv_bwd_weight: prec must be 0, 2, 3 or 4");
+  hipStream_t st = (hipStream_t)stream;
+  SegOffW seg;
+  for (int k = 0; k <= K; ++k) seg.off[k] = seg_off_host[k];
+  const long long nc = seg.off[K] / GCL_PAIR_CHUNK;
+  const long long mat = (long long)ca * cb;
   if ((ca % 32) != 0 || (cb % 32) != 0) {     // generic shapes: exact-fp32 VALU kernel, same slabs + ordered reduction
     GCL_CHECK_ARG(!planes, "gcl_conv_bwd_weight: plane images need channel counts that are multiples of 32");
     GCL_CHECK_ARG(n_a > 0 && n_b > 0, "gcl_conv_bwd_weight: empty operand");
-    hipStream_t gst = (hipStream_t)stream;
-    SegOffW gseg;
-    for (int k = 0; k <= K; ++k) gseg.off[k] = seg_off_host[k];
-    const long long gnc = gseg.off[K] / GCL_PAIR_CHUNK, gmat = (long long)ca * cb;
-    const int gW = bwd_weight_wgs(gnc), gper = (int)cdiv(gnc > 0 ? gnc : 1, gW);
-    if (gnc > 0)
-      hipLaunchKernelGGL(k_conv_bwd_weight_generic, dim3(gW, (unsigned)(cdiv(ca, 16) * cdiv(cb, 16))), dim3(256), 0, gst, a, b,
-                         pair_a, pair_b, gseg, K, ca, cb, gnc, gper, scratch);
-    hipLaunchKernelGGL(k_bwd_weight_reduce, dim3((unsigned)cdiv(gmat, 256), K), dim3(256), 0, gst, (const float*)scratch,
-                       gseg, gper, gmat, dw);
+    const DwLaunch g = dw_launch_shape(K, ca, cb, prec, planes_arg, sorted_side, 0, nc);
+    double* slabs64 = (double*)(((unsigned long long)scratch + 7ull) & ~7ull);      // scratch_len reserves the two floats
+    if (g.path == GCL_DW_PATH_GENERIC)
+      hipLaunchKernelGGL(k_conv_bwd_weight_generic, dim3(g.W, (unsigned)(cdiv(ca, 16) * cdiv(cb, 16))), dim3(256), 0, st, a, b,
+                         pair_a, pair_b, seg, K, ca, cb, nc, g.per, slabs64);
+    hipLaunchKernelGGL(k_bwd_weight_reduce<double>, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st,
+                       (const double*)slabs64, seg, g.per, mat, dw);
     GCL_CHECK_LAUNCH();
     return GCL_OK;
   }
@@ -3043,23 +3100,17 @@ int gcl_conv_bwd_weight_rg(const float* a, int64_t n_a, const float* b, int64_t 
                     (long long)n_b * cb * 4 < (1ll << 32) - (1ll << 20),
                 "gcl_conv_bwd_weight: operands must be non-empty and smaller than 4 GiB (buffer addressing)");
   const unsigned a_bytes = (unsigned)((long long)n_a * ca * 4), b_bytes = (unsigned)((long long)n_b * cb * 4);
-  hipStream_t st = (hipStream_t)stream;
-  SegOffW seg;
-  for (int k = 0; k <= K; ++k) seg.off[k] = seg_off_host[k];
-  long long nc = seg.off[K] / GCL_PAIR_CHUNK;
-  long long mat = (long long)ca * cb;
-  int W = bwd_weight_wgs(nc);
-  int per = (int)cdiv(nc > 0 ? nc : 1, W);
   GCL_CHECK_ARG(sorted_side >= 0 && sorted_side <= 2, "gcl_conv_bwd_weight: sorted_side must be 0, 1 (pair_a) or 2 (pair_b)");
   const long long n_sorted = sorted_side == 1 ? n_a : n_b;
-  if (nc > 0 && dw_rg_shape(K, ca, cb, prec, planes, sorted_side, n_sorted)) {
-    const int rr = dw_range_rows(n_sorted, K);
-    const int nr = (int)cdiv(n_sorted, rr);
+  const DwLaunch s = dw_launch_shape(K, ca, cb, prec, planes_arg, sorted_side, n_sorted, nc);
+  const int W = s.W, per = s.per;
+  if (s.path == GCL_DW_PATH_RG) {
+    const int nr = s.nr;
     const int* bounds = (const int*)rg_bounds;      // gcl_conv_bwd_weight_bounds of the sorted list, made once per map ...
     if (!bounds) {                                  // ... or here, per launch
       int* own = (int*)(scratch + (long long)nr * K * mat);
       hipLaunchKernelGGL(k_pair_bounds, dim3((unsigned)cdiv((long long)K * (nr + 1), 256)), dim3(256), 0, st,
-                         sorted_side == 1 ? pair_a : pair_b, seg, K, rr, nr, own);
+                         sorted_side == 1 ? pair_a : pair_b, seg, K, s.rr, nr, own);
       bounds = own;
     }
     dim3 rgrid((unsigned)(cdiv(nr, 8) * 8 * K));
@@ -3072,9 +3123,9 @@ int gcl_conv_bwd_weight_rg(const float* a, int64_t n_a, const float* b, int64_t 
     else if (prec == 3) LAUNCH_RG(TA, TB, 3);                          \
     else LAUNCH_RG(TA, TB, 4);                                         \
   }
-    if (ca == 64 && cb == 64) LAUNCH_RG_P(64, 64)
-    else if (ca == 64) LAUNCH_RG_P(64, 32)
-    else if (cb == 64) LAUNCH_RG_P(32, 64)
+    if (s.ta == 64 && s.tb == 64) LAUNCH_RG_P(64, 64)
+    else if (s.ta == 64) LAUNCH_RG_P(64, 32)
+    else if (s.tb == 64) LAUNCH_RG_P(32, 64)
     else LAUNCH_RG_P(32, 32)
 #undef LAUNCH_RG_P
 #undef LAUNCH_RG
@@ -3083,52 +3134,53 @@ int gcl_conv_bwd_weight_rg(const float* a, int64_t n_a, const float* b, int64_t 
     GCL_CHECK_LAUNCH();
     return GCL_OK;
   }
-  // plane images with Ca, Cb multiples of 128: one 128 x 128 block per workgroup, rows gathered once and shared by its four
-  // waves (k_conv_bwd_weight_wg128; GCL_DW_WG128=0 / bit 1 of `planes`: the 64 x 64 kernel)
-  static const int wg128 = [] { const char* e = getenv("GCL_DW_WG128"); return e ? atoi(e) : 1; }();
-  if (nc > 0 && prec == 4 && planes && wg128 && !legacy_dw && ca % 128 == 0 && cb % 128 == 0) {
+  if (s.path == GCL_DW_PATH_WG128) {
     const int tiles = (ca / 128) * (cb / 128);
-    static const int dwswz2 = [] { const char* s = getenv("GCL_DW_SWIZZLE"); return s ? atoi(s) : 1; }();
-    const int stiles = (dwswz2 && tiles > 1) ? tiles : 0;
-    const dim3 g2 = stiles ? dim3((unsigned)(cdiv(W, 8) * 8 * stiles)) : dim3(W, tiles);
+    const dim3 g2 = s.stiles ? dim3((unsigned)(cdiv(W, 8) * 8 * s.stiles)) : dim3(W, tiles);
     hipLaunchKernelGGL((k_conv_bwd_weight_wg128<false>), g2, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, ca, cb, nc, per,
-                       scratch, a_amax, b_amax, W, stiles, a_bytes, b_bytes);
-    hipLaunchKernelGGL(k_bwd_weight_reduce, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st, (const float*)scratch,
-                       seg, per, mat, dw);
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
-  }
-  if (nc > 0) {
-    int tca = (ca % 64 == 0) ? 64 : 32, tcb = (cb % 64 == 0) ? 64 : 32;
-    dim3 grid(W, (ca / tca) * (cb / tcb));
-    static const int dwswz = [] { const char* s = getenv("GCL_DW_SWIZZLE"); return s ? atoi(s) : 1; }();
-    const int stiles = (dwswz && grid.y > 1) ? (int)grid.y : 0;
+                       scratch, a_amax, b_amax, W, s.stiles, a_bytes, b_bytes);
+  } else if (s.path != GCL_DW_PATH_NONE) {
+    const int stiles = s.stiles;
+    dim3 grid(W, (ca / s.ta) * (cb / s.tb));
     dim3 sgrid = stiles ? dim3((unsigned)(cdiv(W, 8) * 8 * stiles)) : grid;
 #define LAUNCH_BWS(TA, TB, PLV)                                                                                     \
   hipLaunchKernelGGL((k_conv_bwd_weight_split<TA, TB, PLV>), sgrid, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, \
                      ca, cb, nc, per, scratch, a_amax, b_amax, W, stiles, a_bytes, b_bytes)
 #define LAUNCH_BW(TA, TB)                                                                                          \
   {                                                                                                                \
-    if (prec == 0)                                                                                                 \
+    if (s.path == GCL_DW_PATH_F32)                                                                                 \
       hipLaunchKernelGGL((k_conv_bwd_weight<TA, TB>), grid, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, ca, cb, \
                          nc, per, scratch);                                                                        \
     else if (prec == 2) LAUNCH_BWS(TA, TB, 2);                                                                     \
     else if (prec == 3) LAUNCH_BWS(TA, TB, 3);                                                                     \
-    else if (planes)                                                                                               \
+    else if (s.path == GCL_DW_PATH_PLANES)                                                                         \
       hipLaunchKernelGGL((k_conv_bwd_weight_split<TA, TB, 4, true>), sgrid, dim3(256), 0, st, a, b, pair_a, pair_b, \
                          seg, K, ca, cb, nc, per, scratch, a_amax, b_amax, W, stiles, a_bytes, b_bytes);           \
     else LAUNCH_BWS(TA, TB, 4);                                                                                    \
   }
-    if (tca == 64 && tcb == 64) LAUNCH_BW(64, 64)
-    else if (tca == 64) LAUNCH_BW(64, 32)
-    else if (tcb == 64) LAUNCH_BW(32, 64)
+    if (s.ta == 64 && s.tb == 64) LAUNCH_BW(64, 64)
+    else if (s.ta == 64) LAUNCH_BW(64, 32)
+    else if (s.tb == 64) LAUNCH_BW(32, 64)
     else LAUNCH_BW(32, 32)
 #undef LAUNCH_BW
 #undef LAUNCH_BWS
   }
-  hipLaunchKernelGGL(k_bwd_weight_reduce, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st, (const float*)scratch,
+  hipLaunchKernelGGL(k_bwd_weight_reduce<float>, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st, (const float*)scratch,
                      seg, per, mat, dw);
   GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_conv_bwd_weight_launch_shape(int32_t K, int32_t ca, int32_t cb, int32_t prec, int32_t planes, int32_t sorted_side,
+                                     int64_t n_sorted_rows, int64_t n_pairs_padded, int32_t out[8]) {
+  GCL_CHECK_ARG(out && K >= 1 && K <= 125 && ca > 0 && cb > 0 && prec_ok(prec) && sorted_side >= 0 && sorted_side <= 2 &&
+                    n_sorted_rows >= 0 && n_pairs_padded >= 0 && n_pairs_padded % GCL_PAIR_CHUNK == 0,
+                "gcl_conv_bwd_weight_launch_shape: bad argument");
+  GCL_CHECK_ARG(!(planes & 1) || (prec == 4 && ca % 32 == 0 && cb % 32 == 0),
+                "gcl_conv_bwd_weight_launch_shape: plane images are the fp16x3 operand format (channel multiples of 32)");
+  const DwLaunch s = dw_launch_shape(K, ca, cb, prec, planes, sorted_side, n_sorted_rows, n_pairs_padded / GCL_PAIR_CHUNK);
+  const int v[8] = {s.path, s.ta, s.tb, s.W, s.per, s.stiles, s.rr, s.nr};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
   return GCL_OK;
 }
 

@@ -224,6 +224,8 @@ int gcl_table_sort_pre(const int32_t* tbl, int32_t K, int64_t n, int32_t window,
  *   e.g. the 16-dim head of demo.py:29, `final` 64 -> 16) is a "generic shape": gcl_pack_weights then writes plain fp32
  *   W_eff[k][Cin_eff][Cout_eff] (prec ignored), gcl_conv_fwd / gcl_conv_fwd_fused / gcl_conv_bwd_weight run exact-fp32
  *   VALU kernels (amax pointers, plane images and `stats` are not used / not accepted there).
+ *   The generic weight gradient accumulates and keeps its per-workgroup slabs in fp64 and rounds once (with Ca = Cb = 1 a
+ *   dW[k] is one sum of products of either sign); gcl_conv_bwd_weight_scratch_len accounts for it.
  * gcl_conv_fwd: Y[row(j)] = sum_k X[tbl[k*n_out+j]] . Wp_k (+ bias); tbl == NULL means K == 1, identity.
  *   x_is_planes != 0 (prec 4 only): x points at the gcl_split_planes image of X instead of X (no split in the kernel).
  *   X has n_in rows (n_in * Cin * 4 < 4 GiB: rows are gathered through a buffer resource, absent neighbours read 0).
@@ -347,6 +349,23 @@ int gcl_conv_bwd_weight_rg(const float* a, int64_t n_a, const float* b, int64_t 
                            const int32_t* pair_a, const int32_t* pair_b, const int64_t* seg_off_host, int32_t K,
                            int32_t ca, int32_t cb, int32_t prec, const int32_t* a_amax, const int32_t* b_amax,
                            float* scratch, float* dw, const int32_t* rg_bounds, void* stream);
+/* What gcl_conv_bwd_weight(_rg) launches for a shape: host arithmetic, no GPU (the dispatcher itself calls the same
+ * function; tests pin their cases to kernel instances with it).  planes, sorted_side as above; n_sorted_rows = rows of the
+ * operand on the sorted side (n_a or n_b; any value with sorted_side 0); n_pairs_padded = seg_off_host[K].
+ * out = {path (GCL_DW_PATH_*), TA, TB (channel tile of a workgroup: the template arguments; 16 x 16 for the generic
+ * kernel), W (workgroups along the pair list), per (128-pair chunks per workgroup), swizzled tiles (> 0: a 1-D grid of
+ * ceil(W / 8) * 8 * tiles workgroups, channel tiles of one pair range on one XCD; 0: a W x tiles grid), rr (rows per
+ * range), n_ranges (range-grouped mode: a grid of ceil(n_ranges / 8) * 8 * K workgroups; else both 0)}.  The number of
+ * planes of a split-precision instance follows from prec. */
+#define GCL_DW_PATH_NONE 0      /* no pairs: only the reduce runs (dW = 0) */
+#define GCL_DW_PATH_GENERIC 1   /* k_conv_bwd_weight_generic: channel counts that are no multiples of 32 */
+#define GCL_DW_PATH_F32 2       /* k_conv_bwd_weight<TA, TB> */
+#define GCL_DW_PATH_SPLIT 3     /* k_conv_bwd_weight_split<TA, TB, PL, false, false>: fp32 rows split on the fly */
+#define GCL_DW_PATH_PLANES 4    /* k_conv_bwd_weight_split<TA, TB, 4, true, false>: plane images */
+#define GCL_DW_PATH_RG 5        /* k_conv_bwd_weight_split<TA, TB, PL, false, true>: range-grouped */
+#define GCL_DW_PATH_WG128 6     /* k_conv_bwd_weight_wg128: plane images, 128 x 128 block */
+int gcl_conv_bwd_weight_launch_shape(int32_t K, int32_t ca, int32_t cb, int32_t prec, int32_t planes, int32_t sorted_side,
+                                     int64_t n_sorted_rows, int64_t n_pairs_padded, int32_t out[8]);
 
 /* First layer (Cin <= 4, Cout a multiple of 32, any ks <= 5): VALU kernels over the nbr table (one 32-column block per
  * workgroup column).  Other first-layer widths go through gcl_conv_fwd / gcl_conv_bwd_weight (generic shapes). */
