@@ -10,8 +10,14 @@
 // k2 = 20, 20 x 20 power iteration, weighted Kabsch with a 3 x 3 Jacobi SVD) runs as one wavefront per seed.
 // Ties (argsort / argmax of equal values, unspecified in the reference) go to the LOWEST index; per-seed power
 // iterations always run num_iterations steps (see oracle/sc2pcr_oracle.py).
-// A BATCH of pairs (gcl_sc2_register_batch) runs the same kernel bodies with the pair as the grid's z dimension; see the
-// kernels behind the bodies, below.
+// Every stage has ONE body (a __device__ function).  gcl_sc2_register launches the bodies on one pair's plain arguments; a
+// BATCH of pairs (gcl_sc2_register_batch) runs the same bodies with the pair as the grid's z dimension; the staged entries
+// (gcl_sc2_confidence ... gcl_sc2_refine) launch the same bodies or an independent form of a stage (dense products,
+// k_sc_tight_bits, k_sc_seed_knn).
+// RULE: a body that is compiled into more than one __global__ kernel has every floating-point sum of products written out --
+// explicit __builtin_fmaf / __builtin_fma, or separate operations under `#pragma clang fp contract(off)` -- so that its bits
+// cannot depend on the kernel it is inlined into (left to the compiler, the same source line was contracted differently in
+// different kernels).  A body behind exactly one kernel may leave them as written.
 #include "common.h"
 #include "kabsch.h"
 
@@ -161,7 +167,7 @@ __device__ __forceinline__ void sc_matvec_folded(int n, float* x, int* done, con
         float y = 0.f;
         for (int c = 0; c < SC_CHUNKS; ++c) y += prev[(size_t)c * n + i];
         xs[i] = y;
-        ss += y * y;
+        ss = __builtin_fmaf(y, y, ss);
       }
       red[v] = ss;
     }
@@ -179,7 +185,7 @@ __device__ __forceinline__ void sc_matvec_folded(int n, float* x, int* done, con
       xs[i] = xn;
       if (writer) {
         const float xo = x[i];
-        close = close && (fabsf(xn - xo) <= 1e-8f + 1e-5f * fabsf(xo));
+        close = close && (fabsf(xn - xo) <= __builtin_fmaf(1e-5f, fabsf(xo), 1e-8f));
         x[i] = xn;
       }
     }
@@ -214,21 +220,6 @@ __device__ __forceinline__ void sc_matvec_folded(int n, float* x, int* done, con
   for (; q < cnt; ++q) acc = __builtin_fmaf(e[q].m, xs[e[q].j], acc);
   partial[seg] = acc;
 }
-__global__ void __launch_bounds__(SC_TILE) k_sc_matvec_sparse(int n, const float* __restrict__ x, const int* __restrict__ done,
-                                                              float* partial, const int* __restrict__ count,
-                                                              const ScEntry* __restrict__ entries) {
-  if (*done) return;
-  const int i = blockIdx.x * SC_TILE + threadIdx.x;
-  if (i >= n) return;
-  const int per = (n + SC_CHUNKS - 1) / SC_CHUNKS;
-  const size_t seg = (size_t)blockIdx.y * n + i;
-  const ScEntry* e = entries + seg * per;
-  const int cnt = count[seg];
-  float acc = 0.f;
-  for (int q = 0; q < cnt; ++q) acc = __builtin_fmaf(e[q].m, x[e[q].j], acc);
-  partial[seg] = acc;
-}
-
 // one workgroup: y = sum of the partials, x_new = y / (|y| + 1e-6), done = allclose(x_new, x_old) (:176-181).
 // `nt` threads stand for 1024: thread t for the rows of t, t + nt, ... < 1024, each with its own sum (red[1024]).
 __device__ void sc_normalize_by(int t, int nt, const float* partial, int n, float* x, int* done, float* red, int* allc) {
@@ -238,7 +229,7 @@ __device__ void sc_normalize_by(int t, int nt, const float* partial, int n, floa
     for (int i = v; i < n; i += 1024) {
       float y = 0.f;
       for (int c = 0; c < SC_CHUNKS; ++c) y += pv[(size_t)c * n + i];
-      ss += y * y;
+      ss = __builtin_fmaf(y, y, ss);
     }
     red[v] = ss;
   }
@@ -254,7 +245,7 @@ __device__ void sc_normalize_by(int t, int nt, const float* partial, int n, floa
     float y = 0.f;
     for (int c = 0; c < SC_CHUNKS; ++c) y += pv[(size_t)c * n + i];
     const float xn = y * inv, xo = x[i];
-    close = close && (fabsf(xn - xo) <= 1e-8f + 1e-5f * fabsf(xo));
+    close = close && (fabsf(xn - xo) <= __builtin_fmaf(1e-5f, fabsf(xo), 1e-8f));
     x[i] = xn;
   }
   if (!close) *allc = 0;      // benign race: every writer stores 0
@@ -426,7 +417,7 @@ __global__ void __launch_bounds__(256) k_sc_seed_knn(const float* __restrict__ s
 // read once for all SK_TS seeds (lane = word, coalesced): SK_TS x fewer bytes, the AND + popcount work unchanged.  The 64
 // lanes' partial counts of the SK_TS seeds are packed four to a 64-bit word and summed by a reduce-scatter butterfly (7 word
 // shuffles per column instead of 6 per column and seed).  Counts that are not hard-compatible are zero, as in k_sc_seed_knn;
-// the values go to vals[seed][column] (uint16: a count is <= n <= 8192) and k_sc_seed_topk makes the same selection from them.
+// the values go to vals[seed][column] (uint16: a count is <= n <= 8192) and sc_seed_topk makes the same selection from them.
 // Integers throughout: the k1 lists are those of k_sc_seed_knn (tests: one call == staged calls, bit for bit).
 constexpr int SK_TS = 16;
 __device__ __forceinline__ void sc_seed_sc2(const float* __restrict__ src, const float* __restrict__ tgt,
@@ -528,7 +519,7 @@ __device__ __forceinline__ unsigned sc_topk_key(unsigned short v, int j, int n) 
 }
 // maximum over the wave, uniform: four DPP steps inside every row of 16 lanes (quad swaps, half-row mirror, row mirror),
 // then the four rows through scalar registers -- ~ 10 short instructions; a butterfly of ds_bpermute shuffles was a chain
-// of six LDS-pipe round trips (k_sc_seed_topk: 82 -> 60 us with it, the rounds were nothing but that latency)
+// of six LDS-pipe round trips (sc_seed_topk: 82 -> 60 us with it, the rounds were nothing but that latency)
 __device__ __forceinline__ unsigned sc_wave_umax(unsigned v) {
   v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));       // quad_perm [1,0,3,2]
   v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));       // quad_perm [2,3,0,1]
@@ -618,7 +609,7 @@ __device__ __forceinline__ void sc_seed_trans(const float* __restrict__ src, con
     __syncthreads();
     float y = 0.f;
 #pragma unroll
-    for (int q = 0; q < 32; ++q) y += M[q] * xv[q];
+    for (int q = 0; q < 32; ++q) y = __builtin_fmaf(M[q], xv[q], y);      // one chain in q's order
     const float nrm = sqrtf(wave_sum(lane < k2 ? y * y : 0.f));
     x = lane < k2 ? y / (nrm + 1e-6f) : 0.f;
     __syncthreads();
@@ -640,103 +631,15 @@ __device__ __forceinline__ void sc_seed_trans(const float* __restrict__ src, con
   }
 }
 
-// ---- inlier count of every hypothesis (:149-161) --------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_sc_fitness(const float* __restrict__ src, const float* __restrict__ tgt, int n,
-                                                    const float* __restrict__ trans, float thr, float* fitness) {
-  __shared__ int red[256];
-  const float* T = trans + 12 * blockIdx.x;
-  int cnt = 0;
-  for (int j = threadIdx.x; j < n; j += 256) {
-    const P3 p = ld3(src, j), q = ld3(tgt, j);
-    const float x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3] - q.x;
-    const float y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7] - q.y;
-    const float z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11] - q.z;
-    cnt += sqrtf(x * x + y * y + z * z) < thr;
-  }
-  red[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) fitness[blockIdx.x] = (float)red[0];
-}
-
-// ---- post refinement (:238-279): weighted Kabsch over the inliers until the inlier count stops changing -------
-constexpr int RF_BLOCKS = 64, RF_TERMS = 17;   // sum w, sum w a (3), sum w b (3), sum w a b^T (9), count
-__global__ void __launch_bounds__(256) k_sc_refine_accum(const float* __restrict__ src, const float* __restrict__ tgt,
-                                                         int n, const float* __restrict__ T, float thr,
-                                                         const int* __restrict__ state, double* partial) {
-  if (state[0]) return;
-  __shared__ double red[256];
-  double acc[RF_TERMS];
-  for (int k = 0; k < RF_TERMS; ++k) acc[k] = 0;
-  for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += RF_BLOCKS * 256) {
-    const P3 p = ld3(src, j), q = ld3(tgt, j);
-    const float x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3] - q.x;
-    const float y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7] - q.y;
-    const float z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11] - q.z;
-    const float d = sqrtf(x * x + y * y + z * z);
-    if (d < thr) {
-      const float r = d / thr;
-      const double w = 1.f / (1.f + r * r);
-      const double a[3] = {p.x, p.y, p.z}, b[3] = {q.x, q.y, q.z};
-      acc[0] += w;
-      for (int c = 0; c < 3; ++c) { acc[1 + c] += w * a[c]; acc[4 + c] += w * b[c]; }
-      for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k) acc[7 + 3 * i + k] += w * a[i] * b[k];
-      acc[16] += 1.0;
-    }
-  }
-  for (int k = 0; k < RF_TERMS; ++k) {
-    red[threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x * RF_TERMS + k] = red[0];
-    __syncthreads();
-  }
-}
-
-// state[0] = done, state[1] = previous inlier count
-__global__ void k_sc_refine_solve(const double* __restrict__ partial, int* state, float* T) {
-  if (state[0]) return;
-  double s[RF_TERMS];
-  for (int k = 0; k < RF_TERMS; ++k) {
-    double v = 0;
-    for (int b = 0; b < RF_BLOCKS; ++b) v += partial[b * RF_TERMS + k];
-    s[k] = v;
-  }
-  const int cnt = (int)s[16];
-  if (abs(cnt - state[1]) < 1) {      // :266-267
-    state[0] = 1;
-    return;
-  }
-  state[1] = cnt;
-  const double sw = s[0] + 1e-6;      // common.py:22-23
-  double ca[3], cb[3], H[9];
-  for (int c = 0; c < 3; ++c) { ca[c] = s[1 + c] / sw; cb[c] = s[4 + c] / sw; }
-  // sum w (a - ca)(b - cb)^T = sum w a b^T - ca (sum w b)^T - (sum w a) cb^T + (sum w) ca cb^T
-  for (int i = 0; i < 3; ++i)
-    for (int k = 0; k < 3; ++k)
-      H[3 * i + k] = s[7 + 3 * i + k] - ca[i] * s[4 + k] - s[1 + i] * cb[k] + s[0] * ca[i] * cb[k];
-  kabsch_from_H(H, ca, cb, T);
-}
-
-// |T p - q|^2 with the contraction spelt out (contraction off), for the BATCH kernels of the inlier count and the refinement: the
-// single-pair kernels k_sc_fitness and k_sc_refine_all leave `T[0] * p.x + T[1] * p.y + ...` to the compiler, and which product it
-// rounds before the fma differs between a kernel and the same source inlined into another -- a residual then differs in its
-// last bit, a point within rounding of the threshold changes sides.  So those two kernels (and k_sc_seed_trans, for its Kabsch
-// step) keep their own source, untouched, and the batch kernels compute what THEY were compiled to (read off their gfx950 code):
-//   `packed` (all of a thread's points in k_sc_fitness but an odd last one):
-//     x = fma(T2, pz, fma(T0, px, T1 py)) + T3 - qx,  y, z alike,  d2 = fma(dz, dz, fma(dx, dx, dy dy))
-//   otherwise (that odd last point; every point of k_sc_refine_all):
-//     x = fma(pz, T2, fma(py, T1, T0 px)) + T3 - qx,  y = ((fma(T4, px, T5 py) + T6 pz) + T7) - qy,
-//     z = fma(pz, T10, fma(px, T8, T9 py)) + T11 - qz,  d2 = fma(dy, dy, dx dx) + dz dz
-// A compiler that builds those two kernels differently needs the forms read off again; tests/test_gpu_sc2_batch.py compares
-// the batch's fitness counts, hypotheses and transformations with the single call's bit for bit.
+// |T p - q|^2, the residual of the inlier count and of the refinement, with every operation written out (contraction off): a
+// residual that differs in its last bit moves a point within rounding of the threshold to the other side.  Two forms, chosen
+// by `packed`; they are the DEFINITION of the residual for every kernel that counts inliers or refines:
+//   packed:     x = fma(T2, pz, fma(T0, px, T1 py)) + T3 - qx,  y, z alike,  d2 = fma(dz, dz, fma(dx, dx, dy dy))
+//   otherwise:  x = fma(pz, T2, fma(py, T1, T0 px)) + T3 - qx,  y = ((fma(T4, px, T5 py) + T6 pz) + T7) - qy,
+//               z = fma(pz, T10, fma(px, T8, T9 py)) + T11 - qz,  d2 = fma(dy, dy, dx dx) + dz dz
+// sc_fitness takes a thread's points in pairs by the packed form and an odd last one by the other; sc_refine_all and the
+// labels of sc_finish take every point by the other.  (Two forms and not one because the results of earlier versions are
+// kept bit for bit.)
 __device__ __forceinline__ float sc_residual2(const float* T, const P3& p, const P3& q, bool packed) {
 #pragma clang fp contract(off)
   float x, y, z;
@@ -752,13 +655,43 @@ __device__ __forceinline__ float sc_residual2(const float* T, const P3& p, const
   const float dx = (x + T[3]) - q.x, dy = (y + T[7]) - q.y, dz = (z + T[11]) - q.z;
   return packed ? __builtin_fmaf(dz, dz, __builtin_fmaf(dx, dx, dy * dy)) : __builtin_fmaf(dy, dy, dx * dx) + dz * dz;
 }
+
+// ---- inlier count of one hypothesis T (:149-161), one workgroup of 256 ------------------------------------------
+// a thread's points t, t + 256, ... in pairs by the packed residual, an odd last one on its own
+__device__ __forceinline__ void sc_fitness(const float* __restrict__ src, const float* __restrict__ tgt, int n,
+                                           const float* __restrict__ T, float thr, float* fitness) {
+  __shared__ int red[256];
+  __shared__ float Ts[12];
+  const int t = threadIdx.x;
+  if (t < 12) Ts[t] = T[t];
+  __syncthreads();
+  const int trips = t < n ? (n - 1 - t) / 256 + 1 : 0, packed = trips & ~1;
+  int cnt = 0;
+  for (int k = 0; k < packed; ++k) {
+    const int j = t + 256 * k;
+    cnt += sqrtf(sc_residual2(Ts, ld3(src, j), ld3(tgt, j), true)) < thr;
+  }
+  if (trips & 1) {
+    const int j = t + 256 * packed;
+    cnt += sqrtf(sc_residual2(Ts, ld3(src, j), ld3(tgt, j), false)) < thr;
+  }
+  red[t] = cnt;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (t == 0) *fitness = (float)red[0];
+}
+
+// ---- post refinement (:238-279): weighted Kabsch over the inliers until the inlier count stops changing -------
+constexpr int RF_TERMS = 17;   // sum w, sum w a (3), sum w b (3), sum w a b^T (9), count
+constexpr int RF_BLOCKS = 64;  // only gcl_sc2_refine_partial_len's answer: the length of gcl_sc2_refine's unused `partial`
 // The whole refinement in ONE launch (round 5): a single 1024-thread workgroup runs the iterations and stops at convergence
 // (the two-kernel form launched 2 x 20 kernels per registration, most of them no-ops behind the `done` flag once the inlier
 // count stands still: 0.3 ms of dependent launches per pair).  A thread owns points t, t + 1024, ... and sums their 17
 // weighted-Kabsch terms in fp64 in that order; the 64 lanes of a wave are combined by a butterfly of shuffles, the 16 waves
-// in wave order by thread 0 -- a fixed order, so the result is reproducible; it is NOT the summation order of the two-kernel
-// form (64 blocks of 256, a halving tree each): the fp64 sums may differ in their last bits, the fp32 transformation
-// practically never (tests/test_gpu_parity.py compares the two forms on the golden problems).
+// in wave order by thread 0 -- a fixed order, so the result is reproducible.
 __device__ __forceinline__ void sc_refine_all(const float* __restrict__ src, const float* __restrict__ tgt, int n,
                                               float thr, int iterations, int* state, float* T) {
   __shared__ double ws[16][RF_TERMS];
@@ -775,18 +708,23 @@ __device__ __forceinline__ void sc_refine_all(const float* __restrict__ src, con
     for (int k = 0; k < RF_TERMS; ++k) acc[k] = 0;
     for (int j = t; j < n; j += 1024) {
       const P3 p = ld3(src, j), q = ld3(tgt, j);
-      const float d = sqrtf(sc_residual2(Ts, p, q, false));      // k_sc_refine_all's contraction of the residual, spelt out
+      const float d = sqrtf(sc_residual2(Ts, p, q, false));
       if (d < thr) {
         const float r = d / thr;
-        const double wgt = 1.f / (1.f + r * r);
+        const double wgt = 1.f / __builtin_fmaf(r, r, 1.f);
         const double a[3] = {p.x, p.y, p.z}, b[3] = {q.x, q.y, q.z};
         acc[0] += wgt;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { acc[1 + c] += wgt * a[c]; acc[4 + c] += wgt * b[c]; }
+        for (int c = 0; c < 3; ++c) {
+          acc[1 + c] = __builtin_fma(wgt, a[c], acc[1 + c]);
+          acc[4 + c] = __builtin_fma(wgt, b[c], acc[4 + c]);
+        }
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < 3; ++i) {
+          const double wa = wgt * a[i];
 #pragma unroll
-          for (int k = 0; k < 3; ++k) acc[7 + 3 * i + k] += wgt * a[i] * b[k];
+          for (int k = 0; k < 3; ++k) acc[7 + 3 * i + k] = __builtin_fma(wa, b[k], acc[7 + 3 * i + k]);
+        }
         acc[16] += 1.0;
       }
     }
@@ -813,9 +751,12 @@ __device__ __forceinline__ void sc_refine_all(const float* __restrict__ src, con
         const double sw = s[0] + 1e-6;      // common.py:22-23
         double ca[3], cb[3], H[9];
         for (int c = 0; c < 3; ++c) { ca[c] = s[1 + c] / sw; cb[c] = s[4 + c] / sw; }
-        for (int i = 0; i < 3; ++i)
+        // sum w (a - ca)(b - cb)^T = sum w a b^T - ca (sum w b)^T - (sum w a) cb^T + (sum w) ca cb^T
+        for (int i = 0; i < 3; ++i) {
+          const double swca = s[0] * ca[i];
           for (int k = 0; k < 3; ++k)
-            H[3 * i + k] = s[7 + 3 * i + k] - ca[i] * s[4 + k] - s[1 + i] * cb[k] + s[0] * ca[i] * cb[k];
+            H[3 * i + k] = __builtin_fma(swca, cb[k], __builtin_fma(-s[1 + i], cb[k], __builtin_fma(-ca[i], s[4 + k], s[7 + 3 * i + k])));
+        }
         float Tn[12];
         kabsch_from_H(H, ca, cb, Tn);
         for (int k = 0; k < 12; ++k) Ts[k] = Tn[k];
@@ -915,20 +856,16 @@ __device__ __forceinline__ void sc_finish(const float* __restrict__ src, const f
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < 16) out16[i] = i < 12 ? T[i] : (i == 15 ? 1.f : 0.f);
   if (i >= n) return;
-  const P3 s = ld3(src, i), g = ld3(tgt, i);
-  const float wx = T[0] * s.x + T[1] * s.y + T[2] * s.z + T[3] - g.x;
-  const float wy = T[4] * s.x + T[5] * s.y + T[6] * s.z + T[7] - g.y;
-  const float wz = T[8] * s.x + T[9] * s.y + T[10] * s.z + T[11] - g.z;
-  labels[i] = sqrtf(wx * wx + wy * wy + wz * wz) < thr ? 1.f : 0.f;
+  labels[i] = sqrtf(sc_residual2(T, ld3(src, i), ld3(tgt, i), false)) < thr ? 1.f : 0.f;
 }
 
-// ---- the kernels of the default one-call form: each body above as the single-pair kernel it was, and once more for a BATCH ------
-// A single-pair kernel is its body with the arguments it always had -- except k_sc_fitness, k_sc_seed_trans and k_sc_refine_all,
-// which keep their own source above (see sc_residual2 for why); sc_seed_trans and sc_refine_all serve the batch alone.  The batch kernels (gcl_sc2_register_batch) run the SAME bodies with the pair as the grid's z dimension: a launch is sized for
-// n_cap correspondences and max(n_seeds) seeds, every workgroup reads its own pair's n / n_seeds from the control block -- a
-// BY-VALUE kernel argument filled from the caller's host arrays: no copy on the stream, no read-back -- points the body at the
-// pair's rows, scratch slot and output rows, and returns at once when it lies beyond the pair's own extent.  Inside the body
-// per, words and the tile counts come from that n as in a single call, so a pair's results do not depend on its neighbours.
+// ---- the kernels: the staged entries' single-pair wrappers of the bodies above, then the BATCH kernels ------------------------
+// A single-pair kernel (the staged entries, gcl_sc2_register) is its body with plain arguments.  The batch kernels
+// (gcl_sc2_register_batch) run the SAME bodies with the pair as the grid's z dimension: a launch is sized for n_cap correspondences and
+// max(n_seeds) seeds, every workgroup reads its own pair's n / n_seeds from the control block -- a BY-VALUE kernel argument
+// filled from the caller's host arrays: no copy on the stream, no read-back -- points the body at the pair's rows, scratch slot
+// and output rows, and returns at once when it lies beyond the pair's own extent.  Inside the body per, words and the tile
+// counts come from that n alone, so a pair's results do not depend on its neighbours.
 __global__ void __launch_bounds__(256) k_sc_sparse_build(const float* __restrict__ src, const float* __restrict__ tgt, int n,
                                                          float d2_thre, int* count, ScEntry* entries, float tight_thr,
                                                          unsigned long long* bits) {
@@ -953,149 +890,18 @@ __global__ void __launch_bounds__(256) k_sc_seed_sc2(const float* __restrict__ s
 __global__ void __launch_bounds__(64) k_sc_seed_topk(const unsigned short* __restrict__ vals, int n, int k1, int* knn) {
   sc_seed_topk(vals, n, k1, knn);
 }
-// the single-pair kernel as it always was: its sums of products are left to the compiler, whose choices differ between
-// this kernel and the body inlined into the batch kernel (see k_scb_fitness), so the two do not share source
 __global__ void __launch_bounds__(64) k_sc_seed_trans(const float* __restrict__ src, const float* __restrict__ tgt,
                                                       const int* __restrict__ knn, int k1, int k2, float d_thre,
                                                       int num_iterations, float* trans) {
-  __shared__ float ps[32][3], pt[32][3], fs[32][3], ft[32][3], xv[32];
-  __shared__ unsigned rowbits[32];
-  const int lane = threadIdx.x, s = blockIdx.x;
-  if (lane < k1) {
-    const int r = knn[s * k1 + lane];
-    for (int a = 0; a < 3; ++a) { ps[lane][a] = src[3 * r + a]; pt[lane][a] = tgt[3 * r + a]; }
-  }
-  __syncthreads();
-  unsigned rb = 0;
-  if (lane < k1)
-    for (int b = 0; b < k1; ++b) {
-      const float cd = fabsf(dist3(P3{ps[lane][0], ps[lane][1], ps[lane][2]}, P3{ps[b][0], ps[b][1], ps[b][2]}) -
-                             dist3(P3{pt[lane][0], pt[lane][1], pt[lane][2]}, P3{pt[b][0], pt[b][1], pt[b][2]}));
-      rb |= (unsigned)(cd < d_thre) << b;
-    }
-  if (lane < 32) rowbits[lane] = lane < k1 ? rb : 0u;
-  __syncthreads();
-  // local second-order score (:97) and its k2 largest (value desc, index asc): rank = position in the fine list
-  const int score = lane < k1 ? __popc(rowbits[0] & rb) : -1;
-  int rank = 0;
-  for (int c = 0; c < k1; ++c) {
-    const int sc = __popc(rowbits[0] & rowbits[c]);
-    rank += (sc > score || (sc == score && c < lane)) ? 1 : 0;
-  }
-  if (lane < k1 && rank < k2)
-    for (int a = 0; a < 3; ++a) { fs[rank][a] = ps[lane][a]; ft[rank][a] = pt[lane][a]; }
-  __syncthreads();
-  // soft 20 x 20 measure with zero diagonal (:119-131); lane p keeps row p
-  float M[32];
-#pragma unroll
-  for (int q = 0; q < 32; ++q) {
-    float m = 0.f;
-    if (lane < k2 && q < k2 && q != lane) {
-      const float cd = fabsf(dist3(P3{fs[lane][0], fs[lane][1], fs[lane][2]}, P3{fs[q][0], fs[q][1], fs[q][2]}) -
-                             dist3(P3{ft[lane][0], ft[lane][1], ft[lane][2]}, P3{ft[q][0], ft[q][1], ft[q][2]}));
-      m = fmaxf(1.f - cd * cd / (d_thre * d_thre), 0.f);
-    }
-    M[q] = m;
-  }
-  float x = lane < k2 ? 1.f : 0.f;
-  for (int it = 0; it < num_iterations; ++it) {
-    if (lane < 32) xv[lane] = x;
-    __syncthreads();
-    float y = 0.f;
-#pragma unroll
-    for (int q = 0; q < 32; ++q) y += M[q] * xv[q];
-    const float nrm = sqrtf(wave_sum(lane < k2 ? y * y : 0.f));
-    x = lane < k2 ? y / (nrm + 1e-6f) : 0.f;
-    __syncthreads();
-  }
-  const float w = x / (wave_sum(x) + 1e-6f);                      // :132
-  // weighted Kabsch (common.py:18-33): fp32 centroids and covariance like the reference, SVD in fp64
-  const float sw = wave_sum(w) + 1e-6f;
-  float a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
-  if (lane < k2)
-    for (int c = 0; c < 3; ++c) { a[c] = fs[lane][c]; b[c] = ft[lane][c]; }
-  float ca[3], cb[3];
-  for (int c = 0; c < 3; ++c) { ca[c] = wave_sum(a[c] * w) / sw; cb[c] = wave_sum(b[c] * w) / sw; }
-  double H[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) H[3 * i + j] = (double)wave_sum(lane < k2 ? (a[i] - ca[i]) * w * (b[j] - cb[j]) : 0.f);
-  if (lane == 0) {
-    const double cad[3] = {ca[0], ca[1], ca[2]}, cbd[3] = {cb[0], cb[1], cb[2]};
-    kabsch_from_H(H, cad, cbd, trans + 12 * s);
-  }
+  sc_seed_trans(src, tgt, knn, k1, k2, d_thre, num_iterations, trans);
 }
-// the single-pair kernel as it always was: its sums of products are left to the compiler, whose choices differ between
-// this kernel and the body inlined into the batch kernel (see k_scb_fitness), so the two do not share source
+__global__ void __launch_bounds__(256) k_sc_fitness(const float* __restrict__ src, const float* __restrict__ tgt, int n,
+                                                    const float* __restrict__ trans, float thr, float* fitness) {
+  sc_fitness(src, tgt, n, trans + 12 * blockIdx.x, thr, fitness + blockIdx.x);
+}
 __global__ void __launch_bounds__(1024) k_sc_refine_all(const float* __restrict__ src, const float* __restrict__ tgt, int n,
                                                         float thr, int iterations, int* state, float* T) {
-  __shared__ double ws[16][RF_TERMS];
-  __shared__ float Ts[12];
-  __shared__ int done;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  if (t < 12) Ts[t] = T[t];
-  if (t == 0) done = 0;
-  int prev = 0;      // thread 0's
-  __syncthreads();
-  for (int it = 0; it < iterations; ++it) {
-    double acc[RF_TERMS];
-#pragma unroll
-    for (int k = 0; k < RF_TERMS; ++k) acc[k] = 0;
-    for (int j = t; j < n; j += 1024) {
-      const P3 p = ld3(src, j), q = ld3(tgt, j);
-      const float x = Ts[0] * p.x + Ts[1] * p.y + Ts[2] * p.z + Ts[3] - q.x;
-      const float y = Ts[4] * p.x + Ts[5] * p.y + Ts[6] * p.z + Ts[7] - q.y;
-      const float z = Ts[8] * p.x + Ts[9] * p.y + Ts[10] * p.z + Ts[11] - q.z;
-      const float d = sqrtf(x * x + y * y + z * z);
-      if (d < thr) {
-        const float r = d / thr;
-        const double wgt = 1.f / (1.f + r * r);
-        const double a[3] = {p.x, p.y, p.z}, b[3] = {q.x, q.y, q.z};
-        acc[0] += wgt;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { acc[1 + c] += wgt * a[c]; acc[4 + c] += wgt * b[c]; }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int k = 0; k < 3; ++k) acc[7 + 3 * i + k] += wgt * a[i] * b[k];
-        acc[16] += 1.0;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < RF_TERMS; ++k) {
-      double v = acc[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      if (lane == 0) ws[w][k] = v;
-    }
-    __syncthreads();
-    if (t == 0) {
-      double s[RF_TERMS];
-      for (int k = 0; k < RF_TERMS; ++k) {
-        double v = 0;
-        for (int u = 0; u < 16; ++u) v += ws[u][k];
-        s[k] = v;
-      }
-      const int cnt = (int)s[16];
-      if (abs(cnt - prev) < 1) {      // :266-267
-        done = 1;
-      } else {
-        prev = cnt;
-        const double sw = s[0] + 1e-6;      // common.py:22-23
-        double ca[3], cb[3], H[9];
-        for (int c = 0; c < 3; ++c) { ca[c] = s[1 + c] / sw; cb[c] = s[4 + c] / sw; }
-        for (int i = 0; i < 3; ++i)
-          for (int k = 0; k < 3; ++k)
-            H[3 * i + k] = s[7 + 3 * i + k] - ca[i] * s[4 + k] - s[1 + i] * cb[k] + s[0] * ca[i] * cb[k];
-        float Tn[12];
-        kabsch_from_H(H, ca, cb, Tn);
-        for (int k = 0; k < 12; ++k) Ts[k] = Tn[k];
-      }
-    }
-    __syncthreads();
-    if (done) break;
-  }
-  if (t < 12) T[t] = Ts[t];
-  if (t == 0) { state[0] = done; state[1] = prev; }
+  sc_refine_all(src, tgt, n, thr, iterations, state, T);
 }
 __global__ void k_sc_reg_init(float* conf, int* is_max, int* rank, int* done, int n) { sc_reg_init(conf, is_max, rank, done, n); }
 __global__ void __launch_bounds__(SC_TILE) k_sc_seed_rank(const float* __restrict__ conf, const int* __restrict__ is_max, int n,
@@ -1187,7 +993,8 @@ __global__ void k_scb_seed_place(const ScBatch B) {
   if ((int)(blockIdx.x * blockDim.x) >= P.n) return;
   sc_seed_place((const int*)(P.base + B.o_rank), P.n, P.ns, B.seeds + (size_t)blockIdx.z * B.S);
 }
-// the uint16 second-order rows take the place of the entry slab, as in the single call
+// the uint16 second-order rows (n_seeds * n <= 2 n^2 bytes) take the place of the entry slab (8 n^2 bytes), which nothing reads
+// after the last product
 __global__ void __launch_bounds__(256) k_scb_seed_sc2(const ScBatch B, float d_thre) {
   const ScPair P = sc_pair(B);
   if ((int)blockIdx.x * SK_TS >= P.ns) return;
@@ -1205,28 +1012,11 @@ __global__ void __launch_bounds__(64) k_scb_seed_trans(const ScBatch B, int k2, 
   sc_seed_trans(P.src, P.tgt, B.knn + (size_t)blockIdx.z * B.S * B.k1, B.k1, k2, d_thre, num_iterations,
                 B.seed_trans + (size_t)blockIdx.z * B.S * 12);
 }
-// the inlier count of k_sc_fitness, by sc_residual2: a thread's points t, t + 256, ... in pairs, an odd last one on its own
 __global__ void __launch_bounds__(256) k_scb_fitness(const ScBatch B, float thr) {
   const ScPair P = sc_pair(B);
   if ((int)blockIdx.x >= P.ns) return;
-  __shared__ int red[256];
-  __shared__ float Ts[12];
-  const int t = threadIdx.x;
-  if (t < 12) Ts[t] = B.seed_trans[((size_t)blockIdx.z * B.S + blockIdx.x) * 12 + t];
-  __syncthreads();
-  const int trips = t < P.n ? (P.n - 1 - t) / 256 + 1 : 0, packed = trips & ~1;
-  int cnt = 0;
-  for (int k = 0; k < trips; ++k) {
-    const int j = t + 256 * k;
-    cnt += sqrtf(sc_residual2(Ts, ld3(P.src, j), ld3(P.tgt, j), k < packed)) < thr;
-  }
-  red[t] = cnt;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  if (t == 0) B.fitness[(size_t)blockIdx.z * B.S + blockIdx.x] = (float)red[0];
+  const size_t h = (size_t)blockIdx.z * B.S + blockIdx.x;
+  sc_fitness(P.src, P.tgt, P.n, B.seed_trans + h * 12, thr, B.fitness + h);
 }
 __global__ void __launch_bounds__(256) k_scb_best(const ScBatch B) {
   const ScPair P = sc_pair(B);
@@ -1276,51 +1066,29 @@ int64_t gcl_sc2_confidence_scratch_bytes(int32_t n) {
   return (long long)SC_CHUNKS * n * 4 + 256 + (long long)SC_CHUNKS * n * per * (long long)sizeof(ScEntry) + (long long)SC_CHUNKS * n * 4;
 }
 
-static bool sc_folded_normalize() {      // GCL_SC2_FOLDED_NORMALIZE=0: every product followed by its own k_sc_normalize launch
-  static const bool on = [] {
-    const char* e = getenv("GCL_SC2_FOLDED_NORMALIZE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-static int sc_confidence_sparse(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations,
-                                float* partial, float* x, int32_t* done, void* scratch, float tight_thr,
-                                unsigned long long* bits, void* stream) {
+// the build pass once, then product k normalises product k - 1 itself (k_sc_matvec_folded) and one k_sc_normalize closes
+int gcl_sc2_confidence_sparse(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations,
+                              float* partial, float* x, int32_t* done, void* scratch, void* stream) {
   GCL_CHECK_ARG(src && tgt && partial && x && done && scratch, "gcl_sc2_confidence_sparse: null pointer");
   GCL_CHECK_ARG(n > 0 && n <= SC_MAXN && d_thre > 0 && num_iterations >= 0, "gcl_sc2_confidence: 0 < n <= %d", SC_MAXN);
+  if (num_iterations == 0) return GCL_OK;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(n, SC_TILE), SC_CHUNKS);
   int* count = (int*)scratch;
   const size_t entries_off = ((size_t)SC_CHUNKS * n * 4 + 255) & ~(size_t)255;
   ScEntry* entries = (ScEntry*)((char*)scratch + entries_off);
   float* partial2 = (float*)((char*)scratch + entries_off + (size_t)SC_CHUNKS * n * cdiv(n, SC_CHUNKS) * sizeof(ScEntry));
-  const float d2 = d_thre * d_thre;
-  if (num_iterations > 0)
-    hipLaunchKernelGGL(k_sc_sparse_build, dim3((unsigned)cdiv(n, SB_ROWS), SC_CHUNKS), dim3(256), 0, st, src, tgt, n, d2, count,
-                       entries, tight_thr, bits);
-  if (sc_folded_normalize() && num_iterations > 0) {
-    float* buf[2] = {partial, partial2};
-    hipLaunchKernelGGL(k_sc_matvec_folded<true>, grid, dim3(SC_TILE), 0, st, n, x, done, (const float*)nullptr, buf[0],
-                       (const int*)count, (const ScEntry*)entries);
-    for (int it = 1; it < num_iterations; ++it)
-      hipLaunchKernelGGL(k_sc_matvec_folded<false>, grid, dim3(SC_TILE), 0, st, n, x, done, (const float*)buf[(it - 1) & 1],
-                         buf[it & 1], (const int*)count, (const ScEntry*)entries);
-    hipLaunchKernelGGL(k_sc_normalize, dim3(1), dim3(1024), 0, st, (const float*)buf[(num_iterations - 1) & 1], n, x, done);
-  } else {
-    for (int it = 0; it < num_iterations; ++it) {
-      hipLaunchKernelGGL(k_sc_matvec_sparse, grid, dim3(SC_TILE), 0, st, n, (const float*)x, (const int*)done, partial,
-                         (const int*)count, (const ScEntry*)entries);
-      hipLaunchKernelGGL(k_sc_normalize, dim3(1), dim3(1024), 0, st, (const float*)partial, n, x, done);
-    }
-  }
+  hipLaunchKernelGGL(k_sc_sparse_build, dim3((unsigned)cdiv(n, SB_ROWS), SC_CHUNKS), dim3(256), 0, st, src, tgt, n,
+                     d_thre * d_thre, count, entries, 0.f, (unsigned long long*)nullptr);
+  float* buf[2] = {partial, partial2};
+  hipLaunchKernelGGL(k_sc_matvec_folded<true>, grid, dim3(SC_TILE), 0, st, n, x, done, (const float*)nullptr, buf[0],
+                     (const int*)count, (const ScEntry*)entries);
+  for (int it = 1; it < num_iterations; ++it)
+    hipLaunchKernelGGL(k_sc_matvec_folded<false>, grid, dim3(SC_TILE), 0, st, n, x, done, (const float*)buf[(it - 1) & 1],
+                       buf[it & 1], (const int*)count, (const ScEntry*)entries);
+  hipLaunchKernelGGL(k_sc_normalize, dim3(1), dim3(1024), 0, st, (const float*)buf[(num_iterations - 1) & 1], n, x, done);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
-}
-
-int gcl_sc2_confidence_sparse(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations,
-                              float* partial, float* x, int32_t* done, void* scratch, void* stream) {
-  return sc_confidence_sparse(src, tgt, n, d_thre, num_iterations, partial, x, done, scratch, 0.f, nullptr, stream);
 }
 
 int gcl_sc2_local_max(const float* src, const float* conf, int32_t n, float radius, int32_t* is_max, void* stream) {
@@ -1331,42 +1099,21 @@ int gcl_sc2_local_max(const float* src, const float* conf, int32_t n, float radi
   return GCL_OK;
 }
 
-static bool sc_seed_blocked() {      // GCL_SC2_SEED_BLOCKED=0: k_sc_seed_knn (one workgroup per seed) in the one-call form too
-  static const bool on = [] {
-    const char* e = getenv("GCL_SC2_SEED_BLOCKED");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// `vals` (uint16[n_seeds * n], may be null): scratch of the seed-blocked form; without it one workgroup per seed streams the
-// rows of its compatible columns (k_sc_seed_knn, the staged entry point's form -- same integers, same lists)
-static int sc_seed_knn(const float* src, const float* tgt, int32_t n, const int64_t* seeds, int32_t n_seeds,
-                       float d_thre, int32_t k1, uint64_t* bits, bool make_bits, int32_t* knn, void* stream,
-                       unsigned short* vals = nullptr) {
+// k_sc_tight_bits + k_sc_seed_knn (one workgroup per seed streams the rows of its compatible columns): the independent forms
+// of what the registration takes from the build pass and from the seed-blocked kernels -- same integers, same lists
+int gcl_sc2_seed_knn(const float* src, const float* tgt, int32_t n, const int64_t* seeds, int32_t n_seeds,
+                     float d_thre, int32_t k1, uint64_t* bits, int32_t* knn, void* stream) {
   GCL_CHECK_ARG(src && tgt && seeds && bits && knn, "gcl_sc2_seed_knn: null pointer");
   GCL_CHECK_ARG(n > 0 && n <= SC_MAXN && n_seeds > 0 && k1 >= 1 && k1 <= 32 && k1 <= n,
                 "gcl_sc2_seed_knn: need n <= %d, 1 <= k1 <= min(32, n)", SC_MAXN);
   hipStream_t st = (hipStream_t)stream;
   const int words = (n + 63) / 64;
-  if (make_bits)
-    hipLaunchKernelGGL(k_sc_tight_bits, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, src, tgt, n, words, d_thre * 0.5f,
-                       (unsigned long long*)bits);
-  if (vals && sc_seed_blocked()) {
-    hipLaunchKernelGGL(k_sc_seed_sc2, dim3((unsigned)cdiv(n_seeds, SK_TS), SC_CHUNKS), dim3(256), 0, st, src, tgt,
-                       (const unsigned long long*)bits, n, words, (const long long*)seeds, n_seeds, d_thre, vals);
-    hipLaunchKernelGGL(k_sc_seed_topk, dim3(n_seeds), dim3(64), 0, st, (const unsigned short*)vals, n, k1, knn);
-  } else {
-    hipLaunchKernelGGL(k_sc_seed_knn, dim3(n_seeds), dim3(256), 0, st, src, tgt, (const unsigned long long*)bits, n,
-                       words, (const long long*)seeds, d_thre, k1, knn);
-  }
+  hipLaunchKernelGGL(k_sc_tight_bits, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, src, tgt, n, words, d_thre * 0.5f,
+                     (unsigned long long*)bits);
+  hipLaunchKernelGGL(k_sc_seed_knn, dim3(n_seeds), dim3(256), 0, st, src, tgt, (const unsigned long long*)bits, n, words,
+                     (const long long*)seeds, d_thre, k1, knn);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
-}
-
-int gcl_sc2_seed_knn(const float* src, const float* tgt, int32_t n, const int64_t* seeds, int32_t n_seeds,
-                     float d_thre, int32_t k1, uint64_t* bits, int32_t* knn, void* stream) {
-  return sc_seed_knn(src, tgt, n, seeds, n_seeds, d_thre, k1, bits, true, knn, stream);
 }
 
 int gcl_sc2_seed_trans(const float* src, const float* tgt, int32_t n, const int32_t* knn, int32_t n_seeds, int32_t k1,
@@ -1383,103 +1130,18 @@ int gcl_sc2_seed_trans(const float* src, const float* tgt, int32_t n, const int3
   return GCL_OK;
 }
 
-static bool sc_refine_one_launch() {      // GCL_SC2_REFINE_ONE_LAUNCH=0: the two-kernel form, 2 x iterations launches
-  static const int on = [] { const char* e = getenv("GCL_SC2_REFINE_ONE_LAUNCH"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
-
+// `partial` is unused (it was the scratch of a two-kernel form); it stays in the signature
 int gcl_sc2_refine(const float* src, const float* tgt, int32_t n, float thr, int32_t iterations, double* partial,
                    int32_t* state, float* T, void* stream) {
   GCL_CHECK_ARG(src && tgt && partial && state && T && n > 0 && iterations >= 0, "gcl_sc2_refine: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  if (sc_refine_one_launch()) {
-    hipLaunchKernelGGL(k_sc_refine_all, dim3(1), dim3(1024), 0, st, src, tgt, n, thr, iterations, state, T);
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
-  }
-  GCL_CHECK_HIP(hipMemsetAsync(state, 0, 2 * sizeof(int32_t), st));
-  for (int it = 0; it < iterations; ++it) {
-    hipLaunchKernelGGL(k_sc_refine_accum, dim3(RF_BLOCKS), dim3(256), 0, st, src, tgt, n, (const float*)T, thr,
-                       (const int*)state, partial);
-    hipLaunchKernelGGL(k_sc_refine_solve, dim3(1), dim3(1), 0, st, (const double*)partial, state, T);
-  }
-  GCL_CHECK_LAUNCH();
-  return GCL_OK;
-}
-
-
-static size_t sc_up256(size_t b) { return (b + 255) & ~(size_t)255; }
-struct ScRegLayout { size_t partial, done, sparse, is_max, rank, bits, T, rpart, state, total; };
-static ScRegLayout sc_reg_layout(int n) {
-  ScRegLayout L;
-  size_t o = 0;
-  L.partial = o; o += sc_up256((size_t)SC_CHUNKS * n * 4);
-  L.done = o;    o += 256;
-  L.sparse = o;  o += sc_up256((size_t)gcl_sc2_confidence_scratch_bytes(n));
-  L.is_max = o;  o += sc_up256((size_t)n * 4);
-  L.rank = o;    o += sc_up256((size_t)n * 4);
-  L.bits = o;    o += sc_up256((size_t)n * ((n + 63) / 64) * 8);
-  L.T = o;       o += 256;
-  L.rpart = o;   o += sc_up256((size_t)RF_BLOCKS * RF_TERMS * 8);
-  L.state = o;   o += 256;
-  L.total = o;
-  return L;
-}
-
-int64_t gcl_sc2_register_scratch_bytes(int32_t n) {
-  if (n <= 0 || n > SC_MAXN) return 0;
-  return (int64_t)sc_reg_layout(n).total;
-}
-
-int gcl_sc2_register(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations, float nms_radius,
-                     int32_t n_seeds, int32_t k1, int32_t k2, float inlier_thresh, float refine_thr, int32_t refine_iters,
-                     void* scratch, float* conf, int64_t* seeds, int32_t* knn, float* seed_trans, float* fitness,
-                     int32_t* best, float* trans16, float* labels, void* stream) {
-  GCL_CHECK_ARG(src && tgt && scratch && conf && seeds && knn && seed_trans && fitness && best && trans16 && labels,
-                "gcl_sc2_register: null pointer");
-  GCL_CHECK_ARG(n > 0 && n <= SC_MAXN && n_seeds >= 1 && n_seeds <= n, "gcl_sc2_register: need 1 <= n_seeds <= n <= %d",
-                SC_MAXN);
-  hipStream_t st = (hipStream_t)stream;
-  const ScRegLayout L = sc_reg_layout(n);
-  char* base = (char*)scratch;
-  float* partial = (float*)(base + L.partial);
-  int* done = (int*)(base + L.done);
-  int* is_max = (int*)(base + L.is_max);
-  float* T = (float*)(base + L.T);
-  int* rank = (int*)(base + L.rank);
-  hipLaunchKernelGGL(k_sc_reg_init, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, conf, is_max, rank, done, n);
-  // the tight compatibility bits come out of the confidence's build pass (one evaluation of the n^2 length differences, not two)
-  const bool bits_from_build = num_iterations > 0;
-  int rc = sc_confidence_sparse(src, tgt, n, d_thre, num_iterations, partial, conf, done, base + L.sparse, d_thre * 0.5f,
-                                bits_from_build ? (unsigned long long*)(base + L.bits) : nullptr, stream);
-  if (rc != GCL_OK) return rc;
-  rc = gcl_sc2_local_max(src, conf, n, nms_radius, is_max, stream);
-  if (rc != GCL_OK) return rc;
-  hipLaunchKernelGGL(k_sc_seed_rank, dim3((unsigned)cdiv(n, SC_TILE), SC_CHUNKS), dim3(SC_TILE), 0, st, (const float*)conf,
-                     (const int*)is_max, n, rank);
-  hipLaunchKernelGGL(k_sc_seed_place, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, (const int*)rank, n, n_seeds,
-                     (long long*)seeds);
-  // the second-order values of the seed-blocked form (uint16[n_seeds * n] <= 2 n^2 bytes) take the place of the confidence's
-  // entry slab (8 n^2 bytes, behind its counts), which nothing reads after the last product
-  unsigned short* vals = (unsigned short*)(base + L.sparse + (((size_t)SC_CHUNKS * n * 4 + 255) & ~(size_t)255));
-  rc = sc_seed_knn(src, tgt, n, seeds, n_seeds, d_thre, k1, (uint64_t*)(base + L.bits), !bits_from_build, knn, stream, vals);
-  if (rc != GCL_OK) return rc;
-  rc = gcl_sc2_seed_trans(src, tgt, n, knn, n_seeds, k1, k2, d_thre, num_iterations, inlier_thresh, seed_trans, fitness,
-                          stream);
-  if (rc != GCL_OK) return rc;
-  hipLaunchKernelGGL(k_sc_best, dim3(1), dim3(256), 0, st, (const float*)fitness, (const float*)seed_trans, n_seeds, best, T);
-  rc = gcl_sc2_refine(src, tgt, n, refine_thr, refine_iters, (double*)(base + L.rpart), (int32_t*)(base + L.state), T, stream);
-  if (rc != GCL_OK) return rc;
-  hipLaunchKernelGGL(k_sc_finish, dim3((unsigned)cdiv(std::max(n, 16), 256)), dim3(256), 0, st, src, tgt, n, (const float*)T,
-                     inlier_thresh, trans16, labels);
+  hipLaunchKernelGGL(k_sc_refine_all, dim3(1), dim3(1024), 0, (hipStream_t)stream, src, tgt, n, thr, iterations, state, T);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
 // ---- a batch of pairs in the launches of one registration ----------------------------------------------------------------------
-// A pair's slot is the single-pair layout at n_cap with every slab on a 256-byte boundary (the second partial buffer, which
-// the single layout places right behind the entries, gets a slab of its own); it is never smaller than
-// gcl_sc2_register_scratch_bytes(n_cap), so that the per-pair loop below can hand a slot to gcl_sc2_register.
+// A pair's slot: every slab on a 256-byte boundary, sized for n_cap correspondences (gcl_sc2_register uses one slot at n).
+static size_t sc_up256(size_t b) { return (b + 255) & ~(size_t)255; }
 struct ScBatchLayout { size_t partial, partial2, done, count, entries, is_max, rank, bits, T, state, total; };
 static ScBatchLayout sc_batch_layout(int n_cap) {
   ScBatchLayout L;
@@ -1494,7 +1156,7 @@ static ScBatchLayout sc_batch_layout(int n_cap) {
   L.bits = o;     o += sc_up256((size_t)n_cap * ((n_cap + 63) / 64) * 8);
   L.T = o;        o += 256;
   L.state = o;    o += 256;
-  L.total = std::max(o, sc_up256(sc_reg_layout(n_cap).total));
+  L.total = o;
   return L;
 }
 
@@ -1528,20 +1190,6 @@ int gcl_sc2_register_batch(const float* src, const float* tgt, int32_t batch, in
   }
   hipStream_t st = (hipStream_t)stream;
   const ScBatchLayout L = sc_batch_layout(n_cap);
-  if (!sc_folded_normalize() || !sc_seed_blocked() || !sc_refine_one_launch() || num_iterations == 0) {
-    // not the default forms: the single call per pair, on the pair's slot and output rows
-    for (int b = 0; b < batch; ++b) {
-      float* lab = labels + (size_t)b * n_cap;
-      const int rc = gcl_sc2_register(src + (size_t)b * n_cap * 3, tgt + (size_t)b * n_cap * 3, counts[b], d_thre, num_iterations,
-                                      nms_radius, n_seeds[b], k1, k2, inlier_thresh, refine_thr, refine_iters,
-                                      (char*)scratch + (size_t)b * L.total, conf + (size_t)b * n_cap, seeds + (size_t)b * S,
-                                      knn + (size_t)b * S * k1, seed_trans + (size_t)b * S * 12, fitness + (size_t)b * S, best + b,
-                                      trans16 + (size_t)b * 16, lab, stream);
-      if (rc != GCL_OK) return rc;
-      if (counts[b] < n_cap) GCL_CHECK_HIP(hipMemsetAsync(lab + counts[b], 0, (size_t)(n_cap - counts[b]) * sizeof(float), st));
-    }
-    return GCL_OK;
-  }
   const float d2 = d_thre * d_thre;
   for (int g0 = 0; g0 < batch; g0 += SC_GROUP) {
     const int G = std::min(SC_GROUP, batch - g0);
@@ -1569,14 +1217,19 @@ int gcl_sc2_register_batch(const float* src, const float* tgt, int32_t batch, in
     }
     const unsigned z = (unsigned)G, tiles = (unsigned)cdiv(n_cap, SC_TILE);
     const dim3 rows(tiles, SC_CHUNKS, z);
+    // the stage order of gcl_sc2_register, below: a change to one sequence belongs in the other too
     hipLaunchKernelGGL(k_scb_reg_init, dim3((unsigned)cdiv(n_cap, 256), 1, z), dim3(256), 0, st, B);
+    // the build pass always runs: the tight compatibility bits come out of it (one evaluation of the n^2 length differences,
+    // not two); without iterations there are no products and no normalisation, and conf stays at the ones of k_scb_reg_init
     hipLaunchKernelGGL(k_scb_sparse_build, dim3((unsigned)cdiv(n_cap, SB_ROWS), SC_CHUNKS, z), dim3(256), 0, st, B, d2,
                        d_thre * 0.5f);
-    const size_t buf[2] = {L.partial, L.partial2};
-    hipLaunchKernelGGL(k_scb_matvec_folded<true>, rows, dim3(SC_TILE), 0, st, B, buf[1], buf[0]);
-    for (int it = 1; it < num_iterations; ++it)
-      hipLaunchKernelGGL(k_scb_matvec_folded<false>, rows, dim3(SC_TILE), 0, st, B, buf[(it - 1) & 1], buf[it & 1]);
-    hipLaunchKernelGGL(k_scb_normalize, dim3(1, 1, z), dim3(1024), 0, st, B, buf[(num_iterations - 1) & 1]);
+    if (num_iterations > 0) {
+      const size_t buf[2] = {L.partial, L.partial2};
+      hipLaunchKernelGGL(k_scb_matvec_folded<true>, rows, dim3(SC_TILE), 0, st, B, buf[1], buf[0]);
+      for (int it = 1; it < num_iterations; ++it)
+        hipLaunchKernelGGL(k_scb_matvec_folded<false>, rows, dim3(SC_TILE), 0, st, B, buf[(it - 1) & 1], buf[it & 1]);
+      hipLaunchKernelGGL(k_scb_normalize, dim3(1, 1, z), dim3(1024), 0, st, B, buf[(num_iterations - 1) & 1]);
+    }
     hipLaunchKernelGGL(k_scb_local_max, dim3(tiles, tiles / 2 + 1, z), dim3(SC_TILE), 0, st, B, nms_radius);
     hipLaunchKernelGGL(k_scb_seed_rank, rows, dim3(SC_TILE), 0, st, B);
     hipLaunchKernelGGL(k_scb_seed_place, dim3((unsigned)cdiv(n_cap, 256), 1, z), dim3(256), 0, st, B);
@@ -1588,6 +1241,69 @@ int gcl_sc2_register_batch(const float* src, const float* tgt, int32_t batch, in
     hipLaunchKernelGGL(k_scb_refine_all, dim3(1, 1, z), dim3(1024), 0, st, B, refine_thr, refine_iters);
     hipLaunchKernelGGL(k_scb_finish, dim3((unsigned)cdiv(std::max(n_cap, 16), 256), 1, z), dim3(256), 0, st, B, inlier_thresh);
   }
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+// ---- one pair: the launches of the batch entry with plain arguments, on one slot of the batch layout ------------------------------
+int64_t gcl_sc2_register_scratch_bytes(int32_t n) { return gcl_sc2_register_batch_scratch_bytes(1, n); }
+
+int gcl_sc2_register(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations, float nms_radius,
+                     int32_t n_seeds, int32_t k1, int32_t k2, float inlier_thresh, float refine_thr, int32_t refine_iters,
+                     void* scratch, float* conf, int64_t* seeds, int32_t* knn, float* seed_trans, float* fitness,
+                     int32_t* best, float* trans16, float* labels, void* stream) {
+  GCL_CHECK_ARG(src && tgt && scratch && conf && seeds && knn && seed_trans && fitness && best && trans16 && labels,
+                "gcl_sc2_register: null pointer");
+  GCL_CHECK_ARG(n > 0 && n <= SC_MAXN && n_seeds >= 1 && n_seeds <= n, "gcl_sc2_register: need 1 <= n_seeds <= n <= %d",
+                SC_MAXN);
+  GCL_CHECK_ARG(d_thre > 0 && num_iterations >= 0 && refine_iters >= 0,
+                "gcl_sc2_register: need d_thre > 0, num_iterations >= 0, refine_iters >= 0");
+  GCL_CHECK_ARG(k1 >= 1 && k1 <= 32 && k1 <= n && k2 >= 1 && k2 <= k1,
+                "gcl_sc2_register: need 1 <= k2 <= k1 <= min(32, n), got k1 = %d, k2 = %d", k1, k2);
+  hipStream_t st = (hipStream_t)stream;
+  const ScBatchLayout L = sc_batch_layout(n);
+  char* base = (char*)scratch;
+  int* done = (int*)(base + L.done);
+  int* count = (int*)(base + L.count);
+  ScEntry* entries = (ScEntry*)(base + L.entries);
+  unsigned short* vals = (unsigned short*)(base + L.entries);      // the second-order rows take the entry slab's place
+  int* is_max = (int*)(base + L.is_max);
+  int* rank = (int*)(base + L.rank);
+  unsigned long long* bits = (unsigned long long*)(base + L.bits);
+  float* T = (float*)(base + L.T);
+  const int words = (n + 63) / 64;
+  const unsigned tiles = (unsigned)cdiv(n, SC_TILE);
+  const dim3 rows(tiles, SC_CHUNKS);
+  // the stage order of gcl_sc2_register_batch, above: a change to one sequence belongs in the other too
+  hipLaunchKernelGGL(k_sc_reg_init, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, conf, is_max, rank, done, n);
+  hipLaunchKernelGGL(k_sc_sparse_build, dim3((unsigned)cdiv(n, SB_ROWS), SC_CHUNKS), dim3(256), 0, st, src, tgt, n,
+                     d_thre * d_thre, count, entries, d_thre * 0.5f, bits);      // always: it makes the tight bits
+  if (num_iterations > 0) {
+    float* buf[2] = {(float*)(base + L.partial), (float*)(base + L.partial2)};
+    hipLaunchKernelGGL(k_sc_matvec_folded<true>, rows, dim3(SC_TILE), 0, st, n, conf, done, (const float*)nullptr, buf[0],
+                       (const int*)count, (const ScEntry*)entries);
+    for (int it = 1; it < num_iterations; ++it)
+      hipLaunchKernelGGL(k_sc_matvec_folded<false>, rows, dim3(SC_TILE), 0, st, n, conf, done, (const float*)buf[(it - 1) & 1],
+                         buf[it & 1], (const int*)count, (const ScEntry*)entries);
+    hipLaunchKernelGGL(k_sc_normalize, dim3(1), dim3(1024), 0, st, (const float*)buf[(num_iterations - 1) & 1], n, conf, done);
+  }
+  hipLaunchKernelGGL(k_sc_local_max, dim3(tiles, tiles / 2 + 1), dim3(SC_TILE), 0, st, src, (const float*)conf, n, nms_radius,
+                     is_max);
+  hipLaunchKernelGGL(k_sc_seed_rank, rows, dim3(SC_TILE), 0, st, (const float*)conf, (const int*)is_max, n, rank);
+  hipLaunchKernelGGL(k_sc_seed_place, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, (const int*)rank, n, n_seeds,
+                     (long long*)seeds);
+  hipLaunchKernelGGL(k_sc_seed_sc2, dim3((unsigned)cdiv(n_seeds, SK_TS), SC_CHUNKS), dim3(256), 0, st, src, tgt,
+                     (const unsigned long long*)bits, n, words, (const long long*)seeds, n_seeds, d_thre, vals);
+  hipLaunchKernelGGL(k_sc_seed_topk, dim3(n_seeds), dim3(64), 0, st, (const unsigned short*)vals, n, k1, knn);
+  hipLaunchKernelGGL(k_sc_seed_trans, dim3(n_seeds), dim3(64), 0, st, src, tgt, (const int*)knn, k1, k2, d_thre, num_iterations,
+                     seed_trans);
+  hipLaunchKernelGGL(k_sc_fitness, dim3(n_seeds), dim3(256), 0, st, src, tgt, n, (const float*)seed_trans, inlier_thresh,
+                     fitness);
+  hipLaunchKernelGGL(k_sc_best, dim3(1), dim3(256), 0, st, (const float*)fitness, (const float*)seed_trans, n_seeds, best, T);
+  hipLaunchKernelGGL(k_sc_refine_all, dim3(1), dim3(1024), 0, st, src, tgt, n, refine_thr, refine_iters,
+                     (int*)(base + L.state), T);
+  hipLaunchKernelGGL(k_sc_finish, dim3((unsigned)cdiv(std::max(n, 16), 256)), dim3(256), 0, st, src, tgt, n, (const float*)T,
+                     inlier_thresh, trans16, labels);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

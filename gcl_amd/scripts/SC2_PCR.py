@@ -197,8 +197,9 @@ class _BatchStages:
 class BatchMatcher(Matcher):
     """``Matcher`` for a batch of pairs: ``SC2_PCR`` / ``estimator`` take [B, n, ...] tensors and make ONE
     ``gcl_sc2_register_batch`` call -- the launches of one registration with the pair as the grids' z dimension -- whose
-    results equal ``Matcher``'s on every pair alone bit for bit.  SCRATCH: ~ 8 n^2 bytes per pair (528 MB at n = 8000); a batch
-    that would need more than ``max_batch_bytes`` runs as consecutive sub-batches on one scratch block."""
+    results equal ``Matcher``'s on every pair alone bit for bit (the two entries launch the same kernel bodies).
+    SCRATCH: ~ 8 n^2 bytes per pair (528 MB at n = 8000); a batch that would need more than ``max_batch_bytes`` runs as
+    consecutive sub-batches on one scratch block."""
 
     accepts_batch = True             # scripts/eval_batch.eval_pairs(..., batch_registration=True) asks for these two
     draw_takes_sizes = True

@@ -622,7 +622,8 @@ int gcl_loss_seed(const float* g_total, float w_pos, float w_fin, float w_neg, i
  *                       host: best = lowest index of the maximum fitness.
  *   gcl_sc2_refine      post refinement in place on T float[12] (:238-279): up to `iterations` weighted Kabsch steps
  *                       over the inliers under thr, stopping when the inlier count repeats.
- *                       partial double[gcl_sc2_refine_partial_len()], state int32[2].
+ *                       One launch.  state int32[2]; partial double[gcl_sc2_refine_partial_len()] is UNUSED (the scratch
+ *                       of an earlier two-kernel form: kept in the signature, must not be null).
  * ---------------------------------------------------------------------------------------------- */
 int32_t gcl_sc2_chunks(void);
 int32_t gcl_sc2_refine_partial_len(void);
@@ -634,7 +635,7 @@ int gcl_sc2_confidence(const float* src, const float* tgt, int32_t n, float d_th
  * ones are touched): the same non-zero terms in the same order, i.e. bitwise the result x of gcl_sc2_confidence, without
  * re-deriving 64 M entries (two square roots each) in every one of the 20 products.  `partial` is working space here (the
  * products alternate between it and a second buffer in scratch: product k normalises product k - 1 itself, 21 launches
- * instead of 40; GCL_SC2_FOLDED_NORMALIZE=0 restores one normalisation launch per product) */
+ * instead of 40) */
 int64_t gcl_sc2_confidence_scratch_bytes(int32_t n);
 int gcl_sc2_confidence_sparse(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations,
                               float* partial, float* x, int32_t* done, void* scratch, void* stream);
@@ -650,7 +651,10 @@ int gcl_sc2_confidence_sparse(const float* src, const float* tgt, int32_t n, flo
  * are ever touched, i.e. only those cost bandwidth or physical pages' worth of traffic) + the 8 MB tight-compatibility bit
  * matrix; the seed stage's uint16 second-order rows (2 n_seeds n bytes) reuse the slab once the last product has run.  That
  * is two of the four dense [n, n] float matrices the reference allocates (scripts/SC2_PCR/SC2_PCR.py:327-361); with several
- * registrations in flight (GCL_EVAL_STREAMS > 1) every one needs its own block.  Same results as the staged calls. */
+ * registrations in flight (GCL_EVAL_STREAMS > 1) every one needs its own block.  Same results as the staged calls.
+ * The launches are those of gcl_sc2_register_batch for one pair, with plain arguments, on one slot of its scratch layout:
+ * gcl_sc2_register_scratch_bytes(n) = gcl_sc2_register_batch_scratch_bytes(1, n).  num_iterations = 0: no products, conf stays
+ * at ones (the build pass still runs: it makes the tight compatibility bits). */
 int64_t gcl_sc2_register_scratch_bytes(int32_t n);
 int gcl_sc2_register(const float* src, const float* tgt, int32_t n, float d_thre, int32_t num_iterations, float nms_radius,
                      int32_t n_seeds, int32_t k1, int32_t k2, float inlier_thresh, float refine_thr, int32_t refine_iters,
@@ -659,20 +663,21 @@ int gcl_sc2_register(const float* src, const float* tgt, int32_t n, float d_thre
 /* A BATCH of pairs in the launches of ONE registration (the reference asserts bs == 1; its Matcher is written for
  * [bs, num_corr, 3]).  src / tgt: [batch, n_cap, 3] on the device; pair b uses rows 0 .. counts[b] - 1 of its block and
  * wants n_seeds[b] seeds.  counts / n_seeds are HOST arrays [batch]: they travel to the kernels as a by-value argument (no
- * copy on the stream, no read-back, no synchronisation).  Every launch of gcl_sc2_register's default forms is made once, with
+ * copy on the stream, no read-back, no synchronisation).  Every launch of a registration is made once, with
  * the pair as the grid's z dimension and grids sized for n_cap and S = max(n_seeds); a workgroup reads its own pair's n,
  * derives that pair's chunk length, word count and tile counts, and returns at once when it lies beyond them.  The early
  * exits (the power iteration's `done`, the refinement's convergence) are per pair.  More than 32 pairs: one such launch
  * sequence per 32.
  * CONTRACT: for every pair, every output is bit for bit what gcl_sc2_register writes for that pair alone, whatever the
- * other pairs of the batch are and in whatever order.  With GCL_SC2_FOLDED_NORMALIZE=0, GCL_SC2_SEED_BLOCKED=0,
- * GCL_SC2_REFINE_ONE_LAUNCH=0 or num_iterations = 0 the call IS a loop of gcl_sc2_register over the pairs.
+ * other pairs of the batch are and in whatever order: the two entries launch the same stage bodies, and a body's sums of
+ * products are written out operation by operation, so its bits do not depend on the kernel it is compiled into.
+ * num_iterations = 0 as in the single call.
  * Outputs: trans16 float[batch, 16], labels float[batch, n_cap] (0 from a pair's count on), conf float[batch, n_cap],
  * seeds int64[batch, S], knn int32[batch, S, k1], seed_trans float[batch, S, 12], fitness float[batch, S], best int32[batch];
  * entries beyond a pair's own extent are unspecified, except labels.
  * Needs 1 <= n_seeds[b] <= counts[b] <= n_cap <= 8192, batch >= 1, k1 <= min(counts), no null pointer: checked before any
  * GPU call (GCL_ERR_ARG, gcl_last_error).
- * scratch: gcl_sc2_register_batch_scratch_bytes(batch, n_cap) bytes = batch slots of the single-pair layout at n_cap, every
+ * scratch: gcl_sc2_register_batch_scratch_bytes(batch, n_cap) bytes = batch slots sized for n_cap, every
  * slot and every slab in it on a 256-byte boundary (0 for batch <= 0, n_cap <= 0 or n_cap > 8192); may hold anything, the call
  * initialises what it reads.  SCRATCH FOOTPRINT: ~ 8 n_cap^2 bytes of address space PER PAIR -- 528 MB at n = 8000, 4.2 GB for
  * 8 such pairs -- of which, as in the single call, only the non-zero entries are ever touched. */

@@ -1723,15 +1723,12 @@ def test_sc2pcr_confidence_sparse_equals_dense_bitwise(n, inlier, noise):
             res.append((conf, partial, done))
         assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][2], res[1][2])
         assert bool(torch.isfinite(res[0][0]).all())
-        if os.environ.get("GCL_SC2_FOLDED_NORMALIZE") == "0":      # every product followed by its own normalisation launch:
-            assert torch.equal(res[0][1], res[1][1])              # then the last product's partial sums are the same buffer too
 
 
-def test_sc2pcr_one_launch_refinement_and_sparse_confidence_vs_round_1_forms(tmp_path):
-    """The round-5 forms of two SC2-PCR stages -- the refinement as ONE persistent launch (k_sc_refine_all) and the
-    confidence's products over kept non-zero entries -- against the round-1 forms (GCL_SC2_REFINE_ONE_LAUNCH=0,
-    GCL_SC2_SPARSE=0, selected in a fresh process: the switches are read once): the transformation of every golden problem
-    agrees to 2e-6 (the confidence stage is bitwise, test above; the refinement's fp64 sums take another fixed order)."""
+def test_sc2pcr_sparse_confidence_vs_the_dense_form(tmp_path):
+    """The confidence's products over kept non-zero entries (inside the one-call registration) against the dense round-1
+    form (GCL_SC2_SPARSE=0: the staged calls with gcl_sc2_confidence, selected in a fresh process: the switch is read once):
+    the transformation of every golden problem agrees to 2e-6 (the confidence stage is bitwise, test above)."""
     import subprocess
     script = (
         "import sys, glob, os, numpy as np, torch\n"
@@ -1747,14 +1744,14 @@ def test_sc2pcr_one_launch_refinement_and_sparse_confidence_vs_round_1_forms(tmp
         "    out[os.path.basename(path)] = T[0].cpu().numpy()\n"
         "np.savez(sys.argv[1], **out)\n") % (ROOT, G, SC2_KEYS, DEV, DEV, DEV)
     res = {}
-    for tag, env in (("new", {}), ("old", {"GCL_SC2_REFINE_ONE_LAUNCH": "0", "GCL_SC2_SPARSE": "0"})):
+    for tag, env in (("new", {}), ("old", {"GCL_SC2_SPARSE": "0"})):
         f = str(tmp_path / f"{tag}.npz")
         r = subprocess.run([sys.executable, "-c", script, f], env=dict(os.environ, **env), capture_output=True, text=True,
                            timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         res[tag] = np.load(f)
     assert len(res["new"].files) >= 3
-    for k in res["new"].files:      # (the one-launch refinement sums its fp64 terms in another fixed order: last-bit differences)
+    for k in res["new"].files:
         assert np.abs(res["new"][k] - res["old"][k]).max() < 2e-6, k
 
 

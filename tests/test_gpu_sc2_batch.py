@@ -151,28 +151,43 @@ def test_more_pairs_than_one_launch_sequence_takes():
         _assert_same(g, _single(("33 pairs", b), *p), f"pair {b} of 33")
 
 
-_SWITCH_CHECK = """
-import sys
-sys.path.insert(0, {tests!r})
-import test_gpu_sc2_batch as T
-counts = (257, 64, 300)
-pairs = [T._planted(700 + n, n, 0.5) for n in counts]
-got = T._batch(pairs, n_cap=320)
-for n, p, g in zip(counts, pairs, got):
-    T._assert_same(g, T._single(n, *p), "n = %d" % n)
-print("SWITCH_OK")
-"""
-
-
-def test_a_non_default_form_loops_over_the_single_call():
-    """GCL_SC2_SEED_BLOCKED=0 is read once per process, hence a child: the batch entry then calls gcl_sc2_register per pair
-    (on the pair's scratch slot and output rows, label tails cleared) and must return that form's single-call results."""
-    import subprocess
-    env = dict(os.environ, GCL_SC2_SEED_BLOCKED="0")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", _SWITCH_CHECK.format(tests=os.path.join(root, "tests"))], env=env, cwd=root,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "SWITCH_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+def test_no_iterations_staged_calls_single_call_and_batch_agree(monkeypatch):
+    """num_iterations = 0: the confidence stays at ones and the per-seed power iteration does not run.  Counts (129, 65)
+    padded to n_cap = 160: each pair alone through ``Matcher`` equals the five staged calls (their tight bits come from
+    k_sc_tight_bits, the one call's from the build pass, which runs without any product) in every stage and in the
+    transformation, bit for bit; and the batch equals the single calls bit for bit."""
+    import gcl_amd.scripts.SC2_PCR as S
+    cfg = dict(CFG, num_iterations=0)
+    counts = (129, 65)
+    pairs = [_planted(900 + n, n, 0.5) for n in counts]
+    want = []
+    with torch.cuda.device(DEV):
+        for src, tgt in pairs:
+            s, t = torch.from_numpy(src).to(DEV)[None], torch.from_numpy(tgt).to(DEV)[None]
+            res = []
+            for one_call in (False, True):
+                monkeypatch.setattr(S, "ONE_CALL", one_call)
+                m = S.Matcher(num_node="all", use_mutual=False, **cfg)
+                T = m.SC2_PCR(s, t)
+                r = {k: m.last[k].clone() for k in STAGES}
+                r.update(out=T.clone(), labels=m._labels)
+                res.append(r)
+            staged, one = res
+            assert staged["labels"] is None and one["labels"] is not None
+            assert torch.equal(staged["out"], one["out"])
+            for k in STAGES:
+                assert torch.equal(staged[k].to(one[k].dtype), one[k]), k
+            assert bool((one["conf"] == 1).all())
+            want.append({k: _bytes(v) for k, v in one.items()})
+        monkeypatch.setattr(S, "ONE_CALL", True)
+        m = S.BatchMatcher(num_node="all", use_mutual=False, **cfg)
+        src, tgt, cnt = _padded(pairs, 160)
+        T = m.SC2_PCR(src, tgt, counts=cnt)
+        for b, n in enumerate(counts):
+            got = {k: _bytes(m.last[b][k]) for k in ("out", "labels") + STAGES}
+            _assert_same(got, want[b], f"n = {n}, no iterations")
+            assert _bytes(T[b]) == got["out"] and bool((m._labels[b, n:] == 0).all())
+    assert want[0]["out"] != want[1]["out"]
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------
