@@ -219,6 +219,30 @@ def ctypes_offset(t, elem):
     return ctypes.c_void_p(t.data_ptr() + elem * t.element_size())
 
 
+def fwd_instance_name(lib, n_out, K, cin, cout, prec, planes=False, fused=False, sorted_table=True, scratch=False, flags=0):
+    """Kernel instance gcl_conv_fwd(_fused(_ld)) launches for a shape, asked of the library (gcl_conv_fwd_launch_shape:
+    the function its dispatcher calls); the profile label of the launch."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(lib.gcl_conv_fwd_launch_shape(n_out, K, cin, cout, prec, int(planes), int(fused), int(sorted_table),
+                                             int(scratch), flags, out), "gcl_conv_fwd_launch_shape")
+    path, nb, pl = out[0], out[1], out[2]
+    pre, epi = ("true" if out[3] & 1 else "false"), ("true" if out[3] & 2 else "false")
+    return ("k_conv_generic", f"k_conv_fwd<{nb}>", f"k_conv_fwd_split<{nb},{pl},{pre},{epi}>",
+            f"k_conv_fwd_dma<{nb},{pre},{epi}>", f"k_conv_fwd_tall<{epi}>", f"k_conv_groups_sum<{epi},4>")[path]      # GCL_FWD_PATH_*
+
+
+def dw_instance_name(lib, K, ca, cb, prec, planes, sorted_side, n_sorted, n_pairs_padded):
+    """Kernel instance gcl_conv_bwd_weight(_rg) launches for a shape (gcl_conv_bwd_weight_launch_shape); the profile label
+    of the launch.  The trailing `false` of a template argument list is left out, as profiles/pmc_summary.json spells it."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(lib.gcl_conv_bwd_weight_launch_shape(K, ca, cb, prec, int(planes), sorted_side, n_sorted, n_pairs_padded, out),
+               "gcl_conv_bwd_weight_launch_shape")
+    path, tile = out[0], f"{out[1]},{out[2]}"
+    return ("k_bwd_weight_reduce", "k_conv_bwd_weight_generic", f"k_conv_bwd_weight<{tile}>",
+            f"k_conv_bwd_weight_split<{tile},{prec},false>", f"k_conv_bwd_weight_split<{tile},4,true>",
+            f"k_conv_bwd_weight_split<{tile},{prec},false,true>", "k_conv_bwd_weight_wg128")[path]      # GCL_DW_PATH_*
+
+
 def _conv_launch(lib, x, Wk, mode, table, n_out, cin, cout, bias, pairs=0, want_stats=False, x_amax=None,
                  w_amax=None, wp=None, x_planes=None, generic=False, add=None):
     """One output-stationary convolution launch.  ``Wk`` [K, *, *] is packed for ``mode`` (0 forward, 1 transposed,
@@ -243,14 +267,8 @@ def _conv_launch(lib, x, Wk, mode, table, n_out, cin, cout, bias, pairs=0, want_
         stats = torch.empty((4, cout, (n_out + 127) // 128), dtype=torch.float32, device=x.device)     # channel-major partials: sum, squares, min, max
     name = None
     if PROFILE is not None:
-        nb = lib.gcl_conv_fwd_nb(n_out, cout, prec)
-        pre = "true" if x_planes is not None else "false"
-        name = "k_conv_generic" if generic else \
-            (f"k_conv_fwd<{nb}>" if prec == 0 else
-             f"k_conv_fwd_split<{nb},{prec},{pre},{'true' if add is not None else 'false'}>")
-        if prec == 4 and not generic and os.environ.get("GCL_FWD_DMA", "1") != "0" and \
-                (x_planes is not None or os.environ.get("GCL_FWD_DMA_ROWS", "1") != "0"):
-            name = f"k_conv_fwd_dma<{nb},{pre},{'true' if add is not None else 'false'}>"
+        name = fwd_instance_name(lib, n_out, K, cin, cout, prec, x_planes is not None, add is not None, tile_mask is not None,
+                                 flags=getattr(tbl, "_gcl_flags", 0))
     with _Timed(name, pairs, cin, cout, x.shape[0], n_out, K):
         xin, is_planes = (x_planes, 1) if x_planes is not None else (x, 0)
         if add is not None:
@@ -390,13 +408,9 @@ class _SparseConvFn(torch.autograd.Function):
                 n_sorted = (x.shape[0] if sorted_side == 1 else dy.shape[0]) if sorted_side else 0
                 scratch = torch.empty(lib.gcl_conv_bwd_weight_scratch_len(K, cin, cout, seg[-1], n_sorted),
                                       dtype=torch.float32, device=x.device)
-                tile = f"{64 if cin % 64 == 0 else 32},{64 if cout % 64 == 0 else 32}"
                 use_pl = fp16x3 and _want_planes(cin) and _want_planes(cout)
-                name = "k_conv_bwd_weight_generic" if (cin % 32 or cout % 32) else \
-                    (f"k_conv_bwd_weight<{tile}>" if prec == 0 else
-                     f"k_conv_bwd_weight_split<{tile},{prec},{'true' if use_pl else 'false'}>")
-                if use_pl and cin % 128 == 0 and cout % 128 == 0 and os.environ.get("GCL_DW_WG128", "1") != "0":
-                    name = "k_conv_bwd_weight_wg128"
+                name = dw_instance_name(lib, K, cin, cout, prec, use_pl, sorted_side, n_sorted, int(seg[-1])) \
+                    if PROFILE is not None else None
                 if prec == 4 and not fp16x3 and not (cin % 32 or cout % 32):     # K > 27 with MFMA-shaped channels
                     x_amax, dy_amax = tensor_amax(lib, x), tensor_amax(lib, dy)
                 with _Timed(name, ctx.pairs, cin, cout, x.shape[0], dy.shape[0], K):

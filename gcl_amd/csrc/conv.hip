@@ -2232,35 +2232,33 @@ static int dw_range_rows(long long n_rows, int K) {
   return rr;
 }
 static bool dw_rg_shape(int K, int ca, int cb, int prec, int planes, int sorted_side, long long n_rows) {
-  static const int on = [] { const char* e = getenv("GCL_DW_RANGES"); return e ? atoi(e) : 1; }();
-  return on && sorted_side != 0 && K > 1 && K <= 27 && !planes && prec != 0 && (ca == 32 || ca == 64) &&
+  return sorted_side != 0 && K > 1 && K <= 27 && !planes && prec != 0 && (ca == 32 || ca == 64) &&
          (cb == 32 || cb == 64) && n_rows >= 32768;
 }
 
 // columns per wave (32 NB) of a forward launch: 128 when Cout allows, but 64 when the 128-wide launch would have
 // 513..1024 workgroups -- a second, poorly filled round on 256 CUs x 2 resident workgroups -- where twice as many
 // half-width workgroups (3 resident per CU) finish earlier (measured -7 % on the 128->128 / 256->256 layers of the
-// KITTI batch).  GCL_NB_POLICY=0 disables the rule.
+// KITTI batch).
+constexpr long long FWD_NB_SMALL_WGS = 256;      // a workgroup per CU
 static int conv_fwd_nb(long long n_out, int cout, int prec) {
   int nb = (cout % 128 == 0) ? 4 : ((cout % 64 == 0) ? 2 : 1);
-  static const int pol = [] { const char* s = getenv("GCL_NB_POLICY"); return s ? atoi(s) : 1; }();
-  static const int force = [] { const char* s = getenv("GCL_FORCE_NB"); return s ? atoi(s) : 0; }();   // diagnostic
-  if (force == 1 || (force == 2 && nb > 2)) return force;
   if (prec == 3 && nb == 4) nb = 2;   // three planes: the double-buffered weight block of NB = 4 would not fit twice
   long long wgs = cdiv(n_out, 128) * (cout / (32 * nb));
-  if (prec != 0 && pol == 1 && nb == 4 && wgs > 512 && wgs <= 1024) nb = 2;
+  if (prec != 0 && nb == 4 && wgs > 512 && wgs <= 1024) nb = 2;
   // small launches: narrower column blocks until the launch has a workgroup per CU (the weight layout does not depend on NB and
   // a column's sum is the same chain of products whatever block holds it: bitwise the same result)
-  static const long long small = [] { const char* s = getenv("GCL_NB_SMALL_WGS"); return s ? atoll(s) : 256ll; }();
-  while (prec != 0 && nb > 1 && cdiv(n_out, 128) * (cout / (32 * nb)) < small) nb /= 2;
+  while (prec != 0 && nb > 1 && cdiv(n_out, 128) * (cout / (32 * nb)) < FWD_NB_SMALL_WGS) nb /= 2;
   return nb;
 }
 
+// slabs of a weight-gradient launch: the count fixes the summation order of the result and the value of
+// gcl_conv_bwd_weight_scratch_len (more, smaller slabs measured slower: 1024 / 2048 -> wgrad sum 3.19 -> 3.28 / 3.38 ms per step)
+constexpr int DW_MAX_WGS = 512;
 static int bwd_weight_wgs(long long n_chunks) {
-  static const int cap = [] { const char* e = getenv("GCL_DW_MAX_WGS"); int v = e ? atoi(e) : 512; return v < 64 ? 64 : (v > 8192 ? 8192 : v); }();
-  long long w = n_chunks / 8;     // (more, smaller slabs measured slower: GCL_DW_MAX_WGS 1024 / 2048 -> wgrad sum 3.19 -> 3.28 / 3.38 ms per step)
+  long long w = n_chunks / 8;
   if (w < 1) w = 1;
-  if (w > cap) w = cap;
+  if (w > DW_MAX_WGS) w = DW_MAX_WGS;
   return (int)w;
 }
 
@@ -2294,12 +2292,10 @@ static DwLaunch dw_launch_shape(int K, int ca, int cb, int prec, int planes_arg,
     s.nr = (int)cdiv(n_sorted, s.rr);
     return s;
   }
-  static const int dwswz = [] { const char* e = getenv("GCL_DW_SWIZZLE"); return e ? atoi(e) : 1; }();
   // plane images with Ca, Cb multiples of 128: one 128 x 128 block per workgroup, rows gathered once and shared by its four
-  // waves (k_conv_bwd_weight_wg128; GCL_DW_WG128=0 / bit 1 of `planes`: the 64 x 64 kernel)
-  static const int wg128 = [] { const char* e = getenv("GCL_DW_WG128"); return e ? atoi(e) : 1; }();
+  // waves (k_conv_bwd_weight_wg128; bit 1 of `planes`: the 64 x 64 kernel)
   int tiles;
-  if (prec == 4 && planes && wg128 && !legacy_dw && ca % 128 == 0 && cb % 128 == 0) {
+  if (prec == 4 && planes && !legacy_dw && ca % 128 == 0 && cb % 128 == 0) {
     s.path = GCL_DW_PATH_WG128;
     s.ta = s.tb = 128;
     tiles = (ca / 128) * (cb / 128);
@@ -2309,8 +2305,68 @@ static DwLaunch dw_launch_shape(int K, int ca, int cb, int prec, int planes_arg,
     s.tb = (cb % 64 == 0) ? 64 : 32;
     tiles = (ca / s.ta) * (cb / s.tb);
   }
-  s.stiles = (dwswz && tiles > 1 && s.path != GCL_DW_PATH_F32) ? tiles : 0;      // the exact-f32 kernel keeps the 2-D grid
+  // XCD-aware launch order: the channel tiles of one pair range share an L2 (the exact-f32 kernel keeps the 2-D grid)
+  s.stiles = (tiles > 1 && s.path != GCL_DW_PATH_F32) ? tiles : 0;
   return s;
+}
+
+// shapes the MFMA kernels do not take
+static bool generic_shape(int K, int cin, int cout) { return (cin % 32) != 0 || (cout % 32) != 0 || K > 27; }
+
+// Layers an inference launch (flag GCL_CONV_TALL) runs with the tile's offsets in four fixed groups: at least
+// FWD_TALL_MIN_STEPS = 108 steps per full tile (27 offsets x Cin / 32 >= 4).  Decided by the layer's shape only, so that a
+// row's bits never depend on the launch it is in.  Measured (bench.py secondary, one pair / eight pairs per pass,
+// M voxels/s): off 15.5 / 80.3, Cin >= 128 (this rule) 20.1 / 80 (77.0 with ranges of k instead of k mod 4), Cin >= 64
+// 20.9 / 65.6; eval_pairs 146 -> 160 - 165 pairs/s.
+constexpr int FWD_TALL_MIN_STEPS = 108;
+static bool fwd_tall_shape(int K, int cin, int cout) {
+  return K >= 8 && K <= 27 && cin % 32 == 0 && K * (cin / 32) >= FWD_TALL_MIN_STEPS && cout > 0 && cout % 64 == 0;
+}
+// ... and, up to this many output rows, as four times as many ordinary workgroups when the caller hands over scratch
+constexpr long long FWD_GROUPS_MAX_ROWS = 65536;
+
+// Every host-side decision of a forward / input-gradient launch after argument checking (gcl_conv_fwd_fused_ld launches
+// what this says and nothing else; gcl_conv_fwd_launch_shape exports it).
+//   path: the kernel family (GCL_FWD_PATH_*); nb, pl, pre, epi: its template arguments (nb = TC for the generic kernel;
+//   pl = prec); gx x gy workgroups of `block` threads; swz: the launch-order word handed to the kernel -- bit 0: a
+//   contiguous tile range per XCD (GCL_CONV_XCD_RANGES), bit 1: 1-D grid of cdiv(tiles, 8) * 8 * column blocks, the column
+//   blocks of a row tile on one XCD (they re-read the same gathered rows), bit 4: the mask-sorted row tiles in descending
+//   order, the workgroups with the most offsets first (ascending measured 14 % slower).
+struct FwdLaunch {
+  int path, nb, pl;
+  bool pre, epi;
+  unsigned gx, gy;
+  int block, swz;
+};
+static FwdLaunch conv_fwd_launch_shape(long long n_out, int K, int cin, int cout, int prec, bool planes, bool use_epi,
+                                       bool sorted, bool group_scratch, int flags) {
+  if (generic_shape(K, cin, cout)) {
+    const int tc = cout > 8 ? 16 : 8;
+    return {GCL_FWD_PATH_GENERIC, tc, 0, false, use_epi, (unsigned)cdiv(n_out, 256), (unsigned)cdiv(cout, tc), 256, 0};
+  }
+  const unsigned tiles = (unsigned)cdiv(n_out, CONV_ROWS), tiles8 = (unsigned)(cdiv(tiles, 8) * 8);
+  const bool ranges = (flags & GCL_CONV_XCD_RANGES) != 0;     // spatially ordered table: contiguous tile range per XCD
+  // inference launches: sixteen waves per workgroup (TALL), or -- round 6 -- the same four offset groups as FOUR TIMES AS
+  // MANY ordinary workgroups (k_conv_fwd_dma<2, false, false, GRP>) + one sum / epilogue launch, when the caller hands over
+  // scratch for the four accumulator slabs.  A pass over one pair leaves 52 sixteen-wave workgroups on 256 CUs, each
+  // walking 54 dependent steps at the round trip of a weight block with one step of prefetch (1.3 us per step: 72 us per
+  // launch, ten launches = 0.72 of a 1.75 ms pass); as 832 four-wave workgroups three of them share a CU and cover each
+  // other's round trips.  Same products in the same order per group, the same group order, the same epilogue expression:
+  // bitwise k_conv_fwd_tall's result.
+  if ((flags & GCL_CONV_TALL) && prec == 4 && !planes && sorted && !ranges && fwd_tall_shape(K, cin, cout)) {
+    if (group_scratch && n_out <= FWD_GROUPS_MAX_ROWS)
+      return {GCL_FWD_PATH_GROUPS, 2, 4, false, use_epi, tiles8 * (cout / 64) * 4, 1, 256, 2 | 16};
+    return {GCL_FWD_PATH_TALL, 2, 4, false, use_epi, tiles8 * (cout / 64), 1, 1024, 2 | 16};
+  }
+  const int nb = conv_fwd_nb(n_out, cout, prec);
+  const unsigned cols = cout / (32 * nb);
+  if (prec == 0) return {GCL_FWD_PATH_F32, nb, 0, false, false, tiles, cols, 256, 0};
+  // fp16x3 stages its operands by LDS-DMA (k_conv_fwd_dma; the flag GCL_CONV_NO_DMA selects the register-staged
+  // k_conv_fwd_split): bitwise the same results, 15 - 21 % shorter launches on the C >= 128 layers of the KITTI batch
+  // (profiles/r04_conv_experiments.txt, 19), fp32-row launches (the C = 32 / 64 layers) too
+  const int path = (prec == 4 && !(flags & GCL_CONV_NO_DMA)) ? GCL_FWD_PATH_DMA : GCL_FWD_PATH_SPLIT;
+  const int swz = (cols > 1 ? 2 : 0) | (ranges ? 1 : 0) | ((sorted && !ranges) ? 16 : 0);
+  return {path, nb, prec, planes, use_epi, cols > 1 ? tiles8 * cols : tiles, 1, 256, swz};
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2700,9 +2756,6 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_generic(const float* __
   flush(kcur);
 }
 
-// shapes the MFMA kernels do not take
-static bool generic_shape(int K, int cin, int cout) { return (cin % 32) != 0 || (cout % 32) != 0 || K > 27; }
-
 }  // namespace gcl
 
 using namespace gcl;
@@ -2825,10 +2878,7 @@ int gcl_conv_fwd_fused(const float* x, int64_t n_in, int32_t x_is_planes, const 
                        float* stats, int32_t flags, void* stream);
 
 int64_t gcl_conv_fwd_groups_scratch_len(int64_t n_out, int32_t K, int32_t cin, int32_t cout) {
-  static const int on = [] { const char* e = getenv("GCL_FWD_GROUPS"); return e ? atoi(e) : 1; }();
-  static const long long max_rows = [] { const char* e = getenv("GCL_FWD_GROUPS_MAX_ROWS"); return e ? atoll(e) : 65536ll; }();
-  static const int tall_min = [] { const char* e = getenv("GCL_FWD_TALL_MIN_STEPS"); return e ? atoi(e) : 108; }();
-  if (!on || n_out <= 0 || n_out > max_rows || K < 8 || K > 27 || (cin % 32) || (cout % 64) || K * (cin / 32) < tall_min) return 0;
+  if (n_out <= 0 || n_out > FWD_GROUPS_MAX_ROWS || !fwd_tall_shape(K, cin, cout)) return 0;
   return 4ll * n_out * cout;
 }
 
@@ -2862,166 +2912,116 @@ int gcl_conv_fwd_fused_ld(const float* x, int64_t n_in, int32_t x_is_planes, con
   GCL_CHECK_ARG(prec != 0 || generic_shape(K, cin, cout) || (!col_scale && !residual && !relu && !y_amax),
                 "gcl_conv_fwd_fused: the fused epilogue needs a split-precision mode");
   GCL_CHECK_ARG(x && wp && y, "gcl_conv_fwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
   if (generic_shape(K, cin, cout)) {     // any Cin / Cout, K <= 125: exact-fp32 VALU kernel (wp = fp32 W_eff, see gcl_pack_weights)
     GCL_CHECK_ARG(n_in > 0 && n_out > 0 && K >= 1 && K <= 125 && cin > 0 && cout > 0, "gcl_conv_fwd: bad shape");
     GCL_CHECK_ARG(tbl || K == 1, "gcl_conv_fwd: a neighbour table is required when K > 1");
     GCL_CHECK_ARG(!stats, "gcl_conv_fwd: fused BN statistics need Cin, Cout multiples of 32 and K <= 27");
     GCL_CHECK_ARG(!x_is_planes, "gcl_conv_fwd: plane images need Cin, Cout multiples of 32 and K <= 27");
-    hipStream_t gst = (hipStream_t)stream;
-    if (cout > 8) {
-      hipLaunchKernelGGL(k_conv_generic<16>, dim3((unsigned)cdiv(n_out, 256), (unsigned)cdiv(cout, 16)), dim3(256), 0, gst,
-                         x, (const float*)wp, tbl, order, (long long)n_out, K, cin, cout, bias, y, epi);
-    } else {
-      hipLaunchKernelGGL(k_conv_generic<8>, dim3((unsigned)cdiv(n_out, 256), (unsigned)cdiv(cout, 8)), dim3(256), 0, gst,
-                         x, (const float*)wp, tbl, order, (long long)n_out, K, cin, cout, bias, y, epi);
-    }
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
+  } else {
+    GCL_CHECK_ARG(n_in > 0 && (long long)n_in * cin * 4 < (1ll << 32) - (1ll << 20),
+                  "gcl_conv_fwd: the input tensor must be non-empty and smaller than 4 GiB (buffer addressing)");
+    GCL_CHECK_ARG(n_out > 0 && K >= 1 && K <= 27, "gcl_conv_fwd: n_out must be positive and 1 <= K <= 27");
+    GCL_CHECK_ARG(tbl || K == 1, "gcl_conv_fwd: a neighbour table is required when K > 1");
+    GCL_CHECK_ARG((order == nullptr) == (tile_mask == nullptr), "gcl_conv_fwd: order and tile_mask go together");
+    GCL_CHECK_ARG(cin % 32 == 0 && cout % 32 == 0 && cin > 0 && cout > 0,
+                  "gcl_conv_fwd: Cin (%d) and Cout (%d) must be positive multiples of 32", cin, cout);
+    GCL_CHECK_ARG(prec_ok(prec), "gcl_conv_fwd: prec must be 0 (f32), 2 (bf16x3), 3 (bf16x6) or 4 (fp16x3)");
+    GCL_CHECK_ARG(!stats || prec != 0, "gcl_conv_fwd: fused BN statistics need a split-precision mode");
+    GCL_CHECK_ARG(prec != 4 || (x_amax && w_amax), "gcl_conv_fwd: fp16x3 needs gcl_amax of x and of the weights");
+    GCL_CHECK_ARG(!x_is_planes || prec == 4, "gcl_conv_fwd: plane images are the fp16x3 operand format");
   }
-  GCL_CHECK_ARG(n_in > 0 && (long long)n_in * cin * 4 < (1ll << 32) - (1ll << 20),
-                "gcl_conv_fwd: the input tensor must be non-empty and smaller than 4 GiB (buffer addressing)");
-  const unsigned x_bytes = (unsigned)((long long)n_in * cin * 4);
-  GCL_CHECK_ARG(n_out > 0 && K >= 1 && K <= 27, "gcl_conv_fwd: n_out must be positive and 1 <= K <= 27");
-  GCL_CHECK_ARG(tbl || K == 1, "gcl_conv_fwd: a neighbour table is required when K > 1");
-  GCL_CHECK_ARG((order == nullptr) == (tile_mask == nullptr), "gcl_conv_fwd: order and tile_mask go together");
-  GCL_CHECK_ARG(cin % 32 == 0 && cout % 32 == 0 && cin > 0 && cout > 0,
-                "gcl_conv_fwd: Cin (%d) and Cout (%d) must be positive multiples of 32", cin, cout);
-  GCL_CHECK_ARG(prec_ok(prec), "gcl_conv_fwd: prec must be 0 (f32), 2 (bf16x3), 3 (bf16x6) or 4 (fp16x3)");
-  GCL_CHECK_ARG(!stats || prec != 0, "gcl_conv_fwd: fused BN statistics need a split-precision mode");
-  GCL_CHECK_ARG(prec != 4 || (x_amax && w_amax), "gcl_conv_fwd: fp16x3 needs gcl_amax of x and of the weights");
-  GCL_CHECK_ARG(!x_is_planes || prec == 4, "gcl_conv_fwd: plane images are the fp16x3 operand format");
-  hipStream_t st = (hipStream_t)stream;
-  static const int swz = [] {   // tuning knob, default off (measured: -5 % with the global sort, +7 % with the windowed sort)
-    const char* e = getenv("GCL_XCD_SWIZZLE");
-    return e ? atoi(e) : 0;
-  }();
-  unsigned gx = (unsigned)cdiv(n_out, CONV_ROWS);
-  const int nb = conv_fwd_nb(n_out, cout, prec);
-  dim3 grid(gx, cout / (32 * nb));
-  static const int colgroup = [] { const char* e = getenv("GCL_FWD_COLGROUP"); return e ? atoi(e) : 1; }();
-  const bool cg = colgroup && grid.y > 1 && !swz;
-  dim3 sgrid = cg ? dim3((unsigned)(cdiv(gx, 8) * 8 * grid.y)) : grid;
-  const bool ranges = (flags & GCL_CONV_XCD_RANGES) != 0;     // spatially ordered table: contiguous tile range per XCD
-  static const int heavy_first = [] { const char* e = getenv("GCL_CONV_HEAVY_FIRST"); return e ? atoi(e) : 1; }();
-  const int sswz = (cg ? (ranges ? 3 : 2) : (ranges ? 1 : swz)) | ((heavy_first && tile_mask && !ranges) ? 16 : 0);
-#define LAUNCH_F32(NBV)                                                                                          \
-  hipLaunchKernelGGL(k_conv_fwd<NBV>, grid, dim3(256), 0, st, x, (const float4*)wp, tbl, order, tile_mask,       \
-                     (long long)n_out, K, cin, cout, bias, y, swz)
-#define LAUNCH_SPLIT_I(NBV, PLV, PREV, EPIV)                                                                     \
-  hipLaunchKernelGGL((k_conv_fwd_split<NBV, PLV, PREV, EPIV>), sgrid, dim3(256), 0, st, x, (const u32x4*)wp, tbl, \
-                     order, tile_mask, (long long)n_out, K, cin, cout, bias, y, sswz, stats, x_amax, w_amax,   \
-                     x_bytes, epi)
-#define LAUNCH_SPLIT(NBV, PLV)                                                                                   \
-  do {                                                                                                           \
-    if (PLV == 4 && x_is_planes) {                                                                               \
-      if (use_epi) LAUNCH_SPLIT_I(NBV, 4, true, true); else LAUNCH_SPLIT_I(NBV, 4, true, false);                 \
-    } else {                                                                                                     \
-      if (use_epi) LAUNCH_SPLIT_I(NBV, PLV, false, true); else LAUNCH_SPLIT_I(NBV, PLV, false, false);           \
-    }                                                                                                            \
+  // `stats` of a GCL_CONV_TALL launch is the scratch of the offset-group launches (gcl_conv_fwd_groups_scratch_len floats)
+  // or NULL; such a launch writes no BatchNorm partials
+  float* const groups = (flags & GCL_CONV_TALL) ? stats : nullptr;
+  float* const partials = (flags & GCL_CONV_TALL) ? nullptr : stats;
+  const FwdLaunch s = conv_fwd_launch_shape(n_out, K, cin, cout, prec, x_is_planes != 0, use_epi, tile_mask != nullptr,
+                                            groups != nullptr, flags);
+  const dim3 grid(s.gx, s.gy), block(s.block);
+  const unsigned x_bytes = (unsigned)((long long)n_in * cin * 4), w_bytes = (unsigned)((long long)K * cin * cout * 4);
+  // the template fan-out over the values of s.nb, s.pre and s.epi: L(NB, [PL,] PRE, EPI)
+#define FAN_EPI(L, ...) do { if (s.epi) L(__VA_ARGS__, true); else L(__VA_ARGS__, false); } while (0)
+#define FAN_PRE(L, ...) do { if (s.pre) FAN_EPI(L, __VA_ARGS__, true); else FAN_EPI(L, __VA_ARGS__, false); } while (0)
+#define FAN_NB(F, L, ...)                                                                                   \
+  do {                                                                                                      \
+    if (s.nb == 4) F(L, 4, ##__VA_ARGS__); else if (s.nb == 2) F(L, 2, ##__VA_ARGS__); else F(L, 1, ##__VA_ARGS__); \
   } while (0)
-#define LAUNCH_SPLIT_NB(PLV)                                                             \
-  {                                                                                      \
-    if (nb == 4) LAUNCH_SPLIT(4, PLV); else if (nb == 2) LAUNCH_SPLIT(2, PLV); else LAUNCH_SPLIT(1, PLV); \
-  }
-#define LAUNCH_SPLIT_NB2(PLV)                                                            \
-  {                                                                                      \
-    if (nb >= 2) LAUNCH_SPLIT(2, PLV); else LAUNCH_SPLIT(1, PLV);                        \
-  }
-  // inference launches (flag GCL_CONV_TALL): sixteen-wave workgroups, the tile's offsets in four fixed groups, for layers
-  // with at least tall_min = 108 steps per full tile (27 offsets x Cin / 32 >= 4).  Decided by the layer's shape only, so that
-  // a row's bits never depend on the launch it is in.  Measured (bench.py secondary, one pair / eight pairs per pass,
-  // M voxels/s): off 15.5 / 80.3, Cin >= 128 (default) 20.1 / 80 (77.0 with ranges of k instead of k mod 4), Cin >= 64 20.9 / 65.6;
-  // eval_pairs 146 -> 160 - 165 pairs/s.
-  static const int tall = [] { const char* e = getenv("GCL_FWD_TALL"); return e ? atoi(e) : 1; }();
-  static const int tall_min = [] { const char* e = getenv("GCL_FWD_TALL_MIN_STEPS"); return e ? atoi(e) : 108; }();
-  // Round 6: the same four offset groups as FOUR TIMES AS MANY ordinary workgroups (k_conv_fwd_dma<2, false, false, GRP>) + one
-  // sum / epilogue launch, when the caller hands over scratch for the four accumulator slabs (`stats` of a GCL_CONV_TALL
-  // launch: gcl_conv_fwd_groups_scratch_len floats).  A pass over one pair leaves 52 sixteen-wave workgroups on 256 CUs,
-  // each walking 54 dependent steps at the round trip of a weight block with one step of prefetch (1.3 us per step: 72 us per
-  // launch, ten launches = 0.72 of a 1.75 ms pass); as 832 four-wave workgroups three of them share a CU and cover each
-  // other's round trips.  Same products in the same order per group, the same group order, the same epilogue expression:
-  // bitwise k_conv_fwd_tall's result.
-  if (tall && (flags & GCL_CONV_TALL) && stats && gcl_conv_fwd_groups_scratch_len(n_out, K, cin, cout) > 0 && prec == 4 &&
-      !x_is_planes && tbl && tile_mask && colgroup && !swz && !ranges) {
-    const dim3 ggrid((unsigned)(cdiv(gx, 8) * 8 * (cout / 64) * 4));
-    const int gswz = 2 | (heavy_first ? 16 : 0);
-    const unsigned w_bytes = (unsigned)((long long)K * cin * cout * 4);
-    const ConvEpi none{nullptr, nullptr, 0, nullptr, 0};
-    hipLaunchKernelGGL((k_conv_fwd_dma<2, false, false, true>), ggrid, dim3(256), 0, st, x, (const u32x4*)wp, tbl, order, tile_mask,
-                       (long long)n_out, K, cin, cout, (const float*)nullptr, stats, gswz, (float*)nullptr, x_amax, w_amax, x_bytes,
-                       w_bytes, none);
-    // four float4 groups per thread, all sixteen slab loads in flight (GCL_GROUPS_SUM_ILP=1: one group per thread, the same
-    // bits): 14.7 -> 9.6 us per launch on a pass over one pair, 27.8 -> 29.0 M voxels/s; eight groups: 28.5
-    static const int sum_ilp = [] { const char* e = getenv("GCL_GROUPS_SUM_ILP"); return e ? atoi(e) : 4; }();
-    if (sum_ilp == 4) {
-      const unsigned sg = (unsigned)cdiv((long long)n_out * cout, 4096);
-      if (use_epi)
-        hipLaunchKernelGGL((k_conv_groups_sum<true, 4>), dim3(sg), dim3(256), 0, st, (const float*)stats, (long long)n_out, cout,
-                           bias, x_amax, w_amax, epi, y);
-      else
-        hipLaunchKernelGGL((k_conv_groups_sum<false, 4>), dim3(sg), dim3(256), 0, st, (const float*)stats, (long long)n_out, cout,
-                           bias, x_amax, w_amax, epi, y);
-    } else {
-      const unsigned sg = (unsigned)cdiv((long long)n_out * cout, 1024);
-      if (use_epi)
-        hipLaunchKernelGGL((k_conv_groups_sum<true>), dim3(sg), dim3(256), 0, st, (const float*)stats, (long long)n_out, cout, bias,
-                           x_amax, w_amax, epi, y);
-      else
-        hipLaunchKernelGGL((k_conv_groups_sum<false>), dim3(sg), dim3(256), 0, st, (const float*)stats, (long long)n_out, cout, bias,
-                           x_amax, w_amax, epi, y);
+#define LAUNCH_GENERIC(TC)                                                                                        \
+  hipLaunchKernelGGL(k_conv_generic<TC>, grid, block, 0, st, x, (const float*)wp, tbl, order, (long long)n_out, K, cin, \
+                     cout, bias, y, epi)
+#define FWD(KERNEL, WT, ...)                                                                                      \
+  hipLaunchKernelGGL((KERNEL), grid, block, 0, st, x, (const WT*)wp, tbl, order, tile_mask, (long long)n_out, K, cin, cout, \
+                     bias, y, __VA_ARGS__)
+#define LAUNCH_F32(NBV) FWD(k_conv_fwd<NBV>, float4, 0)
+#define LAUNCH_SPLIT(NBV, PLV, PREV, EPIV) \
+  FWD((k_conv_fwd_split<NBV, PLV, PREV, EPIV>), u32x4, s.swz, partials, x_amax, w_amax, x_bytes, epi)
+#define LAUNCH_DMA(NBV, PREV, EPIV) \
+  FWD((k_conv_fwd_dma<NBV, PREV, EPIV>), u32x4, s.swz, partials, x_amax, w_amax, x_bytes, w_bytes, epi)
+#define LAUNCH_TALL(EPIV) FWD(k_conv_fwd_tall<EPIV>, u32x4, s.swz, x_amax, w_amax, x_bytes, epi)
+  // four float4 groups per thread, all sixteen slab loads in flight (against one group per thread, the same bits:
+  // 14.7 -> 9.6 us per launch on a pass over one pair, 27.8 -> 29.0 M voxels/s; eight groups: 28.5)
+#define LAUNCH_GROUPS_SUM(EPIV)                                                                                  \
+  hipLaunchKernelGGL((k_conv_groups_sum<EPIV, 4>), dim3((unsigned)cdiv((long long)n_out * cout, 4096)), dim3(256), 0, st, \
+                     (const float*)groups, (long long)n_out, cout, bias, x_amax, w_amax, epi, y)
+  // (the order of the cases is the order in which the instances are first named, and the compiler's register assignment
+  // inside some of them follows it: keep it, or compare the device code after a change)
+  switch (s.path) {
+    case GCL_FWD_PATH_GENERIC:
+      if (s.nb == 16) LAUNCH_GENERIC(16); else LAUNCH_GENERIC(8);
+      break;
+    case GCL_FWD_PATH_GROUPS: {
+      const ConvEpi none{nullptr, nullptr, 0, nullptr, 0};
+      hipLaunchKernelGGL((k_conv_fwd_dma<2, false, false, true>), grid, block, 0, st, x, (const u32x4*)wp, tbl, order, tile_mask,
+                         (long long)n_out, K, cin, cout, (const float*)nullptr, groups, s.swz, (float*)nullptr, x_amax, w_amax,
+                         x_bytes, w_bytes, none);
+      if (s.epi) LAUNCH_GROUPS_SUM(true); else LAUNCH_GROUPS_SUM(false);
+      break;
     }
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
+    case GCL_FWD_PATH_TALL:
+      if (s.epi) LAUNCH_TALL(true); else LAUNCH_TALL(false);
+      break;
+    case GCL_FWD_PATH_DMA:
+      FAN_NB(FAN_PRE, LAUNCH_DMA);
+      break;
+    case GCL_FWD_PATH_F32:
+      if (s.nb == 4) LAUNCH_F32(4); else if (s.nb == 2) LAUNCH_F32(2); else LAUNCH_F32(1);
+      break;
+    case GCL_FWD_PATH_SPLIT:
+      if (s.pl == 4) FAN_NB(FAN_PRE, LAUNCH_SPLIT, 4);
+      else if (s.pl == 2) FAN_NB(FAN_EPI, LAUNCH_SPLIT, 2, false);
+      else if (s.nb == 2) FAN_EPI(LAUNCH_SPLIT, 2, 3, false);      // three planes: NB <= 2 (conv_fwd_nb)
+      else FAN_EPI(LAUNCH_SPLIT, 1, 3, false);
+      break;
   }
-  if (tall && (flags & GCL_CONV_TALL)) stats = nullptr;      // scratch of the group launches, not wanted by this shape / size
-  if (tall && (flags & GCL_CONV_TALL) && prec == 4 && !x_is_planes && !stats && tbl && tile_mask && K >= 8 &&
-      K * (cin / 32) >= tall_min && cout % 64 == 0 && colgroup && !swz && !ranges) {
-    const dim3 tgrid((unsigned)(cdiv(gx, 8) * 8 * (cout / 64)));
-    const int tswz = 2 | (heavy_first ? 16 : 0);
-    if (use_epi)
-      hipLaunchKernelGGL((k_conv_fwd_tall<true>), tgrid, dim3(1024), 0, st, x, (const u32x4*)wp, tbl, order, tile_mask,
-                         (long long)n_out, K, cin, cout, bias, y, tswz, x_amax, w_amax, x_bytes, epi);
-    else
-      hipLaunchKernelGGL((k_conv_fwd_tall<false>), tgrid, dim3(1024), 0, st, x, (const u32x4*)wp, tbl, order, tile_mask,
-                         (long long)n_out, K, cin, cout, bias, y, tswz, x_amax, w_amax, x_bytes, epi);
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
-  }
-  // plane-image launches with LDS-DMA staging (k_conv_fwd_dma; default, GCL_FWD_DMA=0 / flag GCL_CONV_NO_DMA select the
-  // register-staged k_conv_fwd_split): bitwise the same results, 15 - 21 % shorter launches on the C >= 128 layers of the
-  // KITTI batch (profiles/r04_conv_experiments.txt, 19)
-  static const int dma = [] { const char* e = getenv("GCL_FWD_DMA"); return e ? atoi(e) : 1; }();
-  // fp32-row launches too (the C = 32 / 64 layers; GCL_FWD_DMA_ROWS=0: plane images only)
-  static const int dma_rows = [] { const char* e = getenv("GCL_FWD_DMA_ROWS"); return e ? atoi(e) : 1; }();
-  if ((dma || (flags & GCL_CONV_DMA)) && !(flags & GCL_CONV_NO_DMA) && prec == 4 && (x_is_planes || dma_rows)) {
-    const unsigned w_bytes = (unsigned)((long long)K * cin * cout * 4);
-#define LAUNCH_DMA(NBV, PREV, EPIV)                                                                               \
-  hipLaunchKernelGGL((k_conv_fwd_dma<NBV, PREV, EPIV>), sgrid, dim3(256), 0, st, x, (const u32x4*)wp, tbl, order,  \
-                     tile_mask, (long long)n_out, K, cin, cout, bias, y, sswz, stats, x_amax, w_amax, x_bytes, w_bytes, epi)
-#define LAUNCH_DMA_P(NBV)                                                                                         \
-  do {                                                                                                            \
-    if (x_is_planes) { if (use_epi) LAUNCH_DMA(NBV, true, true); else LAUNCH_DMA(NBV, true, false); }             \
-    else { if (use_epi) LAUNCH_DMA(NBV, false, true); else LAUNCH_DMA(NBV, false, false); }                       \
-  } while (0)
-    if (nb == 4) LAUNCH_DMA_P(4); else if (nb == 2) LAUNCH_DMA_P(2); else LAUNCH_DMA_P(1);
-#undef LAUNCH_DMA_P
+#undef LAUNCH_GROUPS_SUM
+#undef LAUNCH_TALL
 #undef LAUNCH_DMA
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
-  }
-  if (prec == 0) {
-    if (nb == 4) LAUNCH_F32(4); else if (nb == 2) LAUNCH_F32(2); else LAUNCH_F32(1);
-  } else if (prec == 2) LAUNCH_SPLIT_NB(2)
-  else if (prec == 3) {   // three planes: the double-buffered weight block of NB = 4 would not leave room for 2 WGs/CU
-    if (nb == 4) grid = dim3(gx, cout / 64);
-    LAUNCH_SPLIT_NB2(3)
-  } else LAUNCH_SPLIT_NB(4)
-#undef LAUNCH_F32
 #undef LAUNCH_SPLIT
-#undef LAUNCH_SPLIT_I
-#undef LAUNCH_SPLIT_NB
-#undef LAUNCH_SPLIT_NB2
+#undef LAUNCH_F32
+#undef FWD
+#undef LAUNCH_GENERIC
+#undef FAN_NB
+#undef FAN_PRE
+#undef FAN_EPI
   GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+// out = {path, nb, pl, pre + 2 * epi, grid x, grid y, block, swizzle word}: see include/gcl_amd.h
+int gcl_conv_fwd_launch_shape(int64_t n_out, int32_t K, int32_t cin, int32_t cout, int32_t prec, int32_t x_is_planes,
+                              int32_t fused_epilogue, int32_t sorted_table, int32_t group_scratch, int32_t flags,
+                              int32_t out[8]) {
+  GCL_CHECK_ARG(out && n_out > 0 && K >= 1 && K <= 125 && cin > 0 && cout > 0 && prec_ok(prec),
+                "gcl_conv_fwd_launch_shape: bad argument");
+  const bool generic = generic_shape(K, cin, cout);
+  GCL_CHECK_ARG(!x_is_planes || (prec == 4 && !generic),
+                "gcl_conv_fwd_launch_shape: plane images are the fp16x3 operand format (Cin, Cout multiples of 32, K <= 27)");
+  GCL_CHECK_ARG(!fused_epilogue || prec != 0 || generic,
+                "gcl_conv_fwd_launch_shape: the fused epilogue needs a split-precision mode");
+  const FwdLaunch s = conv_fwd_launch_shape(n_out, K, cin, cout, prec, x_is_planes != 0, fused_epilogue != 0,
+                                            sorted_table != 0, group_scratch != 0 && (flags & GCL_CONV_TALL), flags);
+  const int v[8] = {s.path, s.nb, s.pl, (int)s.pre + 2 * (int)s.epi, (int)s.gx, (int)s.gy, s.block, s.swz};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
   return GCL_OK;
 }
 
@@ -3186,8 +3186,7 @@ int gcl_conv_bwd_weight_launch_shape(int32_t K, int32_t ca, int32_t cb, int32_t 
 
 // kernel_size-1 convolutions: dW = A^T B over ALL rows (pair (i, i) for every i), streamed (k_bwd_weight_rows)
 static bool dw_rows_shape(int ca, int cb, int prec) {
-  static const int on = [] { const char* e = getenv("GCL_DW_ROWS"); return e ? atoi(e) : 1; }();
-  return on && prec == 4 && ca % 32 == 0 && cb % 32 == 0 && ca >= 32 && cb >= 32 && ca <= 128 && cb <= 64 &&
+  return prec == 4 && ca % 32 == 0 && cb % 32 == 0 && ca >= 32 && cb >= 32 && ca <= 128 && cb <= 64 &&
          (ca / 32) * (cb / 32) <= 6;
 }
 static int dw_rows_steps_per_wg(long long n_rows) {
@@ -3248,13 +3247,13 @@ int gcl_stem_fwd(const float* x, const float* w, const int32_t* nbr, int64_t n_o
   return GCL_OK;
 }
 
-// Rows per workgroup of k_stem_bwd_weight: the tiles are dealt evenly to at most `slots` workgroups -- four per CU of an
+// Rows per workgroup of k_stem_bwd_weight: the tiles are dealt evenly to at most STEM_DW_WGS workgroups -- four per CU of an
 // MI355X, one round (a fixed 1024 rows per workgroup ran 518 workgroups on 512 places at 0.53 M rows: a second round of
 // six).  A constant, not the device's CU count: the slab count fixes the summation order of the result.
+constexpr int STEM_DW_WGS = 1024;
 static long long stem_rows_per_wg(long long n_out, int cout) {
-  static const int slots = [] { const char* e = getenv("GCL_STEM_DW_WGS"); int v = e ? atoi(e) : 1024; return v < 1 ? 1 : v; }();
   int col_blocks = cout / 32;
-  long long s = slots / (col_blocks > 0 ? col_blocks : 1);
+  long long s = STEM_DW_WGS / (col_blocks > 0 ? col_blocks : 1);
   if (s < 1) s = 1;
   long long per = cdiv(cdiv(n_out, STEM_TILE), s);
   if (per < 8) per = 8;      // small inputs: few slabs rather than many workgroups

@@ -279,10 +279,9 @@ int gcl_split_planes(const float* x, int64_t n, int32_t c, const int32_t* amax, 
                                non-zero length: <= 65536 output rows) the four groups run as four times as many ordinary
                                workgroups + one sum / epilogue launch -- bitwise the sixteen-wave kernel's result, 2 - 3 x
                                shorter on the deep layers of a pass over one or two clouds. */
-#define GCL_CONV_DMA 2      /* plane-image launches (fp16x3): operands staged by LDS-DMA (`buffer_load ... lds`: no staging
-                               registers, no ds_write); bitwise the same results.  The default (GCL_FWD_DMA=0 turns it off
-                               unless this flag is set) */
-#define GCL_CONV_NO_DMA 8   /* ... and this flag selects the register-staged kernel for a launch regardless */
+#define GCL_CONV_DMA 2      /* accepted, no effect: every fp16x3 launch stages its operands by LDS-DMA (`buffer_load ... lds`: no
+                               staging registers, no ds_write) unless GCL_CONV_NO_DMA is set */
+#define GCL_CONV_NO_DMA 8   /* fp16x3: the register-staged kernel for this launch; bitwise the same results */
 int gcl_conv_fwd(const float* x, int64_t n_in, int32_t x_is_planes, const void* wp, int32_t prec, const int32_t* x_amax,
                  const int32_t* w_amax, const int32_t* tbl, const int32_t* order, const int32_t* tile_mask,
                  int64_t n_out, int32_t K,
@@ -308,6 +307,24 @@ int gcl_conv_fwd_fused_ld(const float* x, int64_t n_in, int32_t x_is_planes, con
                           const int32_t* tile_mask, int64_t n_out, int32_t K, int32_t cin, int32_t cout, const float* bias,
                           const float* col_scale, const float* residual, int32_t residual_ld, int32_t relu,
                           int32_t* y_amax, float* y, float* stats, int32_t flags, void* stream);
+
+/* What gcl_conv_fwd(_fused(_ld)) launches for a shape: host arithmetic, no GPU (the dispatcher itself calls the same
+ * function after its argument checks; tests and profile labels take kernel instances from it).  x_is_planes, flags as
+ * above; fused_epilogue != 0: any of col_scale, residual, relu, y_amax is given; sorted_table != 0: (order, tile_mask) are
+ * given; group_scratch != 0: `stats` of a GCL_CONV_TALL launch is not NULL (ignored without that flag).
+ * out = {path (GCL_FWD_PATH_*), NB (TC for the generic kernel), PL (= prec; 0 for the generic kernel), PRE + 2 EPI
+ * (template arguments: plane-image operand, fused epilogue), grid x, grid y, threads per workgroup, launch-order word of
+ * the kernel (bit 0: a contiguous row-tile range per XCD, bit 1: 1-D grid of ceil(tiles / 8) * 8 * column blocks with a row
+ * tile's column blocks on one XCD, bit 4: mask-sorted row tiles in descending order)}. */
+#define GCL_FWD_PATH_GENERIC 0  /* k_conv_generic<TC>: Cin or Cout no multiple of 32, or K > 27 */
+#define GCL_FWD_PATH_F32 1      /* k_conv_fwd<NB> */
+#define GCL_FWD_PATH_SPLIT 2    /* k_conv_fwd_split<NB, PL, PRE, EPI>: bf16x3, bf16x6; fp16x3 with GCL_CONV_NO_DMA */
+#define GCL_FWD_PATH_DMA 3      /* k_conv_fwd_dma<NB, PRE, EPI>: fp16x3 */
+#define GCL_FWD_PATH_TALL 4     /* k_conv_fwd_tall<EPI>: GCL_CONV_TALL without scratch, or more than 65536 rows */
+#define GCL_FWD_PATH_GROUPS 5   /* k_conv_fwd_dma<2, false, false, true> then k_conv_groups_sum<EPI, 4>: GCL_CONV_TALL with scratch */
+int gcl_conv_fwd_launch_shape(int64_t n_out, int32_t K, int32_t cin, int32_t cout, int32_t prec, int32_t x_is_planes,
+                              int32_t fused_epilogue, int32_t sorted_table, int32_t group_scratch, int32_t flags,
+                              int32_t out[8]);
 
 /* dW[k] = sum over pairs of offset k of  A[pair_a]^T . B[pair_b]   (A: [*, ca], B: [*, cb]) -> dw [K, ca, cb].
  * Forward conv: A = X, pair_a = pair_in, B = dY, pair_b = pair_out.  Transposed conv: roles swapped.

@@ -50,6 +50,24 @@ def test_sizes_sit_at_the_band_edges_of_conv_fwd_nb():
     assert sorted({nb for nb, _ in SIZES}) == [1, 2, 4]
 
 
+INFER_LAYER = (2051, 128, 128)          # rows, Cin, Cout of the inference-sized layer
+
+
+def test_inference_layer_reaches_the_group_launches_and_the_sixteen_wave_kernel():
+    """Host arithmetic (gcl_conv_fwd_launch_shape, the function the dispatcher calls): with GCL_CONV_TALL the inference layer
+    runs the offset-group launches + k_conv_groups_sum when it is handed scratch and k_conv_fwd_tall when it is not, with
+    and without the fused epilogue."""
+    from gcl_amd import _lib
+    lib = _lib.load()
+    n, cin, cout = INFER_LAYER
+    out = (ctypes.c_int32 * 8)()
+    assert lib.gcl_conv_fwd_groups_scratch_len(n, 27, cin, cout) == 4 * n * cout
+    for fused in (0, 1):
+        for has_scratch, path, block in ((1, 5, 256), (0, 4, 1024)):       # include/gcl_amd.h GCL_FWD_PATH_GROUPS, _TALL
+            assert lib.gcl_conv_fwd_launch_shape(n, 27, cin, cout, PREC, 0, fused, 1, has_scratch, TALL, out) == 0
+            assert (out[0], out[3], out[6]) == (path, 2 * fused, block), (fused, has_scratch, list(out))
+
+
 def make_cloud(n, seed):
     """n distinct voxels, 40 % of a box: int32 [n, 4], batch index 0."""
     rng = np.random.RandomState(seed)
@@ -237,7 +255,7 @@ def test_fused_epilogue_equals_the_plain_launch(nb, n, form, staging):
 def test_inference_kernels_fused_epilogue_equals_their_plain_launch(kernel):
     """One inference-sized layer (Cin = 128: 108 steps per tile, GCL_CONV_TALL): the offset-group launches +
     k_conv_groups_sum when the launch is handed scratch, the sixteen-wave k_conv_fwd_tall when it is not."""
-    n, cin, cout = 2051, 128, 128
+    n, cin, cout = INFER_LAYER
     p = layer(n, cin, cout)
     gs_len = p.lib.gcl_conv_fwd_groups_scratch_len(n, 27, cin, cout)
     assert n <= 65536 and gs_len > 0

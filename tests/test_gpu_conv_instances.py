@@ -11,8 +11,10 @@ host dispatcher from (n_out, cout, prec, operand form, epilogue, flags):
 
 NB (32-column blocks per wave) follows from (n_out, cout, prec) in conv_fwd_nb (csrc/conv.hip); small launches take
 narrower blocks, so a test has to pick its row count to reach a wide instance.  CASES below names the instance of every
-case; a test that needs no GPU pins those names against gcl_conv_fwd_nb and requires the table to reach all 37, so a change
-of the dispatcher cannot silently move these tests onto other kernels.
+case; a test that needs no GPU pins those names against gcl_conv_fwd_launch_shape -- the function the dispatcher itself
+calls -- and requires the table to reach all 37, so a change of the dispatcher cannot silently move these tests onto other
+kernels.  Further tests without a GPU pin the paths outside the matrix (generic shapes, the inference kernels of
+GCL_CONV_TALL) and the profile labels of MinkowskiEngine/ops.py.
 
 Per case, on the GPU: y against the fp64 product at the per-operator bound; y, the BatchNorm tile partials and max|y| bit
 for bit against NB = 1 launches of every 32-column slice (the claim "a column's sum is the same chain of products whatever
@@ -35,7 +37,9 @@ gpu = pytest.mark.gpu
 PREC_CODE = {"f32": 0, "bf16x3": 2, "bf16x6": 3, "fp16x3": 4}
 # per-operator tolerance (relative L2 against fp64) of each MFMA arithmetic: tests/test_gpu_parity.py PREC_TOL
 PREC_TOL = {"f32": 2e-6, "bf16x6": 2e-6, "bf16x3": 3e-5, "fp16x3": 2e-6}
-XCD, DMA, NO_DMA = 1, 2, 8          # include/gcl_amd.h GCL_CONV_XCD_RANGES / GCL_CONV_DMA / GCL_CONV_NO_DMA
+XCD, DMA, TALL, NO_DMA = 1, 2, 4, 8          # include/gcl_amd.h GCL_CONV_XCD_RANGES / _DMA / _TALL / _NO_DMA
+# include/gcl_amd.h GCL_FWD_PATH_*
+GENERIC, F32, SPLIT, DMA_PATH, TALL_PATH, GROUPS = range(6)
 
 # Row counts.  n % 128 in 1..31: the last workgroup has one partly filled wave and three idle ones; the "b" counts have
 # n % 128 in 33..127 (full waves, a partly filled one and idle ones).  Tiles of 128 rows: 6 (< 8, fewer tiles than XCDs),
@@ -110,14 +114,36 @@ CASES = [
 ]
 
 
-def instance_of(prec, form, epi, flags, nb):
-    """Name of the kernel instance the dispatcher launches for a case (gcl_conv_fwd_fused_ld in csrc/conv.hip)."""
+def launch_shape(lib, n_out, K, cin, cout, prec, planes=0, fused=0, table=1, scratch=0, flags=0):
+    out = (ctypes.c_int32 * 8)()
+    rc = lib.gcl_conv_fwd_launch_shape(n_out, K, cin, cout, PREC_CODE.get(prec, prec), planes, fused, table, scratch, flags, out)
+    assert rc == 0, (n_out, K, cin, cout, prec, planes, fused, table, scratch, flags)
+    s = dict(zip(("path", "nb", "pl", "pre_epi", "gx", "gy", "block", "swz"), out))
+    s["pre"], s["epi"] = s["pre_epi"] & 1, s["pre_epi"] >> 1
+    return s
+
+
+def case_shape(lib, case, flags=None):
+    """What the dispatcher launches for a CASES entry ("k1" has K = 1 and no table), from gcl_conv_fwd_launch_shape."""
+    prec, cin, cout, conv, n, form, epi, fl, _nb = case
+    return launch_shape(lib, n, 1 if conv == "k1" else 27, cin, cout, prec, int(form == "planes"), int(epi != "plain"),
+                        int(conv != "k1"), 0, fl if flags is None else flags)
+
+
+def instance_of(lib, case, flags=None):
+    """Name of the kernel instance the dispatcher launches for a case."""
+    s = case_shape(lib, case, flags)
+    pre, e = ("false", "true")[s["pre"]], ("false", "true")[s["epi"]]
+    return {F32: f"k_conv_fwd<{s['nb']}>", DMA_PATH: f"k_conv_fwd_dma<{s['nb']},{pre},{e}>",
+            SPLIT: f"k_conv_fwd_split<{s['nb']},{s['pl']},{pre},{e}>"}[s["path"]]
+
+
+def claimed_instance(case):
+    """The instance a CASES entry claims: its section of the table and its NB column, spelled as a name."""
+    prec, _cin, _cout, _conv, _n, form, epi, flags, nb = case
     pre, e = ("true" if form == "planes" else "false"), ("true" if epi != "plain" else "false")
-    if prec == "f32":
-        return f"k_conv_fwd<{nb}>"
-    if prec == "fp16x3" and not flags & NO_DMA:
-        return f"k_conv_fwd_dma<{nb},{pre},{e}>"
-    return f"k_conv_fwd_split<{nb},{PREC_CODE[prec]},{pre},{e}>"
+    return {"f32": f"k_conv_fwd<{nb}>", "fp16x3": f"k_conv_fwd_dma<{nb},{pre},{e}>" if flags == DMA else
+            f"k_conv_fwd_split<{nb},4,{pre},{e}>"}.get(prec, f"k_conv_fwd_split<{nb},{PREC_CODE[prec]},{pre},{e}>")
 
 
 def full_instance_matrix():
@@ -170,21 +196,40 @@ def layer_rows(stride, transpose, n_fine):
 # without a GPU: the table names the instances it reaches, and reaches all of them
 # ---------------------------------------------------------------------------------------------------------------
 def test_case_table_names_its_kernel_instances_and_covers_the_matrix():
-    """gcl_conv_fwd_nb is host arithmetic: every case's (n_out, cout, prec) selects the NB it claims, every case is ragged,
-    the reached instances are exactly the 37 of the dispatcher, and the band edges of conv_fwd_nb are where the table
-    assumes them (the 256-workgroup rule of small launches and the 513..1024 rule), so that a change of either fails here
-    instead of moving the GPU tests onto other kernels."""
+    """gcl_conv_fwd_launch_shape is host arithmetic, and it is what the dispatcher launches: every case reaches the instance
+    (kernel family, NB, planes, operand form, epilogue) it claims, every case is ragged, the reached instances are exactly
+    the 37 of the dispatcher, and the band edges of conv_fwd_nb are where the table assumes them (the 256-workgroup rule of
+    small launches and the 513..1024 rule), so that a change of either fails here instead of moving the GPU tests onto
+    other kernels."""
     from gcl_amd import _lib
     lib = _lib.load()
     reached, second_form = {}, set()
-    for prec, cin, cout, conv, n, form, epi, flags, nb in CASES:
+    for case in CASES:
+        prec, cin, cout, conv, n, form, epi, flags, nb = case
+        s = case_shape(lib, case)
+        want_path = F32 if prec == "f32" else (DMA_PATH if flags == DMA else SPLIT)
+        assert (s["path"], s["nb"], s["pl"], s["pre"], s["epi"]) == \
+            (want_path, nb, PREC_CODE[prec], int(form == "planes"), int(epi != "plain")), (case, s)
         assert lib.gcl_conv_fwd_nb(n, cout, PREC_CODE[prec]) == nb, (prec, cout, n, nb)
+        # the grid: one workgroup per 128-row tile and block of 32 NB columns; with more than one column block a 1-D grid
+        # of the tiles rounded up to 8 (the exact-f32 kernel keeps the 2-D grid)
+        tiles, cols = (n + 127) // 128, cout // (32 * nb)
+        assert s["block"] == 256 and (s["gx"], s["gy"]) == \
+            ((tiles, cols) if prec == "f32" else (((tiles + 7) // 8 * 8 * cols, 1) if cols > 1 else (tiles, 1))), (case, s)
+        assert s["swz"] == (0 if prec == "f32" else (2 if cols > 1 else 0) | (16 if conv != "k1" else 0)), (case, s)
+        sx = case_shape(lib, case, flags | XCD)       # GCL_CONV_XCD_RANGES: the same instance and grid, another launch order
+        assert sx["swz"] == (0 if prec == "f32" else (2 if cols > 1 else 0) | 1) and \
+            {k: v for k, v in sx.items() if k != "swz"} == {k: v for k, v in s.items() if k != "swz"}, (case, sx)
         assert 1 <= n % 128 <= 31 or 33 <= n % 128 <= 127, n
         assert epi in EPILOGUES and conv in ("s1", "tr2", "k1") and form in ("rows", "planes")
         assert cin % 32 == 0 and cout % 32 == 0
         assert (prec == "fp16x3") == (flags in (DMA, NO_DMA)) and (form == "rows" or prec == "fp16x3")
         assert prec != "f32" or epi == "plain"
-        name = instance_of(prec, form, epi, flags, nb)
+        name = instance_of(lib, case)
+        assert name == claimed_instance(case), (case, name)
+        if prec == "fp16x3":          # the other staging of check (g): the twin instance
+            other = instance_of(lib, case, flags ^ (DMA | NO_DMA))
+            assert other == claimed_instance(case[:7] + (flags ^ (DMA | NO_DMA), nb)) and other != name
         reached[name] = reached.get(name, 0) + 1
         if n % 128 >= 33:
             second_form.add(name.split("<")[0] + ("/" + str(PREC_CODE[prec]) if "split" in name else ""))
@@ -220,6 +265,104 @@ def test_case_table_names_its_kernel_instances_and_covers_the_matrix():
         assert sorted(claims) == sorted(PREC_CODE)
     for nb in (2, 4):       # wide instances in both directions
         assert any(c["fp16x3"] == (nb, nb) for *_, c in LAYER_CASES)
+
+
+def test_launch_shape_pins_the_paths_outside_the_matrix():
+    """The inference kernels of GCL_CONV_TALL, the register-staged twin and the generic kernel: which shapes reach them,
+    with which grid, and where gcl_conv_fwd_groups_scratch_len ends.  Defaults of `shape`: a 128 -> 64 layer of 2835 rows,
+    K = 27 (108 steps per tile), fp16x3 on fp32 rows, sorted table, GCL_CONV_TALL, no scratch."""
+    from gcl_amd import _lib
+    lib = _lib.load()
+    glen = lib.gcl_conv_fwd_groups_scratch_len
+
+    def shape(n=N23, K=27, cin=128, cout=64, prec=4, planes=0, fused=0, table=1, scratch=0, flags=TALL):
+        return launch_shape(lib, n, K, cin, cout, prec, planes, fused, table, scratch, flags)
+
+    def path(**kw):
+        return shape(**kw)["path"]
+    tiles8 = ((N23 + 127) // 128 + 7) // 8 * 8
+    s = shape(scratch=1)          # scratch handed over: four times as many four-wave workgroups + the slab sum
+    assert (s["path"], s["nb"], s["pl"], s["pre"], s["epi"]) == (GROUPS, 2, 4, 0, 0), s
+    assert (s["gx"], s["gy"], s["block"], s["swz"]) == (tiles8 * (64 // 64) * 4, 1, 256, 2 | 16), s
+    assert glen(N23, 27, 128, 64) == 4 * N23 * 64
+    s = shape()                   # no scratch: sixteen waves per workgroup
+    assert (s["path"], s["gx"], s["gy"], s["block"], s["swz"]) == (TALL_PATH, tiles8 * (64 // 64), 1, 1024, 2 | 16), s
+    assert shape(cout=256, scratch=1)["gx"] == tiles8 * 4 * 4 and shape(cout=256)["gx"] == tiles8 * 4
+    assert shape(fused=1)["epi"] == 1 and shape(fused=1, scratch=1)["epi"] == 1
+    # 65536 rows: the last size of the group launches
+    assert glen(65536, 27, 128, 64) == 4 * 65536 * 64 and glen(65537, 27, 128, 64) == 0
+    assert path(n=65536, scratch=1) == GROUPS and path(n=65537, scratch=1) == TALL_PATH and path(n=65537) == TALL_PATH
+    # 108 steps per full tile, K >= 8, Cout a multiple of 64: decided by the layer's shape alone
+    for kw in (dict(cin=96), dict(cout=96), dict(K=8, cin=416), dict(K=7, cin=512), dict(K=1, cin=3456)):
+        assert glen(N23, kw.get("K", 27), kw.get("cin", 128), kw.get("cout", 64)) == 0, kw
+        assert path(**kw) == DMA_PATH and path(scratch=1, **kw) == DMA_PATH, kw
+    assert path(K=8, cin=448) == TALL_PATH and path(K=8, cin=448, scratch=1) == GROUPS and glen(N23, 8, 448, 64) > 0
+    assert path(cin=128, cout=128) == TALL_PATH and path(cin=256, cout=192) == TALL_PATH
+    assert glen(0, 27, 128, 64) == 0 and glen(N23, 28, 128, 64) == 0 and glen(N23, 27, 130, 64) == 0
+    # fp16x3 on fp32 rows with a sorted table only, and not with GCL_CONV_XCD_RANGES; the flag itself
+    for scratch in (0, 1):
+        assert path(planes=1, scratch=scratch) == DMA_PATH and path(flags=TALL | XCD, scratch=scratch) == DMA_PATH
+        assert path(prec=2, scratch=scratch) == SPLIT and path(prec=3, scratch=scratch) == SPLIT
+        assert path(prec=0, scratch=scratch) == F32 and path(table=0, scratch=scratch) == DMA_PATH
+        assert path(flags=0, scratch=scratch) == DMA_PATH and path(flags=DMA, scratch=scratch) == DMA_PATH
+        assert path(flags=TALL | NO_DMA, scratch=scratch) == (GROUPS if scratch else TALL_PATH)
+        assert path(cin=96, flags=TALL | NO_DMA, scratch=scratch) == SPLIT
+    # GCL_CONV_NO_DMA: the register-staged twin; GCL_CONV_DMA changes nothing
+    s = shape(flags=NO_DMA)
+    assert (s["path"], s["pl"], s["nb"], s["block"]) == (SPLIT, 4, lib.gcl_conv_fwd_nb(N23, 64, 4), 256), s
+    assert shape(flags=DMA) == shape(flags=0) and shape(flags=DMA)["path"] == DMA_PATH
+    assert shape(flags=NO_DMA, prec=2) == shape(flags=0, prec=2)
+    # generic shapes: TC = 8 up to Cout = 8, else 16; one thread per row, 256 rows per workgroup
+    for kw, tc in ((dict(cin=32, cout=8), 8), (dict(cin=32, cout=9), 16), (dict(K=28, cin=32, cout=32), 16),
+                   (dict(cin=3, cout=1), 8), (dict(K=125, cin=1, cout=17, prec=0), 16), (dict(cin=48, cout=64), 16)):
+        for flags in (0, TALL, NO_DMA, XCD):
+            s = shape(flags=flags, **kw)
+            assert (s["path"], s["nb"], s["pl"], s["pre"], s["block"], s["swz"]) == (GENERIC, tc, 0, 0, 256, 0), (kw, s)
+            assert (s["gx"], s["gy"]) == ((N23 + 255) // 256, -(-kw["cout"] // tc)), (kw, s)
+    assert path(K=27, cin=32, cout=32, flags=0) == DMA_PATH
+    # arguments the entry itself refuses
+    out = (ctypes.c_int32 * 8)()
+    ok = (N23, 27, 128, 64, 4, 0, 0, 1, 0, 0)
+    assert lib.gcl_conv_fwd_launch_shape(*ok, out) == 0
+    assert lib.gcl_conv_fwd_launch_shape(*ok, None) != 0
+    for i, v in ((0, 0), (1, 0), (1, 126), (2, 0), (3, 0), (4, 1), (4, 5)):
+        assert lib.gcl_conv_fwd_launch_shape(*ok[:i], v, *ok[i + 1:], out) != 0, (i, v)
+    assert lib.gcl_conv_fwd_launch_shape(N23, 27, 128, 64, 2, 1, 0, 1, 0, 0, out) != 0          # planes are fp16x3
+    assert lib.gcl_conv_fwd_launch_shape(N23, 27, 100, 64, 4, 1, 0, 1, 0, 0, out) != 0          # ... of MFMA shapes
+    assert lib.gcl_conv_fwd_launch_shape(N23, 27, 128, 64, 0, 0, 1, 1, 0, 0, out) != 0          # exact f32 has no fused epilogue
+
+
+def test_profile_labels_come_from_the_launch_shape_exports():
+    """MinkowskiEngine/ops.py labels a profiled launch with the instance the library's own dispatcher function names: for
+    every case of this table and of the weight-gradient table (tests/test_gpu_dw_instances.py) the label is the claimed
+    instance, in the spelling profiles/pmc_summary.json is keyed by (a trailing `false` template argument left out)."""
+    import re
+    import test_gpu_dw_instances as DW
+    from gcl_amd import _lib
+    from gcl_amd.MinkowskiEngine import ops
+    lib = _lib.load()
+    for case in CASES:
+        prec, cin, cout, conv, n, form, epi, flags, nb = case
+        got = ops.fwd_instance_name(lib, n, 1 if conv == "k1" else 27, cin, cout, PREC_CODE[prec], form == "planes",
+                                    epi != "plain", conv != "k1", flags=flags)
+        assert got == claimed_instance(case), (case, got)
+    assert ops.fwd_instance_name(lib, N23, 27, 64, 16, 4) == "k_conv_generic"
+    assert ops.fwd_instance_name(lib, N23, 27, 128, 64, 4, fused=True, flags=TALL) == "k_conv_fwd_tall<true>"
+    assert ops.fwd_instance_name(lib, N23, 27, 128, 64, 4, scratch=True, flags=TALL) == "k_conv_groups_sum<false,4>"
+    labels = set()
+    for case in DW.CASES:
+        lname, ca, cb, prec, pl, claim = case[:6]
+        L = DW.pair_list(lname)
+        want = re.sub(r",false>$", ">", claim.split(" ")[0].replace("<false>", ""))
+        got = ops.dw_instance_name(lib, L.K, ca, cb, DW.PREC_CODE[prec], pl, L.side, L.n_sorted(), int(L.seg[-1]))
+        assert got == want, (DW.case_id(case), got, want)
+        labels.add(got)
+    # today's spellings, and the one label that changed: a range-grouped launch under its own name
+    assert {"k_conv_bwd_weight_split<64,64,4,true>", "k_conv_bwd_weight_split<64,64,4,false>", "k_conv_bwd_weight_wg128",
+            "k_conv_bwd_weight<64,64>", "k_conv_bwd_weight_generic", "k_conv_bwd_weight_split<64,64,4,false,true>",
+            "k_bwd_weight_reduce"} <= labels, sorted(labels)
+    assert ops.fwd_instance_name(lib, N23, 27, 128, 128, 4, planes=True) == "k_conv_fwd_dma<1,true,false>"
+    assert ops.fwd_instance_name(lib, N161, 27, 128, 128, 4, planes=True) == "k_conv_fwd_dma<2,true,false>"
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -397,7 +540,7 @@ def test_conv_fwd_instance(case):
         _T0.append(time.time())
     lib = _lib.require_gpu()
     code = PREC_CODE[prec]
-    name = instance_of(prec, form, epi, flags, nb)
+    name = instance_of(lib, case)
     p = problem(n, conv, cin, cout)
     n_out, n_tiles = p.n_out, (p.n_out + 127) // 128
     assert n_out == n and lib.gcl_conv_fwd_nb(n_out, cout, code) == nb and lib.gcl_conv_fwd_nb(n_out, 32, code) == 1
@@ -482,7 +625,7 @@ def test_conv_fwd_instance(case):
 
     # (g) LDS-DMA staging against register staging
     if prec == "fp16x3":
-        other = instance_of(prec, form, epi, flags ^ (DMA | NO_DMA), nb)
+        other = instance_of(lib, case, flags ^ (DMA | NO_DMA))
         assert other != name
         yo, so, ao = p.run(prec, form, epi, flags ^ (DMA | NO_DMA))
         assert torch.equal(yo, y), f"{name} against {other}: {where_differs(yo, y)}"
