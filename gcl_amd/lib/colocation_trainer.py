@@ -774,12 +774,21 @@ class FinestContrastiveLossTrainer:
         dist = torch.sqrt(((moved - xyz1) ** 2).sum(1) + 1e-6)
         return (dist < thresh).float().mean().item()
 
-    def _valid_epoch(self, val_batches, val_max_iter=None):
+    def _valid_epoch(self, val_batches, val_max_iter=None, on_device=False, batch_pairs=8):
         """``_valid_epoch`` (lib/colocation_trainer.py:306-379) over ``val_batches`` (pair dicts of
         ``collate_debug_pair_fn``: sinput{0,1}_C / _F, pcd0 / pcd1, T_gt): eval-mode features of both clouds (ONE
         forward pass per pair: bitwise equal to the reference's two, ``scripts.test_kitti.forward_clouds``), feature
         1-NN correspondences on 5000-row subsamples, ``est_quad_linear_robust``, and the five meters the reference
-        returns.  The dataset shell (``reset_seed``, timers, logging) stays with the caller."""
+        returns.  The dataset shell (``reset_seed``, timers, logging) stays with the caller.
+        ``on_device=True`` runs the same epoch through ``gcl_amd.lib.validation.validate_pairs``: ``batch_pairs`` pairs per
+        forward pass, pose and meters in two launches per chunk, no host trip per pair; same draws under one seed."""
+        if on_device:
+            from gcl_amd.lib.validation import validate_pairs
+            limit = getattr(self.config, "val_max_iter", -1) if val_max_iter is None else val_max_iter
+            with torch.cuda.device(self.device):
+                return validate_pairs(self.model, val_batches, val_max_iter=limit, batch_pairs=batch_pairs,
+                                      subsample_size=5000, hit_ratio_thresh=getattr(self.config, "hit_ratio_thresh", 0.3),
+                                      nn_max_n=getattr(self.config, "nn_max_n", 500))[0]
         from gcl_amd.lib.metrics import corr_dist
         from gcl_amd.scripts.test_kitti import AverageMeter, forward_clouds
         from gcl_amd.util.transform_estimation import est_quad_linear_robust

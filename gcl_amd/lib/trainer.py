@@ -458,6 +458,18 @@ class ContrastiveLossTrainer:
                 yield self.train_step(grp if k > 1 else grp[0])
                 grp = []
 
+    def _valid_epoch(self, val_batches, val_max_iter=None, batch_pairs=8):
+        """``_valid_epoch`` of lib/trainer.py (the same step as the co-location trainer's) on the device:
+        ``gcl_amd.lib.validation.validate_pairs`` over ``val_batches`` (pair dicts with sinput{0,1}_C / _F, pcd0 / pcd1,
+        T_gt), ``batch_pairs`` pairs per forward pass.  Returns the reference's dict of meters; leaves the model in eval
+        mode, as the reference does (``train_step`` switches back)."""
+        from gcl_amd.lib.validation import validate_pairs
+        limit = getattr(self.config, "val_max_iter", -1) if val_max_iter is None else val_max_iter
+        with torch.cuda.device(self.device):
+            return validate_pairs(self.model, val_batches, val_max_iter=limit, batch_pairs=batch_pairs, subsample_size=5000,
+                                  hit_ratio_thresh=getattr(self.config, "hit_ratio_thresh", 0.3),
+                                  nn_max_n=getattr(self.config, "nn_max_n", 500))[0]
+
 
 class HardestContrastiveLossTrainer(ContrastiveLossTrainer):
     """lib/trainer.py:408-540: positives against the hardest negatives (``contrastive_hardest_negative_loss``)."""

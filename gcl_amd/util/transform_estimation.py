@@ -66,3 +66,33 @@ def est_quad_linear_robust(pts0, pts1, weight=None):
         w = compute_weights(cur, q, par)
         trans = step @ trans
     return trans.to(pts0.dtype)
+
+
+def est_quad_linear_robust_batch(src, tgt, offsets, weight=None):
+    """``est_quad_linear_robust`` for a ragged batch of pairs in ONE launch (``gcl_irls_pose_batch``, csrc/valpose.hip): the
+    same algorithm in fp64 on the device.  ``src`` / ``tgt``: device float32 [total, 3], the matched points of all pairs;
+    ``offsets``: int64 [B + 1] (device tensor, or a host sequence that is uploaded without a sync); ``weight``: optional
+    device float32 [total].  Returns ``(T, status)`` on the device: float64 [B, 4, 4] and int32 [B] -- status 1 marks a pair
+    whose system was singular (or that has no rows); its T is the identity, where the host function raises."""
+    from gcl_amd import _lib
+    from gcl_amd.lib.eval import host_to_device
+    lib = _lib.require_gpu()
+    src, tgt = src.detach().contiguous(), tgt.detach().contiguous()
+    if src.dim() != 2 or src.shape[1] != 3 or tgt.shape != src.shape:
+        raise ValueError(f"est_quad_linear_robust_batch takes two [total, 3] arrays, got {tuple(src.shape)} and {tuple(tgt.shape)}")
+    if not torch.is_tensor(offsets):
+        offsets = host_to_device(torch.as_tensor([int(o) for o in offsets], dtype=torch.int64), src.device)
+    B, total = offsets.numel() - 1, src.shape[0]
+    if weight is not None:
+        weight = weight.detach().reshape(-1).contiguous()
+        if weight.numel() != total:
+            raise ValueError(f"est_quad_linear_robust_batch: {weight.numel()} weights for {total} rows")
+    n_scratch = lib.gcl_irls_pose_scratch_len(total)
+    scratch = torch.empty(n_scratch, dtype=torch.float64, device=src.device) if n_scratch else None
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=src.device)
+    status = torch.empty(B, dtype=torch.int32, device=src.device)
+    _lib.check(lib.gcl_irls_pose_batch(_lib.ptr(src, torch.float32), _lib.ptr(tgt, torch.float32), total,
+                                       _lib.ptr(offsets, torch.int64), B, _lib.ptr(weight, torch.float32), 20, 1.0, 5,
+                                       _lib.ptr(scratch), _lib.ptr(T), _lib.ptr(status), _lib.stream()),
+               "gcl_irls_pose_batch")          # 20 steps, par 1.0 halved every 5: the host function's constants
+    return T, status

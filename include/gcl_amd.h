@@ -1018,6 +1018,39 @@ int gcl_fpfh_spfh(const float* xyz, const float* normals, int64_t n, const int32
 int gcl_fpfh_combine(const float* xyz, const float* spfh, int64_t n, const int32_t* idx, const int32_t* cnt, int32_t max_nn,
                      int32_t normalize, float* fpfh, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Validation step for a ragged batch of B pairs (csrc/valpose.hip; lib/colocation_trainer.py:306-379 runs it once per
+ * pair on the host).  src / tgt (float [total, 3]) are the matched points of all pairs, pair b owning the rows
+ * offsets[b] .. offsets[b + 1] - 1 (DEVICE int64 [B + 1], ascending, within [0, total]); a pair whose offsets fall outside
+ * that range is treated as empty.  One launch each, no atomics, nothing read back: a pair's numbers are bitwise the same on
+ * every run and whatever else the batch holds.
+ *
+ * gcl_irls_pose_batch: the algorithm of util/transform_estimation.py:97-126 (est_quad_linear_robust) in fp64: n_iter (20)
+ * re-weighted Gauss-Newton steps on w^2 [-[p]x | I] x = w^2 (q - p) through the 6 x 6 normal equations (partial
+ * pivoting), the step applied as Rz Ry Rx + t, w = par / (|p - q| + par) with par = par0 (1.0) halved at every multiple
+ * of halve_every (5) steps, trans = step trans.  weight (float [total], NULL: ones) are the weights of the first step.
+ * T (double [B, 16], row-major 4 x 4) maps src onto tgt; status (int32 [B]) is 0, or 1 when a pair is empty or a step's
+ * system had a zero or non-finite pivot (below 2^-40 of the largest entry of its column counts as zero) or a non-finite
+ * solution: T is the identity then.
+ * Scratch: gcl_irls_pose_scratch_len(total) = 3 * total doubles (the current points); NULL only when total = 0.
+ *
+ * gcl_val_stats_batch: out (double [B, 6]) = loss, rte, rre, hit_ratio, n_corr, status per pair.
+ *   loss       mean over the pair's rows of xyz0 (float [total0, 3], rows offsets0[b] .. offsets0[b + 1] - 1) of
+ *              min(|T_est x - T_gt x|, max_dist)                                        (lib/metrics.py:13-19, corr_dist)
+ *   rte        |t_est - t_gt|;   rre  arccos((trace(R_est^T R_gt) - 1) / 2), NOT clamped: NaN passes through
+ *   hit_ratio  mean over the pair's correspondences of sqrt(|T_gt a - b|^2 + 1e-6) < thresh      (:397-400); the count
+ *              is exact and the quotient rounded to float32, which is the reference's float32 mean bit for bit
+ *   status     a copy of status[b] (NULL: 0).  Means over zero rows are 0.
+ * T_est / T_gt are double [B, 16]; all arithmetic is fp64, sums in a fixed order.  No scratch.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t gcl_irls_pose_scratch_len(int64_t total);
+int gcl_irls_pose_batch(const float* src, const float* tgt, int64_t total, const int64_t* offsets, int32_t B,
+                        const float* weight, int32_t n_iter, double par0, int32_t halve_every, double* scratch, double* T,
+                        int32_t* status, void* stream);
+int gcl_val_stats_batch(const float* src, const float* tgt, int64_t total, const int64_t* offsets, const float* xyz0,
+                        int64_t total0, const int64_t* offsets0, int32_t B, const double* T_est, const double* T_gt,
+                        const int32_t* status, double max_dist, double thresh, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
