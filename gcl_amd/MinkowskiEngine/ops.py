@@ -111,7 +111,6 @@ def tensor_amax(lib, t):
 
 
 PRESPLIT_MIN_C = int(os.environ.get("GCL_PRESPLIT_MIN_C", "128"))     # operands at least this wide are pre-split
-BN_PLANES = os.environ.get("GCL_BN_PLANES", "1") != "0"                  # BatchNorm bound mode (csrc/plan.hip bound_mode)
 
 
 def planes_of(lib, t, amax):
@@ -495,7 +494,7 @@ class _BatchNormFn(torch.autograd.Function):
                 # plane image, whose scale the native plan fixes BEFORE the apply pass from a bound of max|y| -- the same
                 # launch with the same arguments here, so that both paths hand their consumers the same slot value
                 res_amax = known_amax(residual) if residual is not None else None
-                bound = (BN_PLANES and PRECISION == "fp16x3" and c >= PRESPLIT_MIN_C and c % 32 == 0
+                bound = (PRECISION == "fp16x3" and c >= PRESPLIT_MIN_C and c % 32 == 0
                          and (residual is None or res_amax is not None))
                 if bound:
                     bound_slot = amax_slot(dev)

@@ -534,9 +534,6 @@ __device__ __forceinline__ void row_masks_body(const int* __restrict__ tbl, int 
   keys[v] = m;
   vals[v] = (int)v;
 }
-__global__ void k_row_masks(const int* __restrict__ tbl, int K, long long n, unsigned* keys, int* vals) {
-  row_masks_body(tbl, K, n, keys, vals, blockIdx.x);
-}
 
 // bit_count[k] (32 zero-initialised ints) += number of rows whose mask has offset k.  A small fixed grid walks the
 // masks, every thread counts in registers, the workgroup adds up in LDS and issues ONE integer atomic per offset
@@ -564,19 +561,17 @@ __device__ __forceinline__ void mask_bit_count_body(const unsigned* __restrict__
   __syncthreads();
   if ((int)threadIdx.x < K && tot[threadIdx.x]) atomicAdd(&bit_count[threadIdx.x], tot[threadIdx.x]);
 }
-__global__ void __launch_bounds__(256) k_mask_bit_count(const unsigned* __restrict__ keys, long long n, int K, int* bit_count) {
-  mask_bit_count_body(keys, n, K, bit_count, blockIdx.x, gridDim.x);
-}
 
 // Sort key = the mask with its bits re-ordered by how often each offset occurs in THIS table: the rarest offset
 // becomes the most significant bit, the most frequent one the least significant (ties: lower offset index lower).
 // Rows that own a rare offset then sit together, so the unit that offset costs is shared by a whole tile, while the
 // trailing (frequent) bits are set in most rows anyway.  Measured on the KITTI batch against the offset-index order:
 // 7.75 vs 8.26 units per 32-row tile at tensor stride 1, 9.88 vs 10.99 at stride 4, 11.41 vs 13.11 at stride 8
-// (exact sparse work: 6.3 / 7.3 / 7.7).  pos[k] = key bit of offset k, written for k_tile_masks.
-__device__ __forceinline__ void mask_keys_body(unsigned* keys, long long n, int K, const int* __restrict__ bit_count,
-                                               int* pos_out, unsigned bx) {
-  __shared__ int pos[32];
+// (exact sparse work: 6.3 / 7.3 / 7.7).
+// pos[k] (32 ints of LDS) = key bit of offset k = the number of offsets with a larger count, or an equal count and a lower
+// index; the table's first block also writes it to pos_out, for k_tile_masks_multi.  Ends with a barrier.
+__device__ __forceinline__ void mask_key_positions(const int* __restrict__ bit_count, int K, int* pos, int* pos_out,
+                                                   unsigned bx) {
   if (threadIdx.x < 32) {
     const int k = threadIdx.x;
     int p = 0;
@@ -591,6 +586,11 @@ __device__ __forceinline__ void mask_keys_body(unsigned* keys, long long n, int 
     if (bx == 0 && k < K) pos_out[k] = p;
   }
   __syncthreads();
+}
+__device__ __forceinline__ void mask_keys_body(unsigned* keys, long long n, int K, const int* __restrict__ bit_count,
+                                               int* pos_out, unsigned bx) {
+  __shared__ int pos[32];
+  mask_key_positions(bit_count, K, pos, pos_out, bx);
   long long v = (long long)bx * blockDim.x + threadIdx.x;
   if (v >= n) return;
   const unsigned m = keys[v];
@@ -599,10 +599,6 @@ __device__ __forceinline__ void mask_keys_body(unsigned* keys, long long n, int 
   // (taking the key's rank in the reflected Gray-code sequence would save another 2 - 3 % of the units -- measured --
   // but its pseudo-random low digits turn every radix scatter into 64 single-row writes per wave: +1 .. 2 ms per step)
   keys[v] = key;
-}
-__global__ void __launch_bounds__(256) k_mask_keys(unsigned* keys, long long n, int K, const int* __restrict__ bit_count,
-                                                   int* pos_out) {
-  mask_keys_body(keys, n, K, bit_count, pos_out, blockIdx.x);
 }
 
 __device__ __forceinline__ void radix_hist_body(const unsigned* __restrict__ keys, long long n, int shift, int nblk, int* hist,
@@ -618,10 +614,6 @@ __device__ __forceinline__ void radix_hist_body(const unsigned* __restrict__ key
   }
   __syncthreads();
   for (int d = lane; d < 256; d += 64) hist[(long long)d * nblk + bx] = cnt[d];
-}
-__global__ void __launch_bounds__(64) k_radix_hist(const unsigned* __restrict__ keys, long long n, int shift,
-                                                   int nblk, int* hist) {
-  radix_hist_body(keys, n, shift, nblk, hist, blockIdx.x);
 }
 
 // one workgroup per digit d: within[d][b] = sum_{b' < b} hist[d][b'], total[d] = sum_b hist[d][b]  (the digit bases,
@@ -651,10 +643,6 @@ __device__ __forceinline__ void radix_digit_scan_body(const int* __restrict__ hi
     run += h[b];
   }
   if (t == 255) total[d] = part[255];
-}
-__global__ void __launch_bounds__(256) k_radix_digit_scan(const int* __restrict__ hist, int nblk, int* within,
-                                                          int* total) {
-  radix_digit_scan_body(hist, nblk, within, total, blockIdx.x);
 }
 
 __device__ __forceinline__ void radix_scatter_body(const unsigned* __restrict__ keys, const int* __restrict__ vals,
@@ -705,80 +693,6 @@ __device__ __forceinline__ void radix_scatter_body(const unsigned* __restrict__ 
     }
   }
 }
-__global__ void __launch_bounds__(64) k_radix_scatter(const unsigned* __restrict__ keys, const int* __restrict__ vals,
-                                                      long long n, int shift, int nblk,
-                                                      const int* __restrict__ within, const int* __restrict__ total,
-                                                      unsigned* keys_out, int* vals_out) {
-  radix_scatter_body(keys, vals, n, shift, nblk, within, total, keys_out, vals_out, blockIdx.x);
-}
-
-// Windowed variant: rows are mask-sorted only INSIDE windows of WIN consecutive rows of the loader's order, which is
-// spatially coherent (scan order) -- a wave tile then gathers from a compact region (L2 reuse of the gathered rows)
-// at the price of more distinct masks per tile.  One workgroup sorts one window in LDS (bitonic on (mask, row)
-// pairs: unique keys, so the result equals a stable sort); no global passes.
-template <int WIN>
-__global__ void __launch_bounds__(256) k_window_sort(const int* __restrict__ tbl, int K, long long n, int* order,
-                                                     unsigned* keys_sorted, const int* __restrict__ pre) {
-  __shared__ unsigned long long kv[WIN];
-  const long long base = (long long)blockIdx.x * WIN;
-  for (int e = threadIdx.x; e < WIN; e += 256) {
-    long long v = base + e;
-    unsigned long long key = ~0ull;            // padding sorts last
-    if (v < n) {
-      const long long row = pre ? pre[v] : v;  // windows of a spatial pre-order (gcl_spatial_order) or of the row order
-      unsigned m = 0;
-      for (int k = 0; k < K; ++k) m |= (tbl[(long long)k * n + row] >= 0 ? 1u : 0u) << k;
-      key = ((unsigned long long)m << 32) | (unsigned)e;
-    }
-    kv[e] = key;
-  }
-  __syncthreads();
-  for (int size = 2; size <= WIN; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int e = threadIdx.x; e < WIN / 2; e += 256) {
-        int lo = 2 * e - (e & (stride - 1));   // index of the lower element of the pair
-        int hi = lo + stride;
-        bool up = ((lo & size) == 0);
-        unsigned long long a = kv[lo], b = kv[hi];
-        if ((a > b) == up) {
-          kv[lo] = b;
-          kv[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (int e = threadIdx.x; e < WIN; e += 256) {
-    long long j = base + e;
-    if (j < n) {
-      unsigned long long key = kv[e];
-      const long long v = base + (unsigned)(key & 0xffffffffu);
-      order[j] = pre ? pre[v] : (int)v;
-      keys_sorted[j] = (unsigned)(key >> 32);
-    }
-  }
-}
-
-// 16-bit spatial key of a row: cloud id (5 bits, wraps) above an 11-bit Morton code of its cell -- 16 x 16 voxels in x / y
-// (4 bits each: 256 voxels before the code wraps), 4 voxels in z (3 bits) -- so that rows close in space get close keys.
-// A LOCALITY heuristic only (which rows run together on a CU / XCD and re-use each other's gathered neighbours in L2):
-// results never depend on it.
-__global__ void k_spatial_keys(const int4* __restrict__ coords, long long n, int tstride, unsigned* keys, int* vals) {
-  long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n) return;
-  const int4 c = coords[v];
-  const unsigned cx = (unsigned)((c.y / tstride + 4096) >> 4), cy = (unsigned)((c.z / tstride + 4096) >> 4),
-                 cz = (unsigned)((c.w / tstride + 4096) >> 2);
-  unsigned m = 0;
-#pragma unroll
-  for (int b = 3; b >= 0; --b) {       // interleaved from the most significant bit: coarse cells first
-    m = (m << 1) | ((cx >> b) & 1u);
-    m = (m << 1) | ((cy >> b) & 1u);
-    if (b < 3) m = (m << 1) | ((cz >> b) & 1u);
-  }
-  keys[v] = (((unsigned)c.x & 31u) << 11) | (m & 2047u);
-  vals[v] = (int)v;
-}
 
 // tile_mask (optional): an offset missing from a 32-row tile's mask is -1 for all of its rows by definition -- written
 // without the (scattered, 4-byte) read of the source table: ~19 of 27 offsets on the KITTI batch
@@ -790,12 +704,8 @@ __device__ __forceinline__ void permute_table_body(const int* __restrict__ tbl, 
   if (!tile_mask || ((tile_mask[j >> 5] >> k) & 1)) v = tbl[(long long)k * n + order[j]];
   tbl_sorted[(long long)k * n + j] = v;
 }
-__global__ void k_permute_table(const int* __restrict__ tbl, const int* __restrict__ order, long long n,
-                                int* tbl_sorted, const int* __restrict__ tile_mask) {
-  permute_table_body(tbl, order, n, tbl_sorted, tile_mask, blockIdx.x, (int)blockIdx.y);
-}
 
-// pos (optional): the keys are masks with bit k moved to pos[k] (k_mask_keys); the tile mask is returned in offset order.
+// pos (optional): the keys are masks with bit k moved to pos[k] (mask_key_positions); the tile mask is returned in offset order.
 // Lane = row (coalesced key reads), OR over the 32 lanes of a tile by butterfly shuffles.
 __device__ __forceinline__ void tile_masks_body(const unsigned* __restrict__ keys_sorted, long long n, long long n_tiles,
                                                 int* tile_mask, const int* __restrict__ pos, int K, unsigned bx) {
@@ -812,10 +722,6 @@ __device__ __forceinline__ void tile_masks_body(const unsigned* __restrict__ key
     m = u;
   }
   tile_mask[t] = (int)m;
-}
-__global__ void __launch_bounds__(256) k_tile_masks(const unsigned* __restrict__ keys_sorted, long long n, long long n_tiles,
-                                                    int* tile_mask, const int* __restrict__ pos, int K) {
-  tile_masks_body(keys_sorted, n, n_tiles, tile_mask, pos, K, blockIdx.x);
 }
 
 // The 3^3 stride-1 map of a level from its 5^3 stride-1 map: offset (dx, dy, dz) in {-1, 0, 1}^3 is row
@@ -871,10 +777,10 @@ __global__ void __launch_bounds__(256) k_not_ones_rows(const int* __restrict__ c
   rows[v] = (b >= 0 && b < n_cloud) ? cloud[b] : 1;
 }
 
-// ---- the same mask sort for SEVERAL tables per launch (gcl_table_sort_multi) --------------------------------------
-// blockIdx.y (permute: z) = table; a table's blocks beyond its own grid return at once.  Same bodies, same results: what
-// changes is the number of launches -- a network's 12 tables take 14 launches instead of 168, which is what a
-// single-cloud inference pass (a chain of tiny dependent launches) and the trainer's map stream are made of.
+// ---- the mask sort's kernels: SEVERAL tables per launch (gcl_table_sort_multi) ------------------------------------
+// blockIdx.y (permute: z) = table; a table's blocks beyond its own grid return at once.  A network's 12 tables take 14
+// launches instead of 168, which is what a single-cloud inference pass (a chain of tiny dependent launches) and the
+// trainer's map stream are made of.
 constexpr int SORT_MAX_JOBS = 16;
 struct SortJob {
   const int* tbl;
@@ -912,20 +818,7 @@ __global__ void __launch_bounds__(256) k_row_masks_keys_multi(SortJobs J) {
   const SortJob& q = J.j[blockIdx.y];
   if ((long long)blockIdx.x * 256 >= q.n) return;
   __shared__ int pos[32];
-  if (threadIdx.x < 32) {
-    const int k = threadIdx.x;
-    int p = 0;
-    if (k < q.K) {
-      const int ck = q.bit_count[k];
-      for (int j = 0; j < q.K; ++j) {
-        const int cj = q.bit_count[j];
-        p += (cj > ck || (cj == ck && j < k)) ? 1 : 0;
-      }
-    }
-    pos[k] = p;
-    if (blockIdx.x == 0 && k < q.K) q.key_pos[k] = p;
-  }
-  __syncthreads();
+  mask_key_positions(q.bit_count, q.K, pos, q.key_pos, blockIdx.x);
   const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
   if (v >= q.n) return;
   unsigned key = 0;
@@ -1142,19 +1035,15 @@ int gcl_kernel_map(const int32_t* coords_out, int64_t n_out, const int64_t* tabl
   // k_count_reduce launch, `scratch` unused
   // (64 blocks = 16 384 rows.  The K counters share two cache lines: at 256 / 1024 blocks the atomics cost more than the
   // launch they save -- eight pairs per pass 97.4 -> 89 - 96 / 87 - 94 M voxels/s, the training step 11.94 -> 12.0 / 12.35 ms)
-  static const long long acc_max = [] { const char* e = getenv("GCL_MAP_ACC_MAX_BLOCKS"); return e ? atoll(e) : 64ll; }();
-  const int acc = ((same_map & 4) != 0 && cdiv(n_out, 256) <= acc_max) ? 1 : 0;
+  constexpr long long MAP_ACC_MAX_BLOCKS = 64;
+  const int acc = ((same_map & 4) != 0 && cdiv(n_out, 256) <= MAP_ACC_MAX_BLOCKS) ? 1 : 0;
   const bool prefilled = (same_map & 8) != 0;      // bit 3: nbr / nbr_t hold -1 everywhere on entry (one fill for all maps)
   same_map &= 1;
   GCL_CHECK_ARG(!same_map || (nbr_t == nullptr && n_in == n_out), "gcl_kernel_map: same_map excludes nbr_t");
   hipStream_t st = (hipStream_t)stream;
   int K = ks * ks * ks;
   int nblk = (int)cdiv(n_out, 256);
-  static const int kpt = [] {      // GCL_MAP_KPT = 1 | 2 | 4: offsets per thread of the lookup kernels
-    const char* e = getenv("GCL_MAP_KPT");
-    const int v = e ? atoi(e) : 4;
-    return (v == 1 || v == 2) ? v : 4;
-  }();
+  constexpr int KPT = 4;      // offsets per thread of the lookup kernels (1 and 2 measured slower, round 5)
   if (bitmap && !bitmap_valid) {
     fill32(bitmap, BITMAP_WORDS, 0u, st);
     hipLaunchKernelGGL(k_bitmap_fill, dim3((unsigned)cdiv(cap_in, 256)), dim3(256), 0, st, (const Slot*)table_in,
@@ -1163,33 +1052,15 @@ int gcl_kernel_map(const int32_t* coords_out, int64_t n_out, const int64_t* tabl
   if (same_map) {
     if (K > 1 && !prefilled)
       fill32(nbr + (size_t)(K / 2 + 1) * n_out, (long long)(K / 2) * n_out, 0xFFFFFFFFu, st);
-    if (kpt == 4)
-      hipLaunchKernelGGL(k_kernel_map_sym<4>, dim3(nblk, (unsigned)cdiv(K / 2 + 1, 4)), dim3(256), 0, st, (const int4*)coords_out,
-                         (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step,
-                         nbr, acc ? counts : scratch, acc);
-    else if (kpt == 2)
-      hipLaunchKernelGGL(k_kernel_map_sym<2>, dim3(nblk, (unsigned)cdiv(K / 2 + 1, 2)), dim3(256), 0, st, (const int4*)coords_out,
-                         (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step,
-                         nbr, acc ? counts : scratch, acc);
-    else
-      hipLaunchKernelGGL(k_kernel_map_sym<1>, dim3(nblk, K / 2 + 1), dim3(256), 0, st, (const int4*)coords_out,
-                         (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step,
-                         nbr, acc ? counts : scratch, acc);
+    hipLaunchKernelGGL(k_kernel_map_sym<KPT>, dim3(nblk, (unsigned)cdiv(K / 2 + 1, KPT)), dim3(256), 0, st,
+                       (const int4*)coords_out, (long long)n_out, (const Slot*)table_in, (long long)cap_in,
+                       (const unsigned*)bitmap, ks, step, nbr, acc ? counts : scratch, acc);
     if (!acc) hipLaunchKernelGGL(k_count_reduce, dim3(K / 2 + 1), dim3(256), 0, st, (const int*)scratch, nblk, K, 1, counts);
   } else {
     if (nbr_t && !prefilled) fill32(nbr_t, (long long)K * n_in, 0xFFFFFFFFu, st);
-    if (kpt == 4)
-      hipLaunchKernelGGL(k_kernel_map<4>, dim3(nblk, (unsigned)cdiv(K, 4)), dim3(256), 0, st, (const int4*)coords_out,
-                         (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step, nbr,
-                         nbr_t, (long long)n_in, acc ? counts : scratch, acc);
-    else if (kpt == 2)
-      hipLaunchKernelGGL(k_kernel_map<2>, dim3(nblk, (unsigned)cdiv(K, 2)), dim3(256), 0, st, (const int4*)coords_out,
-                         (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step, nbr,
-                         nbr_t, (long long)n_in, acc ? counts : scratch, acc);
-    else
-      hipLaunchKernelGGL(k_kernel_map<1>, dim3(nblk, K), dim3(256), 0, st, (const int4*)coords_out, (long long)n_out,
-                         (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step, nbr, nbr_t,
-                         (long long)n_in, acc ? counts : scratch, acc);
+    hipLaunchKernelGGL(k_kernel_map<KPT>, dim3(nblk, (unsigned)cdiv(K, KPT)), dim3(256), 0, st, (const int4*)coords_out,
+                       (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step, nbr,
+                       nbr_t, (long long)n_in, acc ? counts : scratch, acc);
     if (!acc) hipLaunchKernelGGL(k_count_reduce, dim3(K), dim3(256), 0, st, (const int*)scratch, nblk, K, 0, counts);
   }
   GCL_CHECK_LAUNCH();
@@ -1220,108 +1091,6 @@ int64_t gcl_table_sort_scratch_len(int64_t n) {
   long long nblk = cdiv(n, RS_BLOCK);
   long long hist = 256 * nblk;
   return 4 * n + 2 * hist + cdiv(hist, SCAN_B) + 64 + 256 + 64;   // keys/vals ping-pong, hist, within, digit totals, offset counts + key bit positions
-}
-
-int gcl_spatial_order(const int32_t* coords, int64_t n, int32_t tensor_stride, int32_t* scratch, int32_t* order,
-                      void* stream) {
-  GCL_CHECK_ARG(coords && scratch && order, "gcl_spatial_order: null pointer");
-  GCL_CHECK_ARG(n > 0 && tensor_stride >= 1, "gcl_spatial_order: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = (int)cdiv(n, RS_BLOCK);
-  const long long hist_len = 256ll * nblk;
-  unsigned* ka = (unsigned*)scratch;
-  unsigned* kb = ka + n;
-  int* va = scratch + 2 * n;
-  int* vb = scratch + 3 * n;
-  int* hist = scratch + 4 * n;
-  int* offs = hist + hist_len;
-  int* bs = offs + hist_len;
-  hipLaunchKernelGGL(k_spatial_keys, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, (const int4*)coords, (long long)n,
-                     tensor_stride, ka, va);
-  for (int p = 0; p < 2; ++p) {      // 16-bit keys: two stable 8-bit passes
-    hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(64), 0, st, (const unsigned*)ka, (long long)n, 8 * p, nblk, hist);
-    hipLaunchKernelGGL(k_radix_digit_scan, dim3(256), dim3(256), 0, st, (const int*)hist, nblk, offs, bs);
-    int* vout = (p == 1) ? order : vb;
-    hipLaunchKernelGGL(k_radix_scatter, dim3(nblk), dim3(64), 0, st, (const unsigned*)ka, (const int*)va, (long long)n,
-                       8 * p, nblk, (const int*)offs, (const int*)bs, kb, vout);
-    unsigned* tk = ka; ka = kb; kb = tk;
-    int* tv = va; va = vb; vb = tv;
-  }
-  GCL_CHECK_LAUNCH();
-  return GCL_OK;
-}
-
-int gcl_table_sort(const int32_t* tbl, int32_t K, int64_t n, int32_t window, int32_t* scratch, int32_t* order,
-                   int32_t* tbl_sorted, int32_t* tile_mask, void* stream) {
-  return gcl_table_sort_pre(tbl, K, n, window, nullptr, scratch, order, tbl_sorted, tile_mask, stream);
-}
-
-int gcl_table_sort_pre(const int32_t* tbl, int32_t K, int64_t n, int32_t window, const int32_t* pre, int32_t* scratch,
-                       int32_t* order, int32_t* tbl_sorted, int32_t* tile_mask, void* stream) {
-  GCL_CHECK_ARG(tbl && scratch && order && tbl_sorted && tile_mask, "gcl_table_sort: null pointer");
-  GCL_CHECK_ARG(!pre || window, "gcl_table_sort_pre: a pre-order needs window = 2048 or 4096");
-  GCL_CHECK_ARG(K >= 1 && K <= 27 && n > 0, "gcl_table_sort: K must be <= 27 (3^3 kernels), n > 0");
-  GCL_CHECK_ARG(window == 0 || window == 2048 || window == 4096, "gcl_table_sort: window must be 0, 2048 or 4096");
-  hipStream_t st = (hipStream_t)stream;
-  unsigned* ka = (unsigned*)scratch;
-  int* bit_count = nullptr;
-  int* key_pos = nullptr;
-  if (window) {
-    if (window == 2048)
-      hipLaunchKernelGGL(k_window_sort<2048>, dim3((unsigned)cdiv(n, 2048)), dim3(256), 0, st, tbl, K, (long long)n,
-                         order, ka, pre);
-    else
-      hipLaunchKernelGGL(k_window_sort<4096>, dim3((unsigned)cdiv(n, 4096)), dim3(256), 0, st, tbl, K, (long long)n,
-                         order, ka, pre);
-  } else {
-    int nblk = (int)cdiv(n, RS_BLOCK);
-    long long hist_len = 256ll * nblk;
-    unsigned* kb = ka + n;
-    int* va = scratch + 2 * n;
-    int* vb = scratch + 3 * n;
-    int* hist = scratch + 4 * n;
-    int* offs = hist + hist_len;
-    int* bs = offs + hist_len;
-    static const int freq_order = [] { const char* e = getenv("GCL_SORT_FREQ_ORDER"); return e ? atoi(e) : 1; }();
-    if (freq_order) {
-      bit_count = scratch + gcl_table_sort_scratch_len(n) - 64;
-      key_pos = bit_count + 32;
-      GCL_CHECK_HIP(hipMemsetAsync(bit_count, 0, 32 * sizeof(int32_t), st));
-    }
-    hipLaunchKernelGGL(k_row_masks, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, tbl, K, (long long)n, ka, va);
-    if (freq_order) {
-      hipLaunchKernelGGL(k_mask_bit_count, dim3(512), dim3(256), 0, st, (const unsigned*)ka, (long long)n, K, bit_count);
-      hipLaunchKernelGGL(k_mask_keys, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, ka, (long long)n, K,
-                         (const int*)bit_count, key_pos);
-    }
-    int passes = (K + 7) / 8;
-    // at most three 8-bit passes: a 27-offset mask is ordered by its 24 most significant bits (offsets 3..26); the
-    // three dropped bits only permute rows inside runs that already share 24 bits (measured: MFMA work unchanged,
-    // one pass of ~45 us per table saved)
-    static const int max_passes = [] { const char* e = getenv("GCL_SORT_PASSES"); int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
-    int base = 0;
-    if (passes > max_passes) {
-      base = K - 8 * max_passes;
-      passes = max_passes;
-    }
-    for (int p = 0; p < passes; ++p) {
-      hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(64), 0, st, (const unsigned*)ka, (long long)n, base + 8 * p, nblk, hist);
-      GCL_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_radix_digit_scan, dim3(256), dim3(256), 0, st, (const int*)hist, nblk, offs, bs);
-      int* vout = (p == passes - 1) ? order : vb;
-      hipLaunchKernelGGL(k_radix_scatter, dim3(nblk), dim3(64), 0, st, (const unsigned*)ka, (const int*)va, (long long)n,
-                         base + 8 * p, nblk, (const int*)offs, (const int*)bs, kb, vout);
-      unsigned* tk = ka; ka = kb; kb = tk;
-      if (p != passes - 1) { int* tv = va; va = vb; vb = tv; }
-    }
-  }
-  long long n_tiles = cdiv(n, 32);
-  hipLaunchKernelGGL(k_tile_masks, dim3((unsigned)cdiv(n_tiles * 32, 256)), dim3(256), 0, st, (const unsigned*)ka,
-                     (long long)n, n_tiles, tile_mask, (const int*)key_pos, K);
-  hipLaunchKernelGGL(k_permute_table, dim3((unsigned)cdiv(n, 256), K), dim3(256), 0, st, tbl, (const int*)order,
-                     (long long)n, tbl_sorted, (const int*)tile_mask);
-  GCL_CHECK_LAUNCH();
-  return GCL_OK;
 }
 
 int gcl_kernel_map_3_from_5(const int32_t* nbr5, const int32_t* counts5, int64_t n, int32_t* nbr3, int32_t* counts3,
@@ -1360,7 +1129,6 @@ int gcl_not_ones_rows(const float* x, int32_t cin, const int32_t* coords, int64_
 int gcl_table_sort_multi(const gcl_sort_job* jobs_host, int32_t n_jobs, void* stream) {
   GCL_CHECK_ARG(jobs_host && n_jobs >= 1, "gcl_table_sort_multi: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  static const int max_passes = [] { const char* e = getenv("GCL_SORT_PASSES"); int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
   for (int j0 = 0; j0 < n_jobs; j0 += SORT_MAX_JOBS) {
     const int T = (n_jobs - j0 < SORT_MAX_JOBS) ? n_jobs - j0 : SORT_MAX_JOBS;
     SortJobs J;
@@ -1401,20 +1169,22 @@ int gcl_table_sort_multi(const gcl_sort_job* jobs_host, int32_t n_jobs, void* st
     if (counts_known) {
       hipLaunchKernelGGL(k_row_masks_keys_multi, dim3(gn, T), dim3(256), 0, st, J);     // sort keys -> ka, row ids -> va
     } else {
-    for (int t = 0; t < T; ++t) {      // (a mixed call measures every table)
-      J.j[t].bit_count = jobs_host[j0 + t].scratch + gcl_table_sort_scratch_len(jobs_host[j0 + t].n) - 64;
+      for (int t = 0; t < T; ++t) {      // (a mixed call measures every table)
+        J.j[t].bit_count = jobs_host[j0 + t].scratch + gcl_table_sort_scratch_len(jobs_host[j0 + t].n) - 64;
+      }
+      hipLaunchKernelGGL(k_row_masks_multi, dim3(gn, T), dim3(256), 0, st, J);            // masks -> ka, row ids -> va
+      // (grid-stride body: as many workgroups as the largest table has 1024-row pieces, at most 512 -- a pass over one pair
+      // has 36 of them, and 512 workgroups per table each reduced 27 counters for nothing: 38 us)
+      hipLaunchKernelGGL(k_mask_bit_count_multi, dim3((unsigned)std::min<long long>(512, cdiv(n_max, 1024)), T), dim3(256), 0,
+                         st, J);
+      hipLaunchKernelGGL(k_mask_keys_multi, dim3(gn, T), dim3(256), 0, st, J);             // ka: masks -> sort keys
     }
-    hipLaunchKernelGGL(k_row_masks_multi, dim3(gn, T), dim3(256), 0, st, J);            // masks -> ka, row ids -> va
-    // (grid-stride body: as many workgroups as the largest table has 1024-row pieces, at most 512 -- a pass over one pair has
-    // 36 of them, and 512 workgroups per table each reduced 27 counters for nothing: 38 us)
-    hipLaunchKernelGGL(k_mask_bit_count_multi, dim3((unsigned)std::min<long long>(512, cdiv(n_max, 1024)), T), dim3(256), 0, st, J);
-    hipLaunchKernelGGL(k_mask_keys_multi, dim3(gn, T), dim3(256), 0, st, J);             // ka: masks -> sort keys
-    }
-    int passes = (K0 + 7) / 8, base = 0;
-    if (passes > max_passes) {
-      base = K0 - 8 * max_passes;
-      passes = max_passes;
-    }
+    // at most three 8-bit passes: a 27-offset mask is ordered by its 24 most significant bits (offsets 3..26); the
+    // three dropped bits only permute rows inside runs that already share 24 bits (measured: MFMA work unchanged,
+    // one pass of ~45 us per table saved)
+    constexpr int SORT_MAX_PASSES = 3;
+    const int passes = std::min((K0 + 7) / 8, SORT_MAX_PASSES);
+    const int base = std::max(0, K0 - 8 * passes);      // the key bits below `base` are not sorted on
     for (int p = 0; p < passes; ++p) {
       for (int t = 0; t < T; ++t) {
         SortJob& q = J.j[t];
@@ -1437,6 +1207,14 @@ int gcl_table_sort_multi(const gcl_sort_job* jobs_host, int32_t n_jobs, void* st
     GCL_CHECK_LAUNCH();
   }
   return GCL_OK;
+}
+
+int gcl_table_sort(const int32_t* tbl, int32_t K, int64_t n, int32_t* scratch, int32_t* order, int32_t* tbl_sorted,
+                   int32_t* tile_mask, void* stream) {
+  GCL_CHECK_ARG(tbl && scratch && order && tbl_sorted && tile_mask, "gcl_table_sort: null pointer");
+  GCL_CHECK_ARG(K >= 1 && K <= 27 && n > 0, "gcl_table_sort: K must be <= 27 (3^3 kernels), n > 0");
+  const gcl_sort_job job = {tbl, K, n, scratch, order, tbl_sorted, tile_mask, nullptr};      // no counts: the sort measures them
+  return gcl_table_sort_multi(&job, 1, stream);
 }
 
 }  // extern "C"

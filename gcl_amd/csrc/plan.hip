@@ -109,17 +109,6 @@ __global__ void __launch_bounds__(256) k_cat_right(const float4* __restrict__ b,
   }
   if (amax && !planes) publish_amax_wg(m, amax);
 }
-__global__ void __launch_bounds__(256) k_split2(const float4* __restrict__ g, int ca4, int cb4, long long n,
-                                                float4* __restrict__ ga, float4* __restrict__ gb) {
-  const int c4 = ca4 + cb4;
-  const long long total = n * c4;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long r = i / c4;
-    const int q = (int)(i - r * c4);
-    const float4 v = g[i];
-    if (q < ca4) ga[r * ca4 + q] = v; else gb[r * cb4 + (q - ca4)] = v;
-  }
-}
 // y = a + b for row-major [n, c] operands with row pitches (floats; a column slice of a wider tensor has pitch > c);
 // b == NULL: y = a (materialises a slice)
 __global__ void __launch_bounds__(256) k_add2_ld(const float* __restrict__ a, int a_ld, const float* __restrict__ b, int b_ld,
@@ -305,10 +294,9 @@ static int maps_build(const int32_t* coords, long long n, const gcl_map_spec* sp
     const bool same = sp.stride == 1;
     d.nbr_t = same ? nullptr : A.take_n<int32_t>((long long)d.K * d.n_in);
     d.counts = counts_all + 128 * s;
-    // a 3^3 stride-1 map of a table whose 5^3 stride-1 map is already built: 27 of its rows (GCL_MAP3_FROM5=0: probe again)
-    static const bool from5 = [] { const char* e = getenv("GCL_MAP3_FROM5"); return !(e && e[0] == '0'); }();
+    // a 3^3 stride-1 map of a table whose 5^3 stride-1 map is already built: 27 of its rows
     int src5 = -1;
-    for (int q = 0; q < s && from5 && same && sp.kernel_size == 3; ++q)
+    for (int q = 0; q < s && same && sp.kernel_size == 3; ++q)
       if (specs[q].t_in == sp.t_in && specs[q].kernel_size == 5 && specs[q].stride == 1 && out->maps[q].nbr) src5 = q;
     if (src5 >= 0) {
       launches[n_launches++] = MapLaunch{s, src5, 0, nullptr, nullptr, mstream};
@@ -360,7 +348,6 @@ static int maps_build(const int32_t* coords, long long n, const gcl_map_spec* sp
       else { d.tbl_n = sorted; d.order_n = order; d.mask_n = mask; }
     }
   }
-  static const int sort_multi = [] { const char* e = getenv("GCL_SORT_MULTI"); return e ? atoi(e) : 1; }();
   for (int s = 0; s < n_specs; ++s) {      // presence words of the first layer's table (occupancy path of the stem kernels)
     if (!(specs[s].tables & 4) || specs[s].kernel_size == 1) continue;
     gcl_map_desc& d = out->maps[s];
@@ -369,11 +356,7 @@ static int maps_build(const int32_t* coords, long long n, const gcl_map_spec* sp
   }
   for (int sd = 0; sd < 2; ++sd) {      // the main stream's tables first: the first layers wait for them
     void* sstream = (sd && side) ? (void*)side : stream;
-    if (n_jobs[sd] && sort_multi) PLAN_CALL(gcl_table_sort_multi(jobs[sd], n_jobs[sd], sstream));
-    if (n_jobs[sd] && !sort_multi)
-      for (int q = 0; q < n_jobs[sd]; ++q)
-        PLAN_CALL(gcl_table_sort_pre(jobs[sd][q].tbl, jobs[sd][q].K, jobs[sd][q].n, 0, nullptr, jobs[sd][q].scratch,
-                                     jobs[sd][q].order, jobs[sd][q].tbl_sorted, jobs[sd][q].tile_mask, sstream));
+    if (n_jobs[sd]) PLAN_CALL(gcl_table_sort_multi(jobs[sd], n_jobs[sd], sstream));
   }
   if (!side) out->late_mask = 0;       // (dry run / one stream: nothing is late)
   // the second host sync: per-offset pair counts -> padded segment offsets -> pair lists (KernelMap.pairs); skipped when
@@ -514,13 +497,6 @@ struct Plan : PassState {   // the base part is the pass being enqueued right no
 };
 
 static long long state_words(const Plan& P) { return (long long)P.worder.size() * (2 + 8 + 8); }
-
-// GCL_BN_PLANES=0: the BatchNorm passes publish the measured max-abs and every plane image is a gcl_split_planes pass of
-// its own (rounds 1 - 4); ops.py reads the same variable
-static bool bound_mode() {
-  static const bool on = [] { const char* e = getenv("GCL_BN_PLANES"); return !(e && e[0] == '0'); }();
-  return on;
-}
 
 static int32_t* new_slot(Plan& P) {      // slots are used once per pass (they start zeroed); the pool is sized for the worst case
   if (P.next_slot >= P.n_slots) {
@@ -824,7 +800,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
         // producers have published.
         const int32_t* res_amax = op.x2 >= 0 ? P.t[op.x2].amax : nullptr;
         const int32_t* cat_amax = P.cat_left[i] >= 0 ? P.t[P.ops[P.cat_left[i]].x2].amax : nullptr;
-        const bool bound = stats && bound_mode() && c >= P.presplit && (c % 32) == 0 && (op.x2 < 0 || res_amax) &&
+        const bool bound = stats && c >= P.presplit && (c % 32) == 0 && (op.x2 < 0 || res_amax) &&
                            (P.cat_left[i] < 0 || (cat_amax && (P.ops[P.cat_left[i]].cout % 32) == 0));
         int32_t* bound_slot = bound ? new_slot(P) : nullptr;
         if (stats) {       // column sums (and ranges) from the convolution epilogue
@@ -1056,9 +1032,8 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
     float* scratch = A.take_n<float>(gcl_conv_bwd_weight_scratch_len(op.K, op.cin, op.cout, m.seg_off[op.K], n_sorted));
     const bool pl = pl_w;
     ProfScope ps(P, ws, 2, pairs, op.cin, op.cout, n_in, n_out, op.K);
-    static const bool map_bounds = [] { const char* e = getenv("GCL_DW_MAP_BOUNDS"); return !(e && e[0] == '0'); }();
     // m.dw_bounds: over the map's pair_out with n_out(map) rows -- the sorted list of this launch on either side
-    const int32_t* rgb = (map_bounds && sorted_side != 0 && n_sorted == m.n_out) ? m.dw_bounds : nullptr;
+    const int32_t* rgb = (sorted_side != 0 && n_sorted == m.n_out) ? m.dw_bounds : nullptr;
     PLAN_CALL(gcl_conv_bwd_weight_rg(pl ? (const float*)x.planes : x.ptr, n_in, pl ? (const float*)dy.planes : dy.ptr, n_out,
                                      pl ? 1 : 0, sorted_side, pa, pb, m.seg_off, op.K, op.cin, op.cout, 4, P.saved[i].x_amax,
                                      dy.amax, scratch, dW, rgb, (void*)ws));
@@ -1148,22 +1123,9 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
         // the gradients of the two inputs ARE the column slices of g: handed on as views (row pitch = the cat's width); their
         // readers -- the BatchNorm backward kernels, a convolution epilogue that adds a waiting gradient -- take the pitch
         const int ca = op.cin, cb = op.cout - op.cin;
-        static const int cat_views = [] { const char* e = getenv("GCL_CAT_VIEWS"); return e ? atoi(e) : 1; }();
         if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
-        if (cat_views) {
-          if ((rc = give(P, op.x, g.ptr, n_out * ca, st, nullptr, op.cout, ca))) return rc;
-          if ((rc = give(P, op.x2, g.ptr + ca, n_out * cb, st, nullptr, op.cout, cb))) return rc;
-          break;
-        }
-        float* ga = A.take_n<float>(n_out * ca);
-        float* gb = A.take_n<float>(n_out * cb);
-        if (!A.dry) {
-          hipLaunchKernelGGL(k_split2, dim3(grid_for(n_out * op.cout / 4)), dim3(256), 0, st, (const float4*)g.ptr, ca / 4, cb / 4,
-                             n_out, (float4*)ga, (float4*)gb);
-          GCL_CHECK_LAUNCH();
-        }
-        if ((rc = give(P, op.x, ga, n_out * ca, st))) return rc;
-        if ((rc = give(P, op.x2, gb, n_out * cb, st))) return rc;
+        if ((rc = give(P, op.x, g.ptr, n_out * ca, st, nullptr, op.cout, ca))) return rc;
+        if ((rc = give(P, op.x2, g.ptr + ca, n_out * cb, st, nullptr, op.cout, cb))) return rc;
         break;
       }
       case GCL_OP_ROWNORM: {
@@ -1314,10 +1276,9 @@ void* gcl_plan_create(const gcl_plan_op* ops_host, int32_t n_ops, int32_t n_tens
     P->made[op.y] = 1;
   }
   // CONV directly followed by the RELU that is its only consumer (model/resunet.py:222-224: conv1_tr, MEF.relu, final): the
-  // convolution's epilogue applies the ReLU and publishes max|y| (GCL_PLAN_FUSE_RELU=0: two launches, same values)
+  // convolution's epilogue applies the ReLU and publishes max|y|
   P->fuse_relu.assign(P->ops.size(), 0);
-  static const bool fuse_relu_on = [] { const char* e = getenv("GCL_PLAN_FUSE_RELU"); return !(e && e[0] == '0'); }();
-  for (size_t i = 0; ok && fuse_relu_on && i + 1 < P->ops.size(); ++i) {
+  for (size_t i = 0; ok && i + 1 < P->ops.size(); ++i) {
     const gcl_plan_op &a = P->ops[i], &b = P->ops[i + 1];
     if (a.kind != GCL_OP_CONV || b.kind != GCL_OP_RELU || b.x != a.y || a.cin <= 4) continue;
     bool other = a.y == P->ops.back().y;       // the plan's output keeps its own tensor
@@ -1326,8 +1287,7 @@ void* gcl_plan_create(const gcl_plan_op* ops_host, int32_t n_ops, int32_t n_tens
     if (!other) P->fuse_relu[i] = 1;
   }
   P->cat_left.assign(P->ops.size(), -1);
-  static const bool cat_inplace = [] { const char* e = getenv("GCL_CAT_INPLACE"); return !(e && e[0] == '0'); }();
-  for (size_t i = 0; ok && cat_inplace && i < P->ops.size(); ++i) {
+  for (size_t i = 0; ok && i < P->ops.size(); ++i) {
     const gcl_plan_op& a = P->ops[i];
     if (a.kind != GCL_OP_CONVBN || a.cin <= 4 || a.y == P->ops.back().y) continue;
     int cat = -1, consumers = 0;
@@ -1338,7 +1298,7 @@ void* gcl_plan_create(const gcl_plan_op* ops_host, int32_t n_ops, int32_t n_tens
     if (cat >= 0 && consumers == 1) P->cat_left[i] = cat;
   }
   P->mask_from.assign(P->ops.size(), -1);
-  for (size_t i = 0; ok && fuse_relu_on && i < P->ops.size(); ++i) {
+  for (size_t i = 0; ok && i < P->ops.size(); ++i) {
     const gcl_plan_op& a = P->ops[i];
     if ((a.kind != GCL_OP_CONV && a.kind != GCL_OP_CONVBN) || a.cin <= 4 || a.x == 0) continue;
     int r = -1, consumers = 0;

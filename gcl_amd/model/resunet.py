@@ -182,8 +182,7 @@ class ResUNet2(ME.MinkowskiNetwork):
         ops = ME.ops
         if (self.training or torch.is_grad_enabled() or not native.PLAN_ENABLED or ops.PRECISION != "fp16x3"
                 or self.NORM_TYPE != "BN" or self.BLOCK_NORM_TYPE != "BN" or x.coordinate_map_key.tensor_stride != 1
-                or self.__dict__.get("_plan") is False or any(m.training for m in self._module_list())
-                or ME.core.SORT_WINDOW or ME.core.SPATIAL_MAX_STRIDE):
+                or self.__dict__.get("_plan") is False or any(m.training for m in self._module_list())):
             return None
         mgr = x.coordinate_manager
         plan = self.__dict__.get("_plan")

@@ -171,19 +171,18 @@ int gcl_kernel_map_pairs(const int32_t* nbr, int32_t K, int64_t n_out, const int
 
 /* Row ordering for the output-stationary convolution: sorts the rows of a [K][n] neighbour table (K <= 27) by
  * their K-bit presence mask (stable radix sort), so that the rows of a 32-row wave tile need nearly the same offsets.
- * Global mode: the sort key is the mask with its bits re-ordered by how often each offset occurs in THIS table -- the
+ * The sort key is the mask with its bits re-ordered by how often each offset occurs in THIS table -- the
  * rarest offset is the most significant key bit, the most frequent the least significant, ties: lower offset lower --
  * and the sort runs on the key's 24 most significant bits (key >> max(0, K - 24), three 8-bit passes).  Rows that own a
  * rare offset then share its visit.  The convolution walks the tiles from the END of this order (the tiles with the
  * most offsets first).  order[j] = original row at sorted position j; tbl_sorted[k*n + j] = tbl[k*n + order[j]];
  * tile_mask[t] = OR of the masks of sorted rows 32t .. 32t+31.  scratch: int32[gcl_table_sort_scratch_len(n)].
- * window = 0: one global sort.  window = 2048 | 4096: rows are sorted only inside windows of that many consecutive
- * rows (one LDS bitonic sort per window): keeps the loader's spatial coherence for the gathers. */
+ * gcl_table_sort is gcl_table_sort_multi with one job without `counts`. */
 int64_t gcl_table_sort_scratch_len(int64_t n);
-int gcl_table_sort(const int32_t* tbl, int32_t K, int64_t n, int32_t window, int32_t* scratch, int32_t* order,
-                   int32_t* tbl_sorted, int32_t* tile_mask, void* stream);
-/* gcl_table_sort (global mode, window 0) of SEVERAL tables in one sequence of 14 launches (a network has 12 such tables:
- * 168 launches one by one).  Same results bit for bit.  All tables of a call share K. */
+int gcl_table_sort(const int32_t* tbl, int32_t K, int64_t n, int32_t* scratch, int32_t* order, int32_t* tbl_sorted,
+                   int32_t* tile_mask, void* stream);
+/* The mask sort of SEVERAL tables in one sequence of 14 launches (a network has 12 such tables: 168 launches one by
+ * one).  Same results bit for bit.  All tables of a call share K. */
 typedef struct gcl_sort_job {
   const int32_t* tbl;
   int32_t K;
@@ -196,16 +195,6 @@ typedef struct gcl_sort_job {
                             when EVERY table of the call has it the bit-count and key passes fold into the first launch */
 } gcl_sort_job;
 int gcl_table_sort_multi(const gcl_sort_job* jobs_host, int32_t n_jobs, void* stream);
-/* Spatial pre-order of the rows of a coordinate map at tensor stride `tensor_stride`: order[j] = row at position j when
- * rows are sorted by (cloud id, Morton code of the 4^3-voxel cell); stable, deterministic.  gcl_table_sort_pre with
- * window = 2048 | 4096 then mask-sorts inside windows of THAT order: the rows a workgroup (and, with
- * GCL_CONV_XCD_RANGES, an XCD) processes together are spatial neighbours and re-use each other's gathered input rows in
- * L2 instead of fetching every row from the Infinity Cache once per kernel offset.  A locality heuristic only: results
- * do not depend on it.  scratch: int32[gcl_table_sort_scratch_len(n)]. */
-int gcl_spatial_order(const int32_t* coords, int64_t n, int32_t tensor_stride, int32_t* scratch, int32_t* order,
-                      void* stream);
-int gcl_table_sort_pre(const int32_t* tbl, int32_t K, int64_t n, int32_t window, const int32_t* pre, int32_t* scratch,
-                       int32_t* order, int32_t* tbl_sorted, int32_t* tile_mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Sparse convolution (fp32, exact-f32 MFMA).
@@ -264,9 +253,9 @@ int32_t gcl_conv_fwd_nb(int64_t n_out, int32_t cout, int32_t prec);
  * fp16 hi values (64 bytes) then the fp16 lo values (64 bytes) of x * scale(amax), i.e. 4 bytes per element like x.
  * A tensor that several launches consume (forward, weight gradient; input gradient, weight gradient) is split once. */
 int gcl_split_planes(const float* x, int64_t n, int32_t c, const int32_t* amax, void* planes, void* stream);
-/* flags: GCL_CONV_XCD_RANGES -- the table comes from gcl_table_sort_pre on a spatial pre-order: give every XCD (L2) a
- * CONTIGUOUS range of row tiles, so that the input rows a tile gathers are mostly the ones its neighbours on the same XCD
- * just gathered.  Launch-order hint only. */
+/* flags: GCL_CONV_XCD_RANGES -- for a table whose row order is spatially coherent: give every XCD (L2) a CONTIGUOUS
+ * range of row tiles, so that the input rows a tile gathers are mostly the ones its neighbours on the same XCD just
+ * gathered.  Launch-order hint only. */
 #define GCL_CONV_XCD_RANGES 1
 #define GCL_CONV_TALL 4     /* inference launches: sixteen waves per workgroup, a tile's offsets in four FIXED groups (k with
                                k mod 4 == g) whose partial sums are added in group order -- shortens the chain of dependent

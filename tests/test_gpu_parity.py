@@ -4,6 +4,7 @@ CPU oracle (oracle/) on the same seeded inputs, and against the golden vectors c
 Bar: bit-exact for coordinate maps / kernel maps / indices; for fp32 features the north star's tolerance is
 1e-4 relative L2 against the (fp64) oracle -- the per-operator bounds below are tighter and written in each test.
 """
+import ctypes
 import glob
 import os
 import sys
@@ -1099,46 +1100,126 @@ def test_full_size_properties():
     assert torch.equal(y1.detach(), y2.detach()) and torch.equal(x.grad, x2.grad)
 
 
-@pytest.mark.parametrize("window", [0, 2048, 4096])
-def test_table_sort_is_a_stable_mask_sort(window):
-    """gcl_table_sort: order is a permutation sorted by presence mask (stable; inside windows of consecutive rows when
-    a window is given), the permuted table and the tile masks are consistent with it."""
-    from gcl_amd.MinkowskiEngine import core
+def mask_sort_reference(tbl):
+    """numpy statement of the mask sort of a [K, n] table: (order, tile masks, per-offset row counts).  The key is the
+    presence mask with its bits re-ordered by offset frequency in this table (rarest offset = most significant bit, ties:
+    lower offset lower), sorted stably on its 24 top bits (at most three 8-bit radix passes)."""
+    K, n = tbl.shape
+    mask = np.zeros(n, dtype=np.int64)
+    for k in range(K):
+        mask |= (tbl[k] >= 0).astype(np.int64) << k
+    cnt = np.array([int(((mask >> k) & 1).sum()) for k in range(K)])
+    pos = np.array([int(((cnt > cnt[k]) | ((cnt == cnt[k]) & (np.arange(K) < k))).sum()) for k in range(K)])
+    key = np.zeros_like(mask)
+    for k in range(K):
+        key |= ((mask >> k) & 1) << pos[k]
+    key = key >> max(0, K - 24)
+    order = np.lexsort((np.arange(n), key))
+    pad = (-n) % 32
+    mt = np.concatenate([mask[order], np.zeros(pad, np.int64)]).reshape(-1, 32)
+    return order, np.bitwise_or.reduce(mt, axis=1), cnt
+
+
+def test_table_sort_is_a_stable_mask_sort():
+    """gcl_table_sort: order is a permutation sorted by presence mask (stable), the permuted table and the tile masks
+    are consistent with it."""
     C = random_cloud(9, n=5000, batch=2)
-    old = core.SORT_WINDOW
-    core.SORT_WINDOW = window
-    try:
-        mgr = make_mgr(C)
-        for key in [(1, 3, 1), (1, 3, 2)]:
-            km = mgr.get_kernel_map(*key)
-            for transposed in ([False, True] if km.nbr_t is not None else [False]):
-                tbl = (km.nbr_t if transposed else km.nbr).cpu().numpy()
-                ts, order, tmask = (t.cpu().numpy() for t in km.sorted_table(transposed))
-                n = tbl.shape[1]
-                mask = np.zeros(n, dtype=np.int64)
-                for k in range(km.K):
-                    mask |= (tbl[k] >= 0).astype(np.int64) << k
-                win = np.arange(n) // window if window else np.zeros(n, dtype=np.int64)
-                # the global sort's key: mask bits re-ordered by offset frequency in this table (rarest offset = most
-                # significant bit, ties: lower offset lower), at most three 8-bit radix passes = its 24 top bits
-                if window:
-                    key = mask
-                else:
-                    cnt = np.array([int(((mask >> k) & 1).sum()) for k in range(km.K)])
-                    pos = np.array([int(((cnt > cnt[k]) | ((cnt == cnt[k]) & (np.arange(km.K) < k))).sum())
-                                    for k in range(km.K)])
-                    key = np.zeros_like(mask)
-                    for k in range(km.K):
-                        key |= ((mask >> k) & 1) << pos[k]
-                    key = key >> max(0, km.K - 24)
-                ref_order = np.lexsort((np.arange(n), key, win))
-                assert np.array_equal(order, ref_order)
-                assert np.array_equal(ts, tbl[:, order])
-                pad = (-n) % 32
-                mt = np.concatenate([mask[order], np.zeros(pad, np.int64)]).reshape(-1, 32)
-                assert np.array_equal(tmask.astype(np.int64), np.bitwise_or.reduce(mt, axis=1))
-    finally:
-        core.SORT_WINDOW = old
+    mgr = make_mgr(C)
+    for key in [(1, 3, 1), (1, 3, 2)]:
+        km = mgr.get_kernel_map(*key)
+        for transposed in ([False, True] if km.nbr_t is not None else [False]):
+            tbl = (km.nbr_t if transposed else km.nbr).cpu().numpy()
+            ts, order, tmask = (t.cpu().numpy() for t in km.sorted_table(transposed))
+            ref_order, ref_tmask, _ = mask_sort_reference(tbl)
+            assert np.array_equal(order, ref_order)
+            assert np.array_equal(ts, tbl[:, order])
+            assert np.array_equal(tmask.astype(np.int64), ref_tmask)
+
+
+def synthetic_sort_table(seed, K, n):
+    """int32 [K, n] of -1 / non-negative ids whose offsets differ in how often they are present; from K = 4 on, offset 1
+    is never present, offset K - 2 always, and offsets 0 and K - 1 are present equally often in different rows (the
+    tie rule of the key positions)."""
+    rng = np.random.RandomState(seed)
+    present = rng.rand(K, n) < rng.permutation(np.linspace(0.05, 0.9, K))[:, None]
+    if K >= 4:
+        present[0] = rng.rand(n) < 0.3
+        present[K - 1] = present[0][rng.permutation(n)]
+        present[1] = False
+        present[K - 2] = True
+    return np.where(present, rng.randint(0, n, (K, n)), -1).astype(np.int32)
+
+
+class _SortJob(ctypes.Structure):      # gcl_sort_job
+    _fields_ = [("tbl", ctypes.c_void_p), ("K", ctypes.c_int32), ("n", ctypes.c_int64), ("scratch", ctypes.c_void_p),
+                ("order", ctypes.c_void_p), ("tbl_sorted", ctypes.c_void_p), ("tile_mask", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p)]
+
+
+_SENTINEL = 0x5A5A5A5A
+
+
+def _sort_buffers(lib, tbl):
+    """device copy of the table, and scratch / order / tbl_sorted / tile_mask pre-filled with a sentinel"""
+    K, n = tbl.shape
+    full = lambda m: torch.full((m,), _SENTINEL, dtype=torch.int32, device=DEV)      # noqa: E731
+    return (torch.from_numpy(tbl).to(DEV), full(lib.gcl_table_sort_scratch_len(n)), full(n), full(K * n), full((n + 31) // 32))
+
+
+def _check_sorted(tbl, order, tbl_sorted, tile_mask, what):
+    ref_order, ref_tmask, _ = mask_sort_reference(tbl)
+    order, tbl_sorted, tile_mask = order.cpu().numpy(), tbl_sorted.cpu().numpy().reshape(tbl.shape), tile_mask.cpu().numpy()
+    assert np.array_equal(order, ref_order), what
+    assert np.array_equal(tbl_sorted, tbl[:, ref_order]), what
+    assert np.array_equal(tile_mask.astype(np.int64), ref_tmask), what
+    return order, tbl_sorted, tile_mask
+
+
+def _table_sort_single(lib, tbl):
+    from gcl_amd import _lib
+    K, n = tbl.shape
+    d_tbl, scratch, order, tbl_sorted, tile_mask = _sort_buffers(lib, tbl)
+    _lib.check(lib.gcl_table_sort(_lib.ptr(d_tbl), K, n, _lib.ptr(scratch), _lib.ptr(order), _lib.ptr(tbl_sorted),
+                                  _lib.ptr(tile_mask), _lib.stream()), "gcl_table_sort")
+    return _check_sorted(tbl, order, tbl_sorted, tile_mask, f"gcl_table_sort K={K} n={n}")
+
+
+# n: the tile edges of 32, the block edges of 256 and the radix block edge of 512 at K = 27; K: 1, 1, 2 and 3 radix passes,
+# then four clamped to three with 1 and 3 key bits dropped
+@pytest.mark.parametrize("K,n", [(27, n) for n in (1, 31, 32, 33, 255, 257, 511, 512, 513, 5000)]
+                         + [(K, 513) for K in (1, 8, 9, 24, 25)])      # (27, 513) is in the first list
+def test_table_sort_synthetic_tables(K, n):
+    """gcl_table_sort through the C ABI on synthetic tables (an offset that is never present, one that always is, two
+    with equal counts): order, permuted table and tile masks equal the numpy mask sort, no sentinel left."""
+    from gcl_amd import _lib
+    _table_sort_single(_lib.load(), synthetic_sort_table(1000 * K + n, K, n))
+
+
+@pytest.mark.parametrize("ns,with_counts", [((5000, 33, 1, 513), "all"), ((5000, 33, 1, 513), "none"),
+                                            ((5000, 33, 1, 513), "two"), ((40,) * 17, "all")])
+def test_table_sort_multi_equals_single_and_reference(ns, with_counts):
+    """gcl_table_sort_multi, K = 27: every job's order, permuted table and tile masks equal gcl_table_sort's and the numpy
+    mask sort's, bitwise -- with the true per-offset counts given for all jobs, for none, for two of four (a mixed call
+    measures every table), and for 17 jobs (more than the 16 of one launch sequence: two sequences)."""
+    from gcl_amd import _lib
+    lib = _lib.load()
+    K = 27
+    tables = [synthetic_sort_table(77 + 13 * q + n, K, n) for q, n in enumerate(ns)]
+    given = {"all": [True] * len(ns), "none": [False] * len(ns), "two": [True, False, False, True]}[with_counts]
+    bufs = [_sort_buffers(lib, t) for t in tables]
+    counts = [torch.from_numpy(mask_sort_reference(t)[2].astype(np.int32)).to(DEV) if g else None
+              for t, g in zip(tables, given)]
+    jobs = (_SortJob * len(ns))()
+    for job, t, (d_tbl, scratch, order, tbl_sorted, tile_mask), c in zip(jobs, tables, bufs, counts):
+        job.tbl, job.K, job.n = d_tbl.data_ptr(), K, t.shape[1]
+        job.scratch, job.order, job.tbl_sorted, job.tile_mask = (x.data_ptr() for x in (scratch, order, tbl_sorted, tile_mask))
+        job.counts = c.data_ptr() if c is not None else None
+    _lib.check(lib.gcl_table_sort_multi(ctypes.cast(jobs, ctypes.c_void_p), len(ns), _lib.stream()), "gcl_table_sort_multi")
+    for q, (t, (_, _, order, tbl_sorted, tile_mask)) in enumerate(zip(tables, bufs)):
+        multi = _check_sorted(t, order, tbl_sorted, tile_mask, f"gcl_table_sort_multi job {q} n={t.shape[1]} counts={with_counts}")
+        single = _table_sort_single(lib, t)
+        for a, b in zip(multi, single):
+            assert np.array_equal(a, b), (q, with_counts)
 
 
 def test_extract_features_and_eval_pair_vs_oracle():

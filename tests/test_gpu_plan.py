@@ -85,8 +85,8 @@ def test_native_maps_equal_the_per_operator_maps(seed, n, batch):
 
 @pytest.mark.parametrize("seed,n,batch", [(0, 4000, 2), (1, 300, 1), (2, 20000, 3)])
 def test_kernel_map_3_from_5_equals_the_probed_map(seed, n, batch):
-    """gcl_kernel_map_3_from_5 (the GCL_MAP3_FROM5 shortcut of gcl_maps_build: the 3^3 stride-1 map of the input table as
-    27 rows of its 5^3 map) == the map the probing pass builds (GCL_MAP3_FROM5=0): neighbour table and pair counts, bit
+    """gcl_kernel_map_3_from_5 (the shortcut of gcl_maps_build: the 3^3 stride-1 map of the input table as
+    27 rows of its 5^3 map) == the map the probing pass builds: neighbour table and pair counts, bit
     for bit."""
     import gcl_amd.MinkowskiEngine as ME
     from gcl_amd import _lib
