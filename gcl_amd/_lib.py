@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GCL_LIB_PATH", os.path.join(CSRC, "libgcl_hip.so"))   # override: diagnostic builds only
 SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip", "ransac.hip", "regstats.hip", "fpfh.hip",
-           "valpose.hip"]
+           "valpose.hip", "pairmatch.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gcl_amd.h")
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -205,6 +205,11 @@ SIGNATURES = {
     "gcl_irls_pose_scratch_len": (_i64, [_i64]),
     "gcl_irls_pose_batch": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp]),
     "gcl_val_stats_batch": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _f64, _f64, _vp, _vp]),
+    "gcl_pair_matches_scratch_len": (_i64, [_i64]),
+    "gcl_pair_matches_count": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _i32,
+                                       _vp, _vp, _vp, _vp]),
+    "gcl_pair_matches_emit": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _f64, _i32,
+                                      _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 
 PAIR_CHUNK = 128   # GCL_PAIR_CHUNK

@@ -141,6 +141,40 @@ int gcl_colocation_hits_at(const float* xyz_own, const float* xyz_cf, int64_t ro
  * out: int64[k]. */
 int gcl_host_legacy_choice(uint32_t* key, int32_t* pos, int64_t n, int64_t k, int64_t* work, int64_t* out);
 
+/* Ground-truth correspondences of scan pairs = get_matching_indices (util/pointcloud.py:53-66; called by every pair dataset,
+ * lib/data_loaders.py:256, :506), for a ragged batch of n_pairs >= 1 pairs in the launches of one: count, scan, emit.
+ *   xyz0 [total0, 3], offsets0 int64 [n_pairs + 1]   the source points (one per voxel), pair b = rows offsets0[b] .. offsets0[b+1]
+ *   xyz1 [total1, 3], offsets1 int64 [n_pairs + 1]   the target points, likewise            (all of these on the DEVICE)
+ *   table, cap        coordinate hash table that holds floor(xyz1 / voxel) of every target under the batch id
+ *                     cloud0 + b * cloud_stride (gcl_unique_coords / gcl_coords_insert make it; other clouds may live in it)
+ *   table_row0        int64 [n_pairs] or NULL: the table's value of target b's FIRST row (the table may number the rows of a
+ *                     larger array, e.g. all 2 B clouds of a batch); NULL = offsets1[b], the values address xyz1 directly
+ *   voxel             the voxel size the table's coordinates were made with (the query's voxel is q / voxel in fp64)
+ *   trans             double [n_pairs][12], row-major 3 x 4: source -> target frame;  radii: double [n_pairs]
+ *   radius_max        HOST bound of the radii: radius_max / voxel >= 4 (more than 9^3 candidate voxels) returns GCL_ERR_ARG
+ *                     before anything is launched
+ *   K                 keep the first K hits of a source row; 0 = all (the reference's K = None)
+ * Arithmetic (that of gcl_colocation_hits): q = ((x m0 + y m1) + z m2) + t in fp64 from the fp32 point; d2 = ((ex^2 + ey^2) +
+ * ez^2) against the fp32 target point; a hit is d2 < r r; a row's hits are ordered by (d2, j); output by i, then that order.
+ * gcl_pair_matches_count   cnt int32 [total0] = kept hits per source row; scratch: int32 [gcl_pair_matches_scratch_len(total0)]
+ *                          (row offsets, read again by emit); meta: DEVICE int64 [2 + n_pairs] = {P, status, matches of pair
+ *                          0, 1, ...}.  status 1: offsets not 0 <= o[b] <= o[b+1] <= total; 2: a radius not in (0, radius_max];
+ *                          then nothing but the status word is written, by either call.
+ * gcl_pair_matches_emit    pairs int64 [n_matches, 2], n_matches = the P the host read from meta; absolute = 0: rows relative
+ *                          to the pair's own clouds, 1: rows of xyz0 / xyz1 (collate_pair_fn's running start indices added,
+ *                          lib/data_loaders.py:52-57).  Same inputs as the count call. */
+int64_t gcl_pair_matches_scratch_len(int64_t total0);
+int gcl_pair_matches_count(const float* xyz0, int64_t total0, const int64_t* offsets0, const float* xyz1, int64_t total1,
+                           const int64_t* offsets1, const int64_t* table_row0, int32_t n_pairs, const int64_t* table,
+                           int64_t cap, int32_t cloud0, int32_t cloud_stride, float voxel, const double* trans,
+                           const double* radii, double radius_max, int32_t K, int32_t* cnt, int32_t* scratch, int64_t* meta,
+                           void* stream);
+int gcl_pair_matches_emit(const float* xyz0, int64_t total0, const int64_t* offsets0, const float* xyz1, int64_t total1,
+                          const int64_t* offsets1, const int64_t* table_row0, int32_t n_pairs, const int64_t* table,
+                          int64_t cap, int32_t cloud0, int32_t cloud_stride, float voxel, const double* trans,
+                          const double* radii, double radius_max, int32_t K, int32_t absolute, const int32_t* scratch,
+                          const int64_t* meta, int64_t* pairs, int64_t n_matches, void* stream);
+
 /* Kernel map for kernel size ks^3 (x fastest in k), offsets scaled by `step` (= input tensor stride x dilation),
  * region centred on the OUTPUT coordinate:  nbr[k * n_out + v] = input row at c_out[v] + o_k * step, or -1.
  * same_map != 0: coords_out IS the input map (stride-1 conv): only offsets k <= K/2 are looked up, the mirror
