@@ -70,7 +70,12 @@ SIGNATURES = {
     "gcl_loader_points": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gcl_colocation_hits_at": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, ctypes.POINTER(ctypes.c_double), _vp, _i64, _f32,
                                        ctypes.c_double, _i32, _vp, _vp, _vp, _vp]),
-    "gcl_host_legacy_choice": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "gcl_cloud_centroids_scratch_len": (_i64, [_i64, _i32]),
+    "gcl_cloud_centroids": (_i32, [_vp, _i64, ctypes.POINTER(_i64), _i32, _vp, _vp, _vp]),
+    "gcl_cloud_affines": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "gcl_voxel_coords_aug": (_i32, [_vp, _i64, ctypes.POINTER(_i64), _i32, _f64, _vp, _vp, _i32, _vp, _vp]),
+    "gcl_loader_points_aug": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "gcl_host_legacy_choice":(_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "gcl_kernel_map_bitmap_len": (_i64, []),
     "gcl_kernel_map_scratch_len": (_i64, [_i32, _i64]),
     "gcl_kernel_map": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

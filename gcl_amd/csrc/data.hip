@@ -233,7 +233,61 @@ __global__ void k_colocation_emit(const int* __restrict__ hits, const int* __res
 struct CloudOffsets {
   long long off[65];      // point offsets of up to 64 clouds + the total
 };
+// ---- the loader's augmentation on the device: rotation about the cloud's centroid and the sample's scale, folded into the two
+// kernels that touch every point anyway (lib/colocation_data_loader.py:349-370, lib/data_loaders.py:476-492) ----------------
+// aug: double[n_clouds][12] from the host = R (9, row-major), the scale (1.0: none), rotated (0 / 1), one spare;
+// aff: double[n_clouds][12] = T_c = [R | R (-centroid)] from k_cloud_affines.
+// A cloud that is not rotated stays float32 in both of the reference's loaders: y = x * fp32(scale).  A rotated cloud is
+//   AUG_F32 (co-location loaders: apply_transform casts the transform to float32, colocation_data_loader.py:80-85):
+//           y = ((x0 r0 + x1 r1) + x2 r2) + t in fp32, y * fp32(scale), floor(y / fp32(voxel)), representative y;
+//   AUG_F64 (pair loaders keep float64 through sparse_quantize, data_loaders.py:125-129):
+//           the same expression in fp64, scale * y, floor(y / voxel) by fp64 division, representative fp32(y).
+// No product is contracted with a sum: the blocks below switch contraction off (`__fmul_rn` and its kin are plain operators
+// to this compiler and fuse like them).  AUG_NONE is the key-less path: y = x.
+enum { AUG_NONE = 0, AUG_F32 = 1, AUG_F64 = 2 };
+
+template <int MODE>
+__device__ __forceinline__ void loader_point(const float* __restrict__ p, int cloud, const double* __restrict__ aug,
+                                             const double* __restrict__ aff, float voxel, double voxel_d, float y[3], int v[3]) {
+  const float x0 = p[0], x1 = p[1], x2 = p[2];
+  if constexpr (MODE == AUG_NONE) {
+    y[0] = x0; y[1] = x1; y[2] = x2;
+    // floor(xyz / voxel_size) with the correctly rounded fp32 division numpy performs (util/misc.py:117)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = floor_to_int(__fdiv_rn(y[k], voxel));
+  } else {
+    const double scale = aug[12 * cloud + 9];
+    const bool rotated = aug[12 * cloud + 10] != 0.0;
+    const double* T = aff + 12 * cloud;
+    if (!rotated) {
+      y[0] = x0 * (float)scale; y[1] = x1 * (float)scale; y[2] = x2 * (float)scale;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[k] = floor_to_int(__fdiv_rn(y[k], voxel));
+    } else if constexpr (MODE == AUG_F32) {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float r0 = (float)T[4 * k], r1 = (float)T[4 * k + 1], r2 = (float)T[4 * k + 2], t = (float)T[4 * k + 3];
+        const float q = ((x0 * r0 + x1 * r1) + x2 * r2) + t;
+        y[k] = q * (float)scale;
+        v[k] = floor_to_int(__fdiv_rn(y[k], voxel));
+      }
+    } else {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double q = (((double)x0 * T[4 * k] + (double)x1 * T[4 * k + 1]) + (double)x2 * T[4 * k + 2]) + T[4 * k + 3];
+        const double yd = scale * q;
+        y[k] = (float)yd;
+        v[k] = (int)floor(yd / voxel_d);
+      }
+    }
+  }
+}
+
+template <int MODE>
 __global__ void k_voxel_coords_multi(const float* __restrict__ xyz, long long p, CloudOffsets co, int n_clouds, float voxel,
+                                     double voxel_d, const double* __restrict__ aug, const double* __restrict__ aff,
                                      int4* coords) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p) return;
@@ -242,8 +296,10 @@ __global__ void k_voxel_coords_multi(const float* __restrict__ xyz, long long p,
     const int mid = (lo + hi + 1) >> 1;
     if (co.off[mid] <= i) lo = mid; else hi = mid - 1;
   }
-  coords[i] = make_int4(lo, floor_to_int(__fdiv_rn(xyz[3 * i], voxel)), floor_to_int(__fdiv_rn(xyz[3 * i + 1], voxel)),
-                        floor_to_int(__fdiv_rn(xyz[3 * i + 2], voxel)));
+  float y[3];
+  int v[3];
+  loader_point<MODE>(xyz + 3 * i, lo, aug, aff, voxel, voxel_d, y, v);
+  coords[i] = make_int4(lo, v[0], v[1], v[2]);
 }
 
 // starts[c] = first unique row of cloud c (the unique rows keep the input's cloud-major order), starts[n_clouds] = n;
@@ -260,20 +316,110 @@ __global__ void k_cloud_row_starts(const int4* __restrict__ coords, const int* _
 // voxel representatives: the first point of every voxel in its OWN sensor frame (xyz_raw[index]) and in the frame of its
 // sample's centre cloud -- q = fp32(R p + t) in fp64 from the fp32 point, as the host path's numpy expression
 // (colocation_data_gpu.build_sample_gpu; the reference transforms fp64 copies: util/pointcloud.py:87-89)
+template <int MODE>
 __global__ void k_loader_points(const float* __restrict__ xyz_raw, const long long* __restrict__ index,
                                 const int4* __restrict__ coords, const int* __restrict__ n_dev,
                                 const double* __restrict__ to_center,      // [n_clouds][12], row-major 3 x 4
+                                const double* __restrict__ aug, const double* __restrict__ aff,
                                 float* __restrict__ xyz_own, float* __restrict__ xyz_cf) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= *n_dev) return;
   const long long r = index[i];
-  const float x = xyz_raw[3 * r], y = xyz_raw[3 * r + 1], z = xyz_raw[3 * r + 2];
+  const int cloud = coords[i].x;
+  float p[3];
+  int v[3];
+  loader_point<MODE>(xyz_raw + 3 * r, cloud, aug, aff, 1.f, 1.0, p, v);      // the point k_voxel_coords_multi voxelised
+  const float x = p[0], y = p[1], z = p[2];
   xyz_own[3 * i] = x; xyz_own[3 * i + 1] = y; xyz_own[3 * i + 2] = z;
-  const double* m = to_center + 12 * coords[i].x;
+  const double* m = to_center + 12 * cloud;
   // (x m0 + y m1) + z m2, then + t: the order of a 3-term dot product followed by the broadcast add, no contraction
   xyz_cf[3 * i] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, m[0]), __dmul_rn(y, m[1])), __dmul_rn(z, m[2])), m[3]);
   xyz_cf[3 * i + 1] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, m[4]), __dmul_rn(y, m[5])), __dmul_rn(z, m[6])), m[7]);
   xyz_cf[3 * i + 2] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, m[8]), __dmul_rn(y, m[9])), __dmul_rn(z, m[10])), m[11]);
+}
+
+// ---- centroid of every cloud of the batch: fp64 sums of the fp32 points in an order that depends on nothing but the point's
+// position in ITS cloud -- chunks of CENT_CHUNK points from the cloud's first point on, 256 strided running sums per chunk and
+// a fixed LDS tree over them, then the same shape over the cloud's chunk sums.  No atomics: the centroid of a cloud is bitwise
+// the same alone, anywhere in any batch, and on every run.
+constexpr int CENT_CHUNK = 1024;
+struct CloudChunks {
+  long long off[65];      // point offsets, as CloudOffsets
+  int chunk0[65];         // first chunk of every cloud + the total
+};
+
+__device__ __forceinline__ void tree_sum3(double s[3], double (*sh)[256]) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sh[k][t] = s[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) sh[k][t] = __dadd_rn(sh[k][t], sh[k][t + w]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s[k] = sh[k][0];
+}
+
+__global__ void __launch_bounds__(256) k_centroid_partials(const float* __restrict__ xyz, CloudChunks cc, int n_clouds,
+                                                           double* __restrict__ partial) {
+  __shared__ double sh[3][256];
+  const int b = blockIdx.x;
+  int lo = 0, hi = n_clouds - 1;      // the cloud of chunk b: last c with chunk0[c] <= b (an empty cloud owns no chunk)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cc.chunk0[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const long long first = cc.off[lo] + (long long)(b - cc.chunk0[lo]) * CENT_CHUNK;
+  const long long last = first + CENT_CHUNK < cc.off[lo + 1] ? first + CENT_CHUNK : cc.off[lo + 1];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (long long i = first + threadIdx.x; i < last; i += 256) {
+    s[0] = __dadd_rn(s[0], (double)xyz[3 * i]);
+    s[1] = __dadd_rn(s[1], (double)xyz[3 * i + 1]);
+    s[2] = __dadd_rn(s[2], (double)xyz[3 * i + 2]);
+  }
+  tree_sum3(s, sh);
+  if (threadIdx.x < 3) partial[3 * (long long)b + threadIdx.x] = s[threadIdx.x];
+}
+
+// one block per cloud: the sum of its chunk sums / its number of points (an empty cloud: zeros)
+__global__ void __launch_bounds__(256) k_centroid_finish(const double* __restrict__ partial, CloudChunks cc,
+                                                         double* __restrict__ centroids) {
+  __shared__ double sh[3][256];
+  const int c = blockIdx.x;
+  const int c0 = cc.chunk0[c], c1 = cc.chunk0[c + 1];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int j = c0 + threadIdx.x; j < c1; j += 256) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = __dadd_rn(s[k], partial[3 * (long long)j + k]);
+  }
+  tree_sum3(s, sh);
+  const long long n = cc.off[c + 1] - cc.off[c];
+  if (threadIdx.x < 3) centroids[3 * c + threadIdx.x] = n > 0 ? __ddiv_rn(s[threadIdx.x], (double)n) : 0.0;
+}
+
+// T_c = [R_c | R_c (-centroid_c)] (sample_random_trans / follow_presampled_trans, lib/colocation_data_loader.py:38-50), every
+// dot product as ((a b + c d) + e f) in fp64 without contraction; a cloud that is not rotated gets [I | 0]
+__global__ void k_cloud_affines(const double* __restrict__ aug, const double* __restrict__ centroids, int n_clouds,
+                                double* __restrict__ aff) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 3 * n_clouds) return;
+  const int c = i / 3, k = i - 3 * c;
+  double* o = aff + 12 * c + 4 * k;
+  if (aug[12 * c + 10] == 0.0) {
+    o[0] = k == 0; o[1] = k == 1; o[2] = k == 2; o[3] = 0.0;
+    return;
+  }
+  const double r0 = aug[12 * c + 3 * k], r1 = aug[12 * c + 3 * k + 1], r2 = aug[12 * c + 3 * k + 2];
+  const double* m = centroids + 3 * c;
+  o[0] = r0; o[1] = r1; o[2] = r2;
+  {
+#pragma clang fp contract(off)
+    o[3] = (r0 * -m[0] + r1 * -m[1]) + r2 * -m[2];
+  }
 }
 }  // namespace gcl
 
@@ -299,8 +445,70 @@ int gcl_voxel_coords_multi(const float* xyz, int64_t p, const int64_t* cloud_off
                 "gcl_voxel_coords_multi: 1 <= clouds <= 64, offsets[0] = 0, offsets[clouds] = p");
   CloudOffsets co;
   for (int c = 0; c <= n_clouds; ++c) co.off[c] = cloud_offsets_host[c];
-  hipLaunchKernelGGL(k_voxel_coords_multi, dim3((unsigned)cdiv(p, 256)), dim3(256), 0, (hipStream_t)stream, xyz, (long long)p,
-                     co, n_clouds, voxel, (int4*)coords);
+  hipLaunchKernelGGL(k_voxel_coords_multi<AUG_NONE>, dim3((unsigned)cdiv(p, 256)), dim3(256), 0, (hipStream_t)stream, xyz,
+                     (long long)p, co, n_clouds, voxel, 0.0, (const double*)nullptr, (const double*)nullptr, (int4*)coords);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+static bool offsets_ok(const int64_t* off, int32_t n_clouds, int64_t p) {
+  if (off[0] != 0 || off[n_clouds] != p) return false;
+  for (int c = 0; c < n_clouds; ++c)
+    if (off[c + 1] < off[c]) return false;
+  return true;
+}
+
+int gcl_voxel_coords_aug(const float* xyz, int64_t p, const int64_t* cloud_offsets_host, int32_t n_clouds, double voxel,
+                         const double* aug_dev, const double* aff_dev, int32_t mode, int32_t* coords, void* stream) {
+  GCL_CHECK_ARG(xyz && coords && cloud_offsets_host && aug_dev && aff_dev, "gcl_voxel_coords_aug: null pointer");
+  GCL_CHECK_ARG(p > 0 && voxel > 0 && (float)voxel > 0, "gcl_voxel_coords_aug: need points and a positive voxel size");
+  GCL_CHECK_ARG(mode == AUG_F32 || mode == AUG_F64, "gcl_voxel_coords_aug: mode is 1 (f32) or 2 (f64)");
+  GCL_CHECK_ARG(n_clouds >= 1 && n_clouds <= 64 && offsets_ok(cloud_offsets_host, n_clouds, p),
+                "gcl_voxel_coords_aug: 1 <= clouds <= 64, ascending offsets, offsets[0] = 0, offsets[clouds] = p");
+  CloudOffsets co;
+  for (int c = 0; c <= n_clouds; ++c) co.off[c] = cloud_offsets_host[c];
+  const dim3 grid((unsigned)cdiv(p, 256));
+  if (mode == AUG_F32)
+    hipLaunchKernelGGL(k_voxel_coords_multi<AUG_F32>, grid, dim3(256), 0, (hipStream_t)stream, xyz, (long long)p, co, n_clouds,
+                       (float)voxel, voxel, aug_dev, aff_dev, (int4*)coords);
+  else
+    hipLaunchKernelGGL(k_voxel_coords_multi<AUG_F64>, grid, dim3(256), 0, (hipStream_t)stream, xyz, (long long)p, co, n_clouds,
+                       (float)voxel, voxel, aug_dev, aff_dev, (int4*)coords);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_cloud_centroids_scratch_len(int64_t p, int32_t n_clouds) {
+  if (p < 0 || n_clouds < 0) return 0;
+  return 3 * (p / CENT_CHUNK + n_clouds);      // doubles: a cloud of n points has ceil(n / CENT_CHUNK) chunk sums
+}
+
+int gcl_cloud_centroids(const float* xyz, int64_t p, const int64_t* cloud_offsets_host, int32_t n_clouds, double* scratch,
+                        double* centroids, void* stream) {
+  GCL_CHECK_ARG(xyz && cloud_offsets_host && scratch && centroids, "gcl_cloud_centroids: null pointer");
+  GCL_CHECK_ARG(p > 0 && n_clouds >= 1 && n_clouds <= 64 && offsets_ok(cloud_offsets_host, n_clouds, p),
+                "gcl_cloud_centroids: 1 <= clouds <= 64, ascending offsets, offsets[0] = 0, offsets[clouds] = p > 0");
+  CloudChunks cc;
+  int64_t chunks = 0;
+  for (int c = 0; c <= n_clouds; ++c) {
+    cc.off[c] = cloud_offsets_host[c];
+    cc.chunk0[c] = (int)chunks;
+    if (c < n_clouds) chunks += cdiv(cloud_offsets_host[c + 1] - cloud_offsets_host[c], CENT_CHUNK);
+  }
+  GCL_CHECK_ARG(chunks <= INT_MAX / 4, "gcl_cloud_centroids: too many points");
+  hipLaunchKernelGGL(k_centroid_partials, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, xyz, cc, n_clouds, scratch);
+  GCL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_centroid_finish, dim3((unsigned)n_clouds), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, cc,
+                     centroids);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_cloud_affines(const double* aug_dev, const double* centroids, int32_t n_clouds, double* aff_dev, void* stream) {
+  GCL_CHECK_ARG(aug_dev && centroids && aff_dev, "gcl_cloud_affines: null pointer");
+  GCL_CHECK_ARG(n_clouds >= 1 && n_clouds <= 64, "gcl_cloud_affines: 1 <= clouds <= 64");
+  hipLaunchKernelGGL(k_cloud_affines, dim3((unsigned)cdiv(3 * n_clouds, 64)), dim3(64), 0, (hipStream_t)stream, aug_dev, centroids,
+                     n_clouds, aff_dev);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -319,8 +527,27 @@ int gcl_loader_points(const float* xyz_raw, const int64_t* index, const int32_t*
                       const double* to_center_dev, float* xyz_own, float* xyz_cf, void* stream) {
   GCL_CHECK_ARG(xyz_raw && index && coords && n_dev && to_center_dev && xyz_own && xyz_cf && n_max > 0,
                 "gcl_loader_points: bad argument");
-  hipLaunchKernelGGL(k_loader_points, dim3((unsigned)cdiv(n_max, 256)), dim3(256), 0, (hipStream_t)stream, xyz_raw,
-                     (const long long*)index, (const int4*)coords, (const int*)n_dev, to_center_dev, xyz_own, xyz_cf);
+  hipLaunchKernelGGL(k_loader_points<AUG_NONE>, dim3((unsigned)cdiv(n_max, 256)), dim3(256), 0, (hipStream_t)stream, xyz_raw,
+                     (const long long*)index, (const int4*)coords, (const int*)n_dev, to_center_dev, (const double*)nullptr,
+                     (const double*)nullptr, xyz_own, xyz_cf);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_loader_points_aug(const float* xyz_raw, const int64_t* index, const int32_t* coords, int64_t n_max, const int32_t* n_dev,
+                          const double* to_center_dev, const double* aug_dev, const double* aff_dev, int32_t mode,
+                          float* xyz_own, float* xyz_cf, void* stream) {
+  GCL_CHECK_ARG(xyz_raw && index && coords && n_dev && to_center_dev && aug_dev && aff_dev && xyz_own && xyz_cf,
+                "gcl_loader_points_aug: null pointer");
+  GCL_CHECK_ARG(n_max > 0, "gcl_loader_points_aug: need rows");
+  GCL_CHECK_ARG(mode == AUG_F32 || mode == AUG_F64, "gcl_loader_points_aug: mode is 1 (f32) or 2 (f64)");
+  const dim3 grid((unsigned)cdiv(n_max, 256));
+  if (mode == AUG_F32)
+    hipLaunchKernelGGL(k_loader_points<AUG_F32>, grid, dim3(256), 0, (hipStream_t)stream, xyz_raw, (const long long*)index,
+                       (const int4*)coords, (const int*)n_dev, to_center_dev, aug_dev, aff_dev, xyz_own, xyz_cf);
+  else
+    hipLaunchKernelGGL(k_loader_points<AUG_F64>, grid, dim3(256), 0, (hipStream_t)stream, xyz_raw, (const long long*)index,
+                       (const int4*)coords, (const int*)n_dev, to_center_dev, aug_dev, aff_dev, xyz_own, xyz_cf);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

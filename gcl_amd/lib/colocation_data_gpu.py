@@ -11,8 +11,9 @@ Replaces, with identical results, the CPU side of ``ColocationKittiDataset.__get
   need it, see gcl_amd/lib/colocation_trainer.py).
 * ``build_batch_gpu`` (round 6) -- the same batch dict from the raw scans of ``batch_size`` samples in ONE pass: all clouds
   through one coordinate table (two host synchronisations per batch instead of ~9 per sample, no host round trip for the
-  neighbours' centre-frame points); ``train_from_scans`` feeds ``FinestContrastiveLossTrainer.train_steps`` from raw scans
-  with that pass running a step ahead on its own stream.
+  neighbours' centre-frame points).  The loader's random rotation and scale (:349-370) are applied on the device when a
+  sample carries the draws (``"rotation"`` / ``"scale"``, gcl_amd/lib/augment.py makes them); ``train_from_scans`` feeds
+  ``FinestContrastiveLossTrainer.train_steps`` from raw scans with that pass running a step ahead on its own stream.
 """
 import ctypes
 import os
@@ -21,6 +22,9 @@ import numpy as np
 import torch
 
 from gcl_amd import _lib
+from gcl_amd.lib import augment
+
+AUG_F32, AUG_F64 = 1, 2          # the `mode` of gcl_voxel_coords_aug / gcl_loader_points_aug
 
 
 def _cap(n):
@@ -67,6 +71,21 @@ def sparse_quantize_gpu(xyz, voxel_size, batch_id=0, return_table=False):
     _lib.check(lib.gcl_voxel_coords(_lib.ptr(xyz, torch.float32), P, float(voxel_size), int(batch_id), _lib.ptr(raw),
                                     _lib.stream()), "gcl_voxel_coords")
     return unique_coords_gpu(raw, return_table)
+
+
+def cloud_centroids_gpu(xyz, offsets):
+    """Centroids float64 [n_clouds, 3] (device) of the clouds ``xyz[offsets[c]:offsets[c + 1]]`` of a float32 [P, 3] device
+    tensor (gcl_cloud_centroids): fp64 sums in a fixed order, so a cloud's centroid is bitwise the same alone, in any batch and
+    on every run -- what ``build_batch_gpu`` / ``build_pair_batch_gpu`` turn a cloud about; zeros for an empty cloud."""
+    lib = _lib.require_gpu()
+    xyz = xyz.contiguous()
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    n_clouds, P = len(offs) - 1, xyz.shape[0]
+    scratch = torch.empty(lib.gcl_cloud_centroids_scratch_len(P, n_clouds), dtype=torch.float64, device=xyz.device)
+    cent = torch.empty((n_clouds, 3), dtype=torch.float64, device=xyz.device)
+    _lib.check(lib.gcl_cloud_centroids(_lib.ptr(xyz, torch.float32), P, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                       n_clouds, _lib.ptr(scratch), _lib.ptr(cent), _lib.stream()), "gcl_cloud_centroids")
+    return cent
 
 
 def colocation_groups_gpu(xyz_own, xyz_cf, coords, n_center, n_clouds, list_M, voxel_size, radius, K=5):
@@ -229,9 +248,17 @@ def build_batch_gpu(raw_samples, voxel_size, device, K=5, jitter=None, stream=No
     """``ColocationKittiDataset.__getitem__`` x batch_size + ``collate_colocation_fn`` (lib/colocation_data_loader.py:315-475)
     from raw scans, on the device, in one pass over the whole batch.
 
-    ``raw_samples``: list of dicts ``{"xyz": [centre, nghb_0, ...] float32 [P_c, 3] host arrays (after the loader's rotation /
-    scale, :348-370), "list_M": [4 x 4 neighbour -> centre], "radius": the sample's matching radius (:361-365)}``; every
-    sample has the same number of clouds.  ``jitter`` (optional): ``callable(sample_no, n_center) -> float32 [n_center, 1]``
+    ``raw_samples``: list of dicts ``{"xyz": [centre, nghb_0, ...] float32 [P_c, 3] host arrays, "list_M": [4 x 4 neighbour ->
+    centre], "radius": the sample's matching radius (:361-365)}``; every sample has the same number of clouds.  The clouds are
+    either already augmented (after the loader's rotation / scale, :348-370), or the sample carries the DRAWS and the device
+    applies them (:349-370): ``"rotation"``, one 3 x 3 for the sample (``augment.sample_rotation``) -- every cloud is turned by
+    it about its own centroid, the neighbours following the centre as ``follow_presampled_trans`` does -- and / or ``"scale"``
+    (``augment.draw_scale``).  The points then go through the loader's float32 arithmetic (csrc/data.hip, AUG_F32; DESIGN.md
+    section 4), ``list_M[j]`` becomes ``T0 @ list_M[j] @ inv(Tc_j)`` with its translation scaled (fp64, on the host, from the
+    affines the first host read brings back) and ``radius`` becomes ``radius * scale``; ``list_M`` and ``radius`` are given
+    for the clouds as passed.  ValueError before any GPU work: a rotation with |R^T R - I| above 1e-6, a scale <= 0, an empty
+    cloud in a sample with a rotation.  Without the keys the path and its results are unchanged.
+    ``jitter`` (optional): ``callable(sample_no, n_center) -> float32 [n_center, 1]``
     added to the centre cloud's ones (the reference's ``Jitter`` transform draws it after voxelisation, :414-415).
     Returns the batch dict of ``collate_gpu`` (device tensors; ``index_hash`` None) + ``"cloud_rows"`` (rows per cloud).
     Work is enqueued on ``stream`` (default: the current stream); the two host reads wait for that stream only.
@@ -248,11 +275,19 @@ def build_batch_gpu(raw_samples, voxel_size, device, K=5, jitter=None, stream=No
     if n_clouds > 64:
         raise ValueError("at most 64 clouds per batch")
     sizes = [len(x) for s in raw_samples for x in s["xyz"]]
+    # the augmentation keys, checked before any GPU work; a batch without them takes the path it always took
+    rots = [augment.checked_rotation(s["rotation"]) if s.get("rotation") is not None else None for s in raw_samples]
+    scales = [augment.checked_scale(s["scale"]) if s.get("scale") is not None else None for s in raw_samples]
+    device_aug = any(r is not None for r in rots) or any(v is not None for v in scales)
+    for si, r in enumerate(rots):
+        if r is not None and min(sizes[si * n_c:(si + 1) * n_c]) == 0:
+            raise ValueError(f"sample {si}: an empty cloud has no centroid to rotate about")
     offs = np.zeros(n_clouds + 1, dtype=np.int64)
     offs[1:] = np.cumsum(sizes)
     P = int(offs[-1])
     # one pinned staging block: the points of all clouds, then the neighbour -> centre transforms (identity for a centre)
-    head = n_clouds * 24                     # the transforms first: their doubles stay 8-byte aligned for any P
+    n_tc = n_clouds * 24                     # the transforms first: their doubles stay 8-byte aligned for any P
+    head = n_tc * (2 if device_aug else 1)   # + the per-cloud table of the device's augmentation (augment.affine_rows)
     W = workspace
     import time
     tr = getattr(W, "trace", None)       # diagnostic (tools/micro/e2e_probe.py): wall time of the stages of a build
@@ -263,11 +298,12 @@ def build_batch_gpu(raw_samples, voxel_size, device, K=5, jitter=None, stream=No
         return W.take(name, shape, dtype) if W is not None else torch.empty(shape, dtype=dtype, device=dev)
 
     hp = host[head:].view(P, 3).numpy()
-    hm = host[:head].view(torch.float64).view(n_clouds, 12).numpy()
+    hm = host[:n_tc].view(torch.float64).view(n_clouds, 12).numpy()
+    ha = host[n_tc:head].view(torch.float64).view(n_clouds, 12).numpy() if device_aug else None
     ci = 0
     pool = _copy_pool()
     staged = []                         # per sample: the pending copies of its clouds into the pinned block
-    for s in raw_samples:
+    for si, s in enumerate(raw_samples):
         pend = []
         for c, x in enumerate(s["xyz"]):
             # numpy releases the interpreter lock for a plain copy of this size (36 MB per batch: 2.4 ms on one thread -- the
@@ -279,6 +315,8 @@ def build_batch_gpu(raw_samples, voxel_size, device, K=5, jitter=None, stream=No
             else:
                 hp[offs[ci]:offs[ci + 1]] = x
             hm[ci] = (np.eye(4) if c == 0 else np.asarray(s["list_M"][c - 1], dtype=np.float64))[:3].reshape(-1)
+            if device_aug:
+                ha[ci] = augment.affine_rows(rots[si], scales[si])
             ci += 1
         staged.append(pend)
     st_ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.stream(torch.cuda.current_stream(dev))
@@ -296,27 +334,60 @@ def build_batch_gpu(raw_samples, voxel_size, device, K=5, jitter=None, stream=No
             a, b = head + 3 * int(offs[si * n_c]), head + 3 * int(offs[(si + 1) * n_c])
             d[a:b].copy_(host[a:b], non_blocking=True)
         xyz_raw = d[head:]
-        to_center = d[:head]
+        to_center, aug_dev = d[:n_tc], d[n_tc:head]
         raw = tmp("raw", (P, 4), torch.int32)
-        _lib.check(lib.gcl_voxel_coords_multi(_lib.ptr(xyz_raw), P, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                              n_clouds, float(voxel_size), _lib.ptr(raw), st), "gcl_voxel_coords_multi")
+        off = lambda t, e: ctypes.c_void_p(t.data_ptr() + e * t.element_size())
+        offs_p = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        # meta: rows, status, the clouds' first rows and, behind them (8-byte aligned), the device's affines T_c as doubles
+        a0 = (8 + n_clouds + 1 + 1) // 2 * 2
+        meta = tmp("meta", (a0 + (24 * n_clouds if device_aug else 0),), torch.int32)
+        if device_aug:
+            cent = tmp("centroids", (3 * n_clouds,), torch.float64)
+            cscr = tmp("centroid_sums", (lib.gcl_cloud_centroids_scratch_len(P, n_clouds),), torch.float64)
+            _lib.check(lib.gcl_cloud_centroids(_lib.ptr(xyz_raw), P, offs_p, n_clouds, _lib.ptr(cscr), _lib.ptr(cent), st),
+                       "gcl_cloud_centroids")
+            _lib.check(lib.gcl_cloud_affines(_lib.ptr(aug_dev), _lib.ptr(cent), n_clouds, off(meta, a0), st), "gcl_cloud_affines")
+            _lib.check(lib.gcl_voxel_coords_aug(_lib.ptr(xyz_raw), P, offs_p, n_clouds, float(voxel_size), _lib.ptr(aug_dev),
+                                                off(meta, a0), AUG_F32, _lib.ptr(raw), st), "gcl_voxel_coords_aug")
+        else:
+            _lib.check(lib.gcl_voxel_coords_multi(_lib.ptr(xyz_raw), P, offs_p, n_clouds, float(voxel_size), _lib.ptr(raw), st),
+                       "gcl_voxel_coords_multi")
         cap = _cap(P)
         table = tmp("table", (cap, 2), torch.int64)
         scratch = tmp("scratch", (lib.gcl_scan_scratch_len(P),), torch.int32)
         coords = out("coords", (P, 4), torch.int32)
         index = tmp("index", (P,), torch.int64)
-        meta = tmp("meta", (8 + n_clouds + 1,), torch.int32)
-        off = lambda t, e: ctypes.c_void_p(t.data_ptr() + e * t.element_size())
         _lib.check(lib.gcl_unique_coords(_lib.ptr(raw), P, _lib.ptr(table), cap, _lib.ptr(scratch), _lib.ptr(coords),
                                          _lib.ptr(index), off(meta, 0), off(meta, 4), st), "gcl_unique_coords")
         _lib.check(lib.gcl_cloud_row_starts(_lib.ptr(coords), P, off(meta, 0), n_clouds, off(meta, 8), st),
                    "gcl_cloud_row_starts")
         xyz_own = out("xyz_own", (P, 3), torch.float32)
         xyz_cf = out("xyz_cf", (P, 3), torch.float32)
-        _lib.check(lib.gcl_loader_points(_lib.ptr(xyz_raw), _lib.ptr(index), _lib.ptr(coords), P, off(meta, 0),
-                                         _lib.ptr(to_center), _lib.ptr(xyz_own), _lib.ptr(xyz_cf), st), "gcl_loader_points")
-        t_1 = time.perf_counter()
-        m = meta.tolist()                                        # host read 1: rows, status, the clouds' first rows
+        list_Ms, radii = [s["list_M"] for s in raw_samples], [float(s["radius"]) for s in raw_samples]
+        if not device_aug:
+            _lib.check(lib.gcl_loader_points(_lib.ptr(xyz_raw), _lib.ptr(index), _lib.ptr(coords), P, off(meta, 0),
+                                             _lib.ptr(to_center), _lib.ptr(xyz_own), _lib.ptr(xyz_cf), st), "gcl_loader_points")
+            t_1 = time.perf_counter()
+            m = meta.tolist()                                    # host read 1: rows, status, the clouds' first rows
+        else:
+            t_1 = time.perf_counter()
+            mh = meta.cpu().numpy()                              # host read 1: the same + the clouds' affines T_c
+            m = mh[:a0].tolist()
+            T = [augment.affine4(r) for r in mh[a0:].view(np.float64).reshape(n_clouds, 12)]
+            # the neighbour -> centre transforms of the augmented clouds need the centroids, so the representatives' centre-frame
+            # points are made after this read (the upload is from pinned memory the first copy has long left)
+            for si, s in enumerate(raw_samples):
+                if rots[si] is not None or scales[si] is not None:
+                    list_Ms[si] = [augment.follow_list_M(T[si * n_c], M, T[si * n_c + 1 + j], scales[si])
+                                   for j, M in enumerate(s["list_M"])]
+                    for j, M in enumerate(list_Ms[si]):
+                        hm[si * n_c + 1 + j] = M[:3].reshape(-1)
+                if scales[si] is not None:
+                    radii[si] = radii[si] * scales[si]
+            to_center.copy_(host[:n_tc], non_blocking=True)
+            _lib.check(lib.gcl_loader_points_aug(_lib.ptr(xyz_raw), _lib.ptr(index), _lib.ptr(coords), P, off(meta, 0),
+                                                 _lib.ptr(to_center), _lib.ptr(aug_dev), off(meta, a0), AUG_F32,
+                                                 _lib.ptr(xyz_own), _lib.ptr(xyz_cf), st), "gcl_loader_points_aug")
         t_2 = time.perf_counter()
         if m[4]:
             raise ValueError(f"{m[4]} points outside the packable voxel range")
@@ -337,11 +408,11 @@ def build_batch_gpu(raw_samples, voxel_size, device, K=5, jitter=None, stream=No
         for si, s in enumerate(raw_samples):
             to_cloud = np.zeros((n_c, 12), dtype=np.float64)
             to_cloud[0] = np.eye(4)[:3].reshape(-1)
-            for j, M in enumerate(s["list_M"]):
+            for j, M in enumerate(list_Ms[si]):
                 to_cloud[j + 1] = np.linalg.inv(np.asarray(M, dtype=np.float64))[:3].reshape(-1)
             _lib.check(lib.gcl_colocation_hits_at(_lib.ptr(xyz_own), _lib.ptr(xyz_cf), starts[si * n_c], n_center[si],
                                                   si * n_c, n_c, to_cloud.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                  _lib.ptr(table), cap, float(1.0 / voxel_size), float(s["radius"]), K,
+                                                  _lib.ptr(table), cap, float(1.0 / voxel_size), radii[si], K,
                                                   off(hits, c0 * n_c * K), off(cnt, c0 * n_c), off(rng, c0 * n_c), st),
                        "gcl_colocation_hits_at")
             c0 += n_center[si]

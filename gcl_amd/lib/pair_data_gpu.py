@@ -5,8 +5,10 @@ correspondences (``get_matching_indices``, util/pointcloud.py:53-66) and the bat
 
 All 2 B clouds of a batch go through ONE coordinate table (cloud id 2 b + k, as ``build_batch_gpu`` does for the co-location
 batches), the matches of the whole batch are one count and one emit (csrc/pairmatch.hip), and the host reads twice: the row
-counts of the clouds, then the match totals.  The file readers, the ICP cache and the rotation / scale draws stay with the
-caller, as they do for ``build_batch_gpu``.
+counts of the clouds, then the match totals.  The loader's random rotations and scale (:476-492) are applied on the device when
+a pair carries the draws (``"rotation0"``, ``"rotation1"``, ``"scale"``; gcl_amd/lib/augment.py makes them), in the float64
+arithmetic the pair loaders keep through ``sparse_quantize``.  The file readers and the ICP cache stay with the caller, as they
+do for ``build_batch_gpu``.
 """
 import ctypes
 
@@ -14,7 +16,8 @@ import numpy as np
 import torch
 
 from gcl_amd import _lib
-from gcl_amd.lib.colocation_data_gpu import _cap
+from gcl_amd.lib import augment
+from gcl_amd.lib.colocation_data_gpu import AUG_F64, _cap
 from gcl_amd.util.pointcloud import matches_on_device, pack_params
 
 
@@ -26,6 +29,15 @@ def build_pair_batch_gpu(raw_pairs, voxel_size, device, K=None, stream=None):
     ``pcd0``, ``pcd1``, ``T_gt`` float32 [4 B', 4], ``len_batch``.  The reference's quirk is kept: a pair WITHOUT a match is
     left out of ``pcd0``, ``pcd1``, ``T_gt``, ``len_batch`` (B' pairs remain) and contributes no correspondence, but its rows
     stay in ``sinput*_C`` and the start indices move past it (:46-57).  ``K``: as ``get_matching_indices``' (None = all).
+    A pair may carry the loader's DRAWS instead of augmented clouds (:476-492): ``"rotation0"`` / ``"rotation1"`` (3 x 3, each
+    cloud turned about its own centroid: ``T_k = [R_k | R_k (-centroid_k)]``) and / or ``"scale"``.  The device then evaluates
+    ``scale * (x @ R.T + t)`` and ``floor(y / voxel_size)`` in float64 as the pair loaders do (lib/data_loaders.py:125-129;
+    csrc/data.hip, AUG_F64), ``pcd0`` / ``pcd1`` and the matching read the float32 of those points, ``trans`` becomes
+    ``T1 @ trans @ inv(T0)`` with its translation scaled (:479, lib/colocation_data_loader.py:369,
+    lib/complement_data_loader.py:662), ``T_gt`` is the float32 of that and ``radius`` becomes ``radius * scale`` (:490).
+    ``KITTIPairDataset`` itself leaves the translation unscaled, which puts its ground truth off by (1 - scale) |t|: that quirk
+    is NOT reproduced.  A cloud without a rotation stays float32 (``x * fp32(scale)``), as in the reference.  ValueError before
+    any GPU work: a rotation with |R^T R - I| above 1e-6, a scale <= 0, an empty cloud that has a rotation.
     Work is enqueued on ``stream`` (default: the current one); the two host reads wait for that stream only."""
     lib = _lib.require_gpu()
     dev = torch.device(device)
@@ -41,11 +53,22 @@ def build_pair_batch_gpu(raw_pairs, voxel_size, device, K=None, stream=None):
         raise ValueError("a batch without points")
     trans = [np.asarray(p["trans"], dtype=np.float64).reshape(4, 4) for p in raw_pairs]
     radii = [float(p["radius"]) for p in raw_pairs]
+    # the augmentation keys, checked before any GPU work; a batch without them takes the path it always took
+    rots = [augment.checked_rotation(p[k], k) if p.get(k) is not None else None for p in raw_pairs
+            for k in ("rotation0", "rotation1")]
+    scales = [augment.checked_scale(p["scale"]) if p.get("scale") is not None else None for p in raw_pairs]
+    device_aug = any(r is not None for r in rots) or any(v is not None for v in scales)
+    if any(r is not None and len(x) == 0 for r, x in zip(rots, clouds)):
+        raise ValueError("an empty cloud has no centroid to rotate about")
     # one pinned block, one copy: identity frames for gcl_loader_points (doubles first: they stay 8-byte aligned), T_gt as the
     # reference's .float() makes it, then the points of the 2 B clouds
-    head, tg = n_clouds * 24, B * 16
+    n_fr, tg = n_clouds * 24, B * 16
+    head = n_fr * (2 if device_aug else 1)      # + the per-cloud table of the device's augmentation (augment.affine_rows)
     host = torch.empty(head + tg + 3 * P, dtype=torch.float32, pin_memory=True)
-    host[:head].view(torch.float64).view(n_clouds, 12).numpy()[:] = np.eye(4)[:3].reshape(-1)
+    host[:n_fr].view(torch.float64).view(n_clouds, 12).numpy()[:] = np.eye(4)[:3].reshape(-1)
+    if device_aug:
+        host[n_fr:head].view(torch.float64).view(n_clouds, 12).numpy()[:] = np.stack(
+            [augment.affine_rows(rots[c], scales[c // 2]) for c in range(n_clouds)])
     host[head:head + tg].view(B, 4, 4).numpy()[:] = np.stack(trans).astype(np.float32)
     hp = host[head + tg:].view(P, 3).numpy()
     for c, x in enumerate(clouds):
@@ -55,26 +78,53 @@ def build_pair_batch_gpu(raw_pairs, voxel_size, device, K=None, stream=None):
         st = _lib.stream()
         d = torch.empty(host.numel(), dtype=torch.float32, device=dev)
         d.copy_(host, non_blocking=True)
-        frames, T_all, xyz_raw = d[:head], d[head:head + tg].view(4 * B, 4), d[head + tg:]
+        frames, aug_dev, T_all, xyz_raw = d[:n_fr], d[n_fr:head], d[head:head + tg].view(4 * B, 4), d[head + tg:]
         raw = torch.empty((P, 4), dtype=torch.int32, device=dev)
-        _lib.check(lib.gcl_voxel_coords_multi(_lib.ptr(xyz_raw), P, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                              n_clouds, float(voxel_size), _lib.ptr(raw), st), "gcl_voxel_coords_multi")
+        off = lambda t, e: ctypes.c_void_p(t.data_ptr() + e * t.element_size())
+        offs_p = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        # meta: rows, status, the clouds' first rows and, behind them (8-byte aligned), the device's affines T_c as doubles
+        a0 = (8 + n_clouds + 1 + 1) // 2 * 2
+        meta = torch.empty(a0 + (24 * n_clouds if device_aug else 0), dtype=torch.int32, device=dev)
+        if device_aug:
+            cent = torch.empty(3 * n_clouds, dtype=torch.float64, device=dev)
+            cscr = torch.empty(lib.gcl_cloud_centroids_scratch_len(P, n_clouds), dtype=torch.float64, device=dev)
+            _lib.check(lib.gcl_cloud_centroids(_lib.ptr(xyz_raw), P, offs_p, n_clouds, _lib.ptr(cscr), _lib.ptr(cent), st),
+                       "gcl_cloud_centroids")
+            _lib.check(lib.gcl_cloud_affines(_lib.ptr(aug_dev), _lib.ptr(cent), n_clouds, off(meta, a0), st), "gcl_cloud_affines")
+            _lib.check(lib.gcl_voxel_coords_aug(_lib.ptr(xyz_raw), P, offs_p, n_clouds, float(voxel_size), _lib.ptr(aug_dev),
+                                                off(meta, a0), AUG_F64, _lib.ptr(raw), st), "gcl_voxel_coords_aug")
+        else:
+            _lib.check(lib.gcl_voxel_coords_multi(_lib.ptr(xyz_raw), P, offs_p, n_clouds, float(voxel_size), _lib.ptr(raw), st),
+                       "gcl_voxel_coords_multi")
         cap = _cap(P)
         table = torch.empty((cap, 2), dtype=torch.int64, device=dev)
         scratch = torch.empty(lib.gcl_scan_scratch_len(P), dtype=torch.int32, device=dev)
         coords = torch.empty((P, 4), dtype=torch.int32, device=dev)
         index = torch.empty(P, dtype=torch.int64, device=dev)
-        meta = torch.empty(8 + n_clouds + 1, dtype=torch.int32, device=dev)
-        off = lambda t, e: ctypes.c_void_p(t.data_ptr() + e * t.element_size())
         _lib.check(lib.gcl_unique_coords(_lib.ptr(raw), P, _lib.ptr(table), cap, _lib.ptr(scratch), _lib.ptr(coords),
                                          _lib.ptr(index), off(meta, 0), off(meta, 4), st), "gcl_unique_coords")
         _lib.check(lib.gcl_cloud_row_starts(_lib.ptr(coords), P, off(meta, 0), n_clouds, off(meta, 8), st),
                    "gcl_cloud_row_starts")
         xyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
         xyz_cf = torch.empty((P, 3), dtype=torch.float32, device=dev)      # identity frames: a second copy nobody reads
-        _lib.check(lib.gcl_loader_points(_lib.ptr(xyz_raw), _lib.ptr(index), _lib.ptr(coords), P, off(meta, 0),
-                                         _lib.ptr(frames), _lib.ptr(xyz), _lib.ptr(xyz_cf), st), "gcl_loader_points")
-        m = meta.tolist()                                        # host read 1: rows, status, the clouds' first rows
+        if not device_aug:
+            _lib.check(lib.gcl_loader_points(_lib.ptr(xyz_raw), _lib.ptr(index), _lib.ptr(coords), P, off(meta, 0),
+                                             _lib.ptr(frames), _lib.ptr(xyz), _lib.ptr(xyz_cf), st), "gcl_loader_points")
+            m = meta.tolist()                                    # host read 1: rows, status, the clouds' first rows
+        else:
+            _lib.check(lib.gcl_loader_points_aug(_lib.ptr(xyz_raw), _lib.ptr(index), _lib.ptr(coords), P, off(meta, 0),
+                                                 _lib.ptr(frames), _lib.ptr(aug_dev), off(meta, a0), AUG_F64, _lib.ptr(xyz),
+                                                 _lib.ptr(xyz_cf), st), "gcl_loader_points_aug")
+            mh = meta.cpu().numpy()                              # host read 1: the same + the clouds' affines T_c
+            m = mh[:a0].tolist()
+            T = [augment.affine4(r) for r in mh[a0:].view(np.float64).reshape(n_clouds, 12)]
+            for b in range(B):
+                trans[b] = augment.follow_pair_trans(T[2 * b], T[2 * b + 1], trans[b], scales[b])
+                if scales[b] is not None:
+                    radii[b] = radii[b] * scales[b]
+            # T_gt of the augmented pairs: the pinned block's first copy has long left it
+            host[head:head + tg].view(B, 4, 4).numpy()[:] = np.stack(trans).astype(np.float32)
+            d[head:head + tg].copy_(host[head:head + tg], non_blocking=True)
         if m[4]:
             raise ValueError(f"{m[4]} points outside the packable voxel range")
         starts = m[8:8 + n_clouds + 1]

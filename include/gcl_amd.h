@@ -133,6 +133,30 @@ int gcl_colocation_hits_at(const float* xyz_own, const float* xyz_cf, int64_t ro
                            int32_t n_clouds, const double* to_cloud_host, const int64_t* table, int64_t cap, float inv_voxel,
                            double radius, int32_t K, int32_t* hits, int32_t* cnt, double* first_rng, void* stream);
 
+/* The loader's augmentation on the device (lib/colocation_data_loader.py:349-370, lib/data_loaders.py:476-492): every cloud
+ * turned about its centroid, the sample's scale applied, inside the two passes above that touch every point.
+ *   gcl_cloud_centroids     centroids double[n_clouds][3] of the clouds of gcl_voxel_coords_multi's layout: fp64 sums of the fp32
+ *                           points in a fixed order (no atomics) / the number of points; bitwise the same for a cloud alone,
+ *                           anywhere in any batch and on every run; zeros for an empty cloud.  scratch: device
+ *                           double[gcl_cloud_centroids_scratch_len(p, n_clouds)].
+ *   gcl_cloud_affines       aff double[n_clouds][12] (row-major 3 x 4) = T_c = [R_c | R_c (-centroid_c)], every dot product
+ *                           ((a b + c d) + e f) in fp64, uncontracted.  aug_dev: DEVICE double[n_clouds][12] = R_c (9, row-major),
+ *                           the scale (1.0: none), rotated (0.0 / 1.0), one spare; a cloud with rotated = 0 gets [I | 0].
+ *   gcl_voxel_coords_aug    gcl_voxel_coords_multi of the augmented points.  mode 1 (f32, the co-location loaders): T_c rounded
+ *                           to fp32, y = (((x0 r0 + x1 r1) + x2 r2) + t) * fp32(scale) in fp32, floor(y / fp32(voxel)); mode 2
+ *                           (f64, the pair loaders): y = scale * (((x0 r0 + x1 r1) + x2 r2) + t) in fp64, floor(y / voxel) by
+ *                           fp64 division.  A cloud with rotated = 0 is y = x * fp32(scale) in fp32 in both modes.
+ *   gcl_loader_points_aug   gcl_loader_points with xyz_own[i] = that y (mode 2: fp32(y)) of point index[i]; xyz_cf from xyz_own. */
+int64_t gcl_cloud_centroids_scratch_len(int64_t p, int32_t n_clouds);
+int gcl_cloud_centroids(const float* xyz, int64_t p, const int64_t* cloud_offsets_host, int32_t n_clouds, double* scratch,
+                        double* centroids, void* stream);
+int gcl_cloud_affines(const double* aug_dev, const double* centroids, int32_t n_clouds, double* aff_dev, void* stream);
+int gcl_voxel_coords_aug(const float* xyz, int64_t p, const int64_t* cloud_offsets_host, int32_t n_clouds, double voxel,
+                         const double* aug_dev, const double* aff_dev, int32_t mode, int32_t* coords, void* stream);
+int gcl_loader_points_aug(const float* xyz_raw, const int64_t* index, const int32_t* coords, int64_t n_max, const int32_t* n_dev,
+                          const double* to_center_dev, const double* aug_dev, const double* aff_dev, int32_t mode,
+                          float* xyz_own, float* xyz_cf, void* stream);
+
 /* HOST function (no GPU, every pointer is a HOST pointer): numpy's legacy np.random.choice(n, k, replace=False) =
  * permutation(n)[:k] -- the three draws of every training step (lib/colocation_trainer.py:457, :506-507) -- reproduced
  * bit for bit from the RandomState's MT19937 state (key[624], *pos as in np.random.get_state(); both updated in place so
