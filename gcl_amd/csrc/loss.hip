@@ -297,15 +297,19 @@ __global__ void __launch_bounds__(64) k_circle_group_bwd(const float* __restrict
     if (lane < c && gr != 0.f) atomicAdd(&df[row * c + lane], gr);
   }
   if (lane < c && gt != 0.f) atomicAdd(&df[index[g.tpos] * c + lane], gt);
-  if ((flags & GL_PAIR) && gp != 0.f && lane < c) {
+  if ((flags & GL_PAIR) && gp != 0.f) {                  // wave-uniform
     const int* pp = pairpos + 2 * blockIdx.x;
     const long long ra = index[b + pp[0]], rb = index[b + pp[1]];
-    const float diff = f[ra * c + lane] - f[rb * c + lane];
-    const float d2 = wave_sum(diff * diff);
+    const float diff = (lane < c) ? f[ra * c + lane] - f[rb * c + lane] : 0.f;
+    const float d2 = wave_sum(diff * diff);              // all lanes take part in the reduction: inside `lane < c` a lane
+                                                         // read its switched-off partners as 0 and, at a width that is no
+                                                         // power of two, ended with a partial sum
     const float dist = sq ? d2 : sqrtf(d2 + 1e-7f);
     const float coef = gp * sigmoid_f(dist - pos_thresh) * (sq ? 2.f : 1.f / dist);
-    atomicAdd(&df[ra * c + lane], coef * diff);
-    atomicAdd(&df[rb * c + lane], -coef * diff);
+    if (lane < c) {
+      atomicAdd(&df[ra * c + lane], coef * diff);
+      atomicAdd(&df[rb * c + lane], -coef * diff);
+    }
   }
 }
 

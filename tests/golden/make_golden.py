@@ -1,6 +1,7 @@
 """Generates tests/golden/*.npz by IMPORTING the reference's own Python (this container only).
 
 Run:  python tests/golden/make_golden.py        (needs /root/reference; writes small .npz fixtures)
+      python tests/golden/make_golden.py widths (only the cases at 16 / 64 channels and the further switch sets)
 
 The reference never travels to the GPU box: only the arrays written here do (inputs, the exact RNG
 draws, outputs, gradients).  What is captured, and from where:
@@ -117,8 +118,34 @@ def main():
     _finest_cases(Trainer, _exhaustive_hash, None)
 
 
-def _finest_cases(Trainer, _exhaustive_hash, only):
+# the recorded cases beyond 32 channels and beyond the switch sets of _finest_cases / circle_golden: <= 1000 rows each, so
+# that a file stays below the smallest of the first fixtures
+_small = dict(N=1000, n_groups=60, sizes=[2, 3, 5, 8, 16, 35], max_pos=48, max_hn=256)
+FINEST_WIDTH_CASES = {
+    16: {"w16_s10": dict(_small, seed=10), "w16sqrt_s15": dict(_small, seed=15, square_loss=False)},
+    64: {"w64_s11": dict(_small, seed=11, N=600, n_groups=50)},
+    32: {"sqrtblock_s12": dict(_small, seed=12, square_loss=False, block_finest_gradient=True),
+         "sqrtpair_s13": dict(_small, seed=13, square_loss=False, use_pair_group_positive_loss=True),
+         "blockpair_s14": dict(_small, seed=14, block_finest_gradient=True, use_pair_group_positive_loss=True)},
+}
+_small_c = dict(N=1000, n_groups=60, max_pos=48, batch_lengths=[400, 300, 300], block_finest_gradient=False)
+CIRCLE_SWITCH_CASES = {"c4": dict(_small_c, seed=24, square_loss=False),
+                       "c5": dict(_small_c, seed=25, use_pair_group_positive_loss=True),
+                       "c6": dict(_small_c, seed=26, square_loss=False, use_pair_group_positive_loss=True)}
+
+
+def width_and_switch_cases():
+    """Only the cases above (``python tests/golden/make_golden.py widths``): the first fixtures are left as they are."""
+    _, _, _, _, _exhaustive_hash, Trainer = _import_reference()
+    torch.set_num_threads(4)
+    for width, cases in FINEST_WIDTH_CASES.items():
+        _finest_cases(Trainer, _exhaustive_hash, None, width=width, cases=cases)
+    circle_golden(Trainer, _exhaustive_hash, cases=CIRCLE_SWITCH_CASES)
+
+
+def _finest_cases(Trainer, _exhaustive_hash, only, width=32, cases=None):
     # ---- finest_contrastive_loss ---------------------------------------------------------------
+    given = cases
     cases = {
         "var_s0": dict(seed=0, N=4000, n_groups=200, sizes=[2, 3, 5, 7, 16, 35], max_pos=64, max_hn=512),
         "g16_s1": dict(seed=1, N=6000, n_groups=300, sizes=[16], max_pos=128, max_hn=1024),
@@ -139,20 +166,22 @@ def _finest_cases(Trainer, _exhaustive_hash, only):
                        use_pair_group_positive_loss=True),
         "loc_s9": dict(base, seed=9, fn="location_contrastive_loss", square_loss=False),   # always the sqrt form
     })
+    if given is not None:
+        cases = given
     for name, c in cases.items():
         if only and name != only:
             continue
         rng = np.random.RandomState(c["seed"])
         gt = torch.Generator().manual_seed(c["seed"])
         N = c["N"]
-        Fo = _unit_rows(gt, N, 32)
+        Fo = _unit_rows(gt, N, width)
         group, index, finest = make_groups(rng, N, c["n_groups"], c["sizes"])
         # make group members similar (anchor + noise) and plant near-duplicate NON-group rows so that the
         # hardest negatives are below the 1.4 threshold and some of them hit the positive-pair mask
         p = 0
         for gsz in group:
             rows = index[p:p + gsz]
-            Fo[rows] = Fo[rows[0]] + 0.25 * torch.randn(gsz, 32, generator=gt)
+            Fo[rows] = Fo[rows[0]] + 0.25 * torch.randn(gsz, width, generator=gt)
             p += gsz
         Fo = Fo / Fo.norm(dim=1, keepdim=True)
         Fo = Fo.clone().requires_grad_(True)
@@ -226,16 +255,17 @@ def hardest_golden():
         print("hardest", seed, pos.item(), neg.item())
 
 
-def circle_golden(Trainer, _exhaustive_hash):
+def circle_golden(Trainer, _exhaustive_hash, width=32, cases=None):
     """location_circle_loss (lib/colocation_trainer.py:538-681) with its switches."""
-    cases = {"c0": dict(seed=20), "c1": dict(seed=21, square_loss=False), "c2": dict(seed=22, block_finest_gradient=False),
-             "c3": dict(seed=23, use_pair_group_positive_loss=True)}
+    if cases is None:
+        cases = {"c0": dict(seed=20), "c1": dict(seed=21, square_loss=False), "c2": dict(seed=22, block_finest_gradient=False),
+                 "c3": dict(seed=23, use_pair_group_positive_loss=True)}
     for name, c in cases.items():
         rng = np.random.RandomState(c["seed"])
         gt = torch.Generator().manual_seed(c["seed"])
-        N, n_groups, max_pos = 3000, 160, 96
-        batch_lengths = [1100, 900, 1000]
-        Fo = _unit_rows(gt, N, 32)
+        N, n_groups, max_pos = c.get("N", 3000), c.get("n_groups", 160), c.get("max_pos", 96)
+        batch_lengths = c.get("batch_lengths", [1100, 900, 1000])
+        Fo = _unit_rows(gt, N, width)
         # groups stay inside one sample and are ordered by sample, as the collate function produces them
         group, index, finest = [], [], []
         starts = np.concatenate([[0], np.cumsum(batch_lengths)])
@@ -252,7 +282,7 @@ def circle_golden(Trainer, _exhaustive_hash):
         p = 0
         for gsz in group:
             rows = index[p:p + gsz]
-            Fo[rows] = Fo[rows[0]] + 0.25 * torch.randn(int(gsz), 32, generator=gt)
+            Fo[rows] = Fo[rows[0]] + 0.25 * torch.randn(int(gsz), width, generator=gt)
             p += gsz
         Fo = (Fo / Fo.norm(dim=1, keepdim=True)).clone().requires_grad_(True)
         points = torch.from_numpy(rng.randint(-40, 40, (N, 3)).astype(np.int32))
@@ -347,6 +377,9 @@ def validation_golden(Trainer):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:] == ["widths"]:
+        width_and_switch_cases()
+        sys.exit(0)
     main()
     if os.environ.get("GCL_GOLDEN_ONLY"):
         sys.exit(0)
@@ -354,3 +387,4 @@ if __name__ == "__main__":
     sc2pcr_golden()
     circle_golden(*_TRAINER_AND_HASH)
     validation_golden(_TRAINER_AND_HASH[0])
+    width_and_switch_cases()
