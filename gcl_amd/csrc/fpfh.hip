@@ -18,6 +18,7 @@
 // Every loop over the lists or the grid is bounded by max_nn, by 64 halvings or by the number of points; a list entry is
 // used only after it has been checked against [0, n), so a -1 (or any stale word) is never dereferenced.
 #include "common.h"
+#include "fpgrid.h"
 
 #include <math.h>
 
@@ -29,7 +30,6 @@ namespace gcl {
 constexpr int FP_THREADS = 256, FP_WAVES = FP_THREADS / 64;
 constexpr int FP_MAX_NN = 128;          // GCL_FPFH_MAX_NN
 constexpr int FP_BINS = 33;
-constexpr int FP_CELL_MAX = 32767, FP_CELL_MIN = -32768;
 constexpr int FP_SWEEPS = 12;           // cyclic Jacobi on a symmetric 3 x 3 converges quadratically: 6 - 7 sweeps reach 1e-16
 
 #define FP_WAVE_SYNC()                                      \
@@ -38,33 +38,6 @@ constexpr int FP_SWEEPS = 12;           // cyclic Jacobi on a symmetric 3 x 3 co
     __builtin_amdgcn_wave_barrier();                        \
   } while (0)
 
-// d2 = (dx dx + dy dy) + dz dz, each operation rounded (an fma would give other bits)
-__device__ __forceinline__ double fp_d2(double ax, double ay, double az, double bx, double by, double bz) {
-  const double dx = ax - bx, dy = ay - by, dz = az - bz;
-  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
-// cloud of row i: the b with off[b] <= i < off[b + 1] (off ascending, off[0] = 0, off[B] = n); at most 32 halvings
-__device__ __forceinline__ int fp_cloud_of(const long long* __restrict__ off, int B, long long i) {
-  int lo = 0, hi = B - 1;
-  for (int it = 0; it < 32 && lo < hi; ++it) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int fp_cell(float x, double inv_edge) {
-  const double c = floor((double)x * inv_edge);
-  // the clamp is monotone and 1-Lipschitz: two cells that differ by at most one still do after it, so the 27-cell scan stays
-  // complete; a non-finite coordinate lands in a border cell and fails the distance test there
-  return c >= (double)FP_CELL_MAX ? FP_CELL_MAX : (c <= (double)FP_CELL_MIN ? FP_CELL_MIN : (int)c);
-}
-__device__ __forceinline__ long long fp_key(int b, int cx, int cy, int cz) {
-  return ((long long)b << 48) | ((long long)(cx - FP_CELL_MIN) << 32) | ((long long)(cy - FP_CELL_MIN) << 16) |
-         (long long)(cz - FP_CELL_MIN);
-}
-
 __global__ void __launch_bounds__(FP_THREADS) k_fpfh_cell_keys(const float* __restrict__ xyz, long long n,
                                                               const long long* __restrict__ off, int B, double inv_edge,
                                                               long long* __restrict__ keys) {
@@ -72,16 +45,6 @@ __global__ void __launch_bounds__(FP_THREADS) k_fpfh_cell_keys(const float* __re
   if (i >= n) return;
   const int b = fp_cloud_of(off, B, i);
   keys[i] = fp_key(b, fp_cell(xyz[3 * i], inv_edge), fp_cell(xyz[3 * i + 1], inv_edge), fp_cell(xyz[3 * i + 2], inv_edge));
-}
-
-// first position in the ascending keys[0, n) whose key is >= k; at most 64 halvings
-__device__ __forceinline__ long long fp_lower_bound(const long long* __restrict__ keys, long long n, long long k) {
-  long long lo = 0, hi = n;
-  for (int it = 0; it < 64 && lo < hi; ++it) {
-    const long long mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 __device__ __forceinline__ bool fp_less(double da, int ra, double db, int rb) { return da < db || (da == db && ra < rb); }
@@ -361,11 +324,6 @@ __global__ void __launch_bounds__(FP_THREADS) k_fpfh_combine(const float* __rest
     r = (float)((double)r / (sqrt(sq) + 1e-6));
   }
   if (lane < FP_BINS) out[i * FP_BINS + lane] = r;
-}
-
-static inline double fp_inv_edge(float radius) {
-  // an edge a little above the radius: two points with d2 <= r2 as rounded are never two cells apart
-  return 1.0 / ((double)radius * 1.000001);
 }
 
 }  // namespace gcl

@@ -1,5 +1,5 @@
 // The fp64 3 x 3 Kabsch solution shared by the registration back-ends (sc2pcr.hip: weighted, per seed and per refinement
-// step; ransac.hip: unweighted, per minimal sample).
+// step; ransac.hip: unweighted, per minimal sample; icp.hip: the fp64 rotation, per ICP update).
 #pragma once
 #include "common.h"
 
@@ -9,7 +9,10 @@ namespace gcl {
 
 // ---- 3 x 3 SVD (one-sided Jacobi, fp64) and the weighted Kabsch solution (common.py:7-45) ---------------------
 // H = A^T W B;  R = V diag(1, 1, det(V U^T)) U^T with singular values in DESCENDING order (torch.svd);  t = cb - R ca
-static __device__ void kabsch_from_H(const double H[9], const double ca[3], const double cb[3], float* T12) {
+// One body, two exits: PACK = true rounds R and t to the 3 x 4 float rows the registration kernels keep (kabsch_from_H);
+// PACK = false hands out the fp64 rotation before any packing (kabsch_rotation, R9 row-major).
+template <bool PACK>
+static __device__ void kabsch_solve(const double H[9], const double ca[3], const double cb[3], float* T12, double* R9) {
   double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) A[i][j] = H[3 * i + j];
@@ -71,11 +74,21 @@ static __device__ void kabsch_from_H(const double H[9], const double ca[3], cons
   double R[3][3];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) R[i][j] = Vs[i][0] * U[j][0] + Vs[i][1] * U[j][1] + d * Vs[i][2] * U[j][2];
+  if constexpr (!PACK) {
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) R9[3 * i + j] = R[i][j];
+    return;
+  }
   for (int i = 0; i < 3; ++i) {
     const float r0 = (float)R[i][0], r1 = (float)R[i][1], r2 = (float)R[i][2];
     T12[4 * i] = r0; T12[4 * i + 1] = r1; T12[4 * i + 2] = r2;
     T12[4 * i + 3] = (float)(cb[i] - ((double)r0 * ca[0] + (double)r1 * ca[1] + (double)r2 * ca[2]));
   }
 }
+
+static __device__ void kabsch_from_H(const double H[9], const double ca[3], const double cb[3], float* T12) {
+  kabsch_solve<true>(H, ca, cb, T12, nullptr);
+}
+static __device__ void kabsch_rotation(const double H[9], double R9[9]) { kabsch_solve<false>(H, nullptr, nullptr, nullptr, R9); }
 
 }  // namespace gcl

@@ -7,8 +7,8 @@ All 2 B clouds of a batch go through ONE coordinate table (cloud id 2 b + k, as 
 batches), the matches of the whole batch are one count and one emit (csrc/pairmatch.hip), and the host reads twice: the row
 counts of the clouds, then the match totals.  The loader's random rotations and scale (:476-492) are applied on the device when
 a pair carries the draws (``"rotation0"``, ``"rotation1"``, ``"scale"``; gcl_amd/lib/augment.py makes them), in the float64
-arithmetic the pair loaders keep through ``sparse_quantize``.  The file readers and the ICP cache stay with the caller, as they
-do for ``build_batch_gpu``.
+arithmetic the pair loaders keep through ``sparse_quantize``.  The file readers and the ICP cache files stay with the caller, as
+they do for ``build_batch_gpu``; the ICP refinement that makes a pair's ``"trans"`` is ``gcl_amd.lib.icp.refine_pair_poses``.
 """
 import ctypes
 

@@ -1098,6 +1098,42 @@ int gcl_val_stats_batch(const float* src, const float* tgt, int64_t total, const
                         int64_t total0, const int64_t* offsets0, int32_t B, const double* T_est, const double* T_gt,
                         const int32_t* status, double max_dist, double thresh, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Point-to-point ICP for a ragged batch of n_pairs scan pairs (csrc/icp.hip): open3d's registration_icp with
+ * TransformationEstimationPointToPoint, restated from its published source (DESIGN.md "ICP" holds the semantics and the two
+ * deviations), as the pair loaders refine the odometry pose with it (lib/data_loaders.py:447-474,
+ * lib/complement_data_loader.py:369-399) and scripts/SC2_PCR/benchmark_utils.py:40-56 offers it.  All arithmetic is fp64.
+ *   xyz0 [total0, 3], xyz1 [total1, 3]   sources and targets; pair b owns the rows offsets[b] .. offsets[b + 1] - 1
+ *   offsets0_host / offsets1_host        HOST int64 [n_pairs + 1], ascending from 0 to total0 / total1 (<= 2^31 - 1), checked
+ *                                        before anything is launched; offsets0 / offsets1: the same numbers on the DEVICE
+ *   sorted_keys, order                   gcl_fpfh_cell_keys(xyz1, total1, offsets1, n_pairs, (float)max_correspondence_distance)
+ *                                        sorted ascending, and the permutation (`order[s]` = target row of the s-th key)
+ *   init  double [n_pairs, 16]           row-major 4 x 4, T_0
+ * Iteration k pairs every source point p = T_k x with the target row of its own pair that minimises
+ * d2 = (dx dx + dy dy) + dz dz (every operation rounded) among those with d2 <= double(max_correspondence_distance)^2, ties
+ * to the lowest row; n_corr, fitness = n_corr / n_source and inlier_rmse = sqrt(sum d2 / n_corr) are the result under T_k;
+ * the update is the Kabsch solution U without scale over the pairs (p, q) and T_k+1 = U T_k.  The result under T_0 is
+ * evaluated first; then up to max_iteration times: update, evaluate, stop when |d fitness| < relative_fitness and
+ * |d inlier_rmse| < relative_rmse.  Outputs per pair:
+ *   T      double [n_pairs, 16]   the final transformation (init's fourth row is kept)
+ *   stats  double [n_pairs, 4]    fitness, inlier_rmse, n_corr under T; the number of updates applied
+ *   status int32 [n_pairs]        0; 1: an empty source or target or no correspondence at some evaluation; 2: one or two
+ *                                 correspondences (the solution is not unique).  1 and 2 stop the pair with the T and the
+ *                                 result of that evaluation; they are looked at before the convergence test.
+ *   corr   int32 [total0]         optional: the target row WITHIN the pair's own target under the final T, or -1
+ * The call enqueues one set-up launch and max_iteration + 1 pairs of launches (step, update); the blocks of a finished pair
+ * return at once.  Nothing is read back, the host never waits, there are no atomics: a pair's T, stats and corr are bitwise
+ * the same alone, anywhere in any batch and on every run.  scratch: gcl_icp_scratch_bytes(total0, total1, n_pairs) bytes (16 per target
+ * for the targets in cell order, 136 per 256 source rows for the partial sums); the query returns 0 for arguments out of
+ * range.  1 <= n_pairs <= GCL_FPFH_MAX_CLOUDS, 0 <= max_iteration <= 1 000 000.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t gcl_icp_scratch_bytes(int64_t total0, int64_t total1, int32_t n_pairs);
+int gcl_icp_register_batch(const float* xyz0, const int64_t* offsets0_host, const int64_t* offsets0, const float* xyz1,
+                           const int64_t* offsets1_host, const int64_t* offsets1, int32_t n_pairs,
+                           const int64_t* sorted_keys, const int64_t* order, double max_correspondence_distance,
+                           const double* init, int32_t max_iteration, double relative_fitness, double relative_rmse,
+                           void* scratch, double* T, double* stats, int32_t* status, int32_t* corr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
