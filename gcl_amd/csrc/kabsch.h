@@ -12,7 +12,7 @@ namespace gcl {
 // One body, two exits: PACK = true rounds R and t to the 3 x 4 float rows the registration kernels keep (kabsch_from_H);
 // PACK = false hands out the fp64 rotation before any packing (kabsch_rotation, R9 row-major).
 template <bool PACK>
-static __device__ void kabsch_solve(const double H[9], const double ca[3], const double cb[3], float* T12, double* R9) {
+static __host__ __device__ void kabsch_solve(const double H[9], const double ca[3], const double cb[3], float* T12, double* R9) {
   double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) A[i][j] = H[3 * i + j];
@@ -86,9 +86,9 @@ static __device__ void kabsch_solve(const double H[9], const double ca[3], const
   }
 }
 
-static __device__ void kabsch_from_H(const double H[9], const double ca[3], const double cb[3], float* T12) {
+static __host__ __device__ void kabsch_from_H(const double H[9], const double ca[3], const double cb[3], float* T12) {
   kabsch_solve<true>(H, ca, cb, T12, nullptr);
 }
-static __device__ void kabsch_rotation(const double H[9], double R9[9]) { kabsch_solve<false>(H, nullptr, nullptr, nullptr, R9); }
+static __host__ __device__ void kabsch_rotation(const double H[9], double R9[9]) { kabsch_solve<false>(H, nullptr, nullptr, nullptr, R9); }
 
 }  // namespace gcl
