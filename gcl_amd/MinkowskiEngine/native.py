@@ -10,6 +10,11 @@
 Both issue exactly the launches of the per-operator path (same entry points, same arguments, same order), so losses
 and parameters stay bitwise equal (tests/test_gpu_plan.py); what disappears is ~560 Python -> ctypes round trips per
 training step.  There is no CPU path here either: everything raises without the library / a GPU.
+
+One exception to "the same launches": a caller that knows which rows of the output gradient can be non-zero
+(``NetworkPlan.set_touched_rows`` / ``touch_loss_rows``: the trainer's group loss writes ~7 % of the rows) has the row-local
+records at the network's end -- conv1_tr, ReLU, final, the row normalisation -- run on those rows only.  Everything upstream stays
+bitwise; the gradients of those records' own parameters become sums over fewer rows (tests/test_gpu_head_touched_rows.py).
 """
 import ctypes
 import os
@@ -201,6 +206,7 @@ class NetworkPlan:
         self._anchor = None
         self._aux = None
         self._eval_key = None
+        self._touched = None
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -472,6 +478,32 @@ class NetworkPlan:
             segs.append((0, hi, []))
         return segs
 
+    def set_touched_rows(self, rows, cap):
+        """``rows`` (int32 device tensor, at least ``cap`` entries: the distinct rows of the output whose gradient can be
+        non-zero, ascending, -1 behind them) for the NEXT backward pass of this plan, which then runs the row-local records
+        at the network's end on those rows only (include/gcl_amd.h, "Touched rows").  The pass clears the list."""
+        lib = _lib.load()
+        self._touched = rows            # alive until the pass that reads it is enqueued
+        _lib.check(lib.gcl_plan_set_touched_rows(self.handle, _lib.ptr(rows, torch.int32), int(cap)),
+                   "gcl_plan_set_touched_rows")
+
+    def touch_loss_rows(self, index, goff, sel, rows_a, rows_b, n_rows, cap):
+        """The list of a group loss's backward pass -- the members of the selected groups and the two negative subsets -- made
+        on the device from the index tensors the loss holds (gcl_touched_rows: no host read) and handed to the next backward
+        pass.  ``cap``: the host's bound of the list's length.  Returns (rows, count), device tensors."""
+        lib = _lib.load()
+        dev = index.device
+        scratch = torch.empty(int(lib.gcl_touched_rows_scratch_len(int(n_rows))), dtype=torch.int32, device=dev)
+        out = torch.empty(int(cap) + 1, dtype=torch.int32, device=dev)
+        rows, count = out[:cap], out[cap:]
+        _lib.check(lib.gcl_touched_rows(_lib.ptr(index, torch.int64), index.shape[0], _lib.ptr(goff, torch.int64),
+                                        goff.shape[0] - 1, _lib.ptr(sel, torch.int64), sel.shape[0],
+                                        _lib.ptr(rows_a, torch.int64), rows_a.shape[0], _lib.ptr(rows_b, torch.int64),
+                                        rows_b.shape[0], int(n_rows), _lib.ptr(scratch), _lib.ptr(rows), int(cap),
+                                        _lib.ptr(count), _lib.stream()), "gcl_touched_rows")
+        self.set_touched_rows(rows, cap)
+        return rows, count
+
     def _backward(self, run, dy):
         lib = _lib.load()
         targets = run.grad_targets
@@ -490,6 +522,7 @@ class NetworkPlan:
                                              last, st), "gcl_plan_backward")
             for b in buckets:
                 self.on_bucket(b)
+        self._touched = None
         if self.profile_next:
             self.profile_next = False
             self._profile_pending = True

@@ -132,6 +132,73 @@ __global__ void __launch_bounds__(256) k_add2(const float4* __restrict__ a, cons
     y[i] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
   }
 }
+// rows of a row-major [n_src, cv] tensor of V (float4, or float for a column of scalars; row pitch ld floats: a column slice
+// has pitch > its width) picked by a row list: out[j] = src[rows[j]], or `pad` in every component where rows[j] is the -1
+// padding or lies outside the tensor
+template <typename V>
+__device__ __forceinline__ V splat(float v);
+template <>
+__device__ __forceinline__ float splat<float>(float v) { return v; }
+template <>
+__device__ __forceinline__ float4 splat<float4>(float v) { return make_float4(v, v, v, v); }
+template <typename V>
+__global__ void __launch_bounds__(256) k_gather_rows(const float* __restrict__ src, int ld, long long n_src,
+                                                     const int* __restrict__ rows, long long cap, int cv, float pad,
+                                                     V* __restrict__ out) {
+  const long long total = cap * cv;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long j = i / cv;
+    const int q = (int)(i - j * cv);
+    const long long r = rows[j];
+    out[i] = (r >= 0 && r < n_src) ? reinterpret_cast<const V*>(src + r * ld)[q] : splat<V>(pad);
+  }
+}
+// the inverse: dst[rows[j]] = src[j] for the rows of the list that lie inside dst ([n_dst, c4 float4], row pitch ld floats);
+// the list holds a row at most once and the caller has zero-filled dst
+__global__ void __launch_bounds__(256) k_scatter_rows(const float4* __restrict__ src, const int* __restrict__ rows,
+                                                      long long cap, int c4, long long n_dst, float* __restrict__ dst,
+                                                      int ld) {
+  const long long total = cap * c4;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long j = i / c4;
+    const int q = (int)(i - j * c4);
+    const long long r = rows[j];
+    if (r >= 0 && r < n_dst) reinterpret_cast<float4*>(dst + r * ld)[q] = src[i];
+  }
+}
+// touched-row list (gcl_touched_rows): flag[r] = 1 for every row an index array names; ids outside [0, n) are dropped
+__global__ void __launch_bounds__(256) k_touch_rows(const long long* __restrict__ ids, long long count, long long n,
+                                                    int* __restrict__ flag) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const long long r = ids[i];
+  if (r >= 0 && r < n) flag[r] = 1;
+}
+// ... and for the members of the selected groups: one workgroup per selection, index[goff[g] .. goff[g + 1])
+__global__ void __launch_bounds__(64) k_touch_groups(const long long* __restrict__ index, long long n_index,
+                                                     const long long* __restrict__ goff, long long n_groups,
+                                                     const long long* __restrict__ sel, long long n,
+                                                     int* __restrict__ flag) {
+  const long long g = sel[blockIdx.x];
+  if (g < 0 || g >= n_groups) return;
+  long long b = goff[g], e = goff[g + 1];
+  if (b < 0) b = 0;
+  if (e > n_index) e = n_index;
+  for (long long j = b + threadIdx.x; j < e; j += 64) {
+    const long long r = index[j];
+    if (r >= 0 && r < n) flag[r] = 1;
+  }
+}
+// pos = exclusive scan of flag: the flagged rows in ascending order, -1 behind them, the count (which may exceed cap: the
+// list is then cut, and the caller's bound was wrong)
+__global__ void __launch_bounds__(256) k_touch_emit(const int* __restrict__ flag, const int* __restrict__ pos, long long n,
+                                                    int* __restrict__ rows, long long cap, int* __restrict__ n_touched) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int total = pos[n - 1] + flag[n - 1];
+  if (i == 0) *n_touched = total;
+  if (i < n && flag[i] && pos[i] < cap) rows[pos[i]] = (int)i;
+  if (i < cap && i >= total) rows[i] = -1;
+}
 // identity pair list of a kernel_size-1 convolution: p[i] = i for i < n, -1 padding (CoordinateManager.identity_pairs)
 __global__ void __launch_bounds__(256) k_identity_pairs(int* __restrict__ p, long long n, long long total) {
   long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -490,6 +557,15 @@ struct Plan : PassState {   // the base part is the pass being enqueued right no
   std::vector<hipEvent_t> events;
   size_t events_used = 0;
   bool aux_dirty = false;
+  // touched-row suffix: the records [suffix_first, ops.size()) are row-local (ROWNORM, RELU, kernel_size-1 CONV), form one
+  // chain, and nothing but the chain reads its input (ops.size(): no such suffix).  A caller that knows which rows of dy can
+  // be non-zero hands them over for ONE backward pass (gcl_plan_set_touched_rows), which then runs these records on those
+  // rows only (suffix_backward)
+  int suffix_first = 0;
+  bool suffix_rows_ok = false;      // every CONV of the suffix has a shape gcl_conv_bwd_weight_rows takes
+  const int32_t* touched = nullptr;
+  long long touched_cap = 0;
+  long long suffix_rows_used = 0;   // rows the suffix of the latest backward pass ran on (0: all of them, the dense records)
   // profiling
   bool profile = false;
   std::vector<ProfRec> prof;
@@ -1045,10 +1121,116 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
   return GCL_OK;
 }
 
-static int plan_backward(Plan& P, const float* dy, void* const* grads, int first, int last, hipStream_t st) {
+// The records of the touched-row suffix on the rows of a list (rows[cap]: distinct rows ascending, -1 padding): dy and every
+// saved operand are gathered once into compact [cap, c] tensors, the records run through the entries the dense pass calls,
+// with cap rows, and *g_out is the compact gradient of the suffix's input.  A row's results do not depend on the other rows
+// of a launch, and a row of dy that is zero gives a zero row of every gradient and adds nothing to a weight gradient: the
+// input gradient is the dense pass's row for row, the weight gradients are its sums over fewer rows in other groups.  The
+// -1 padding rows are zero rows throughout (their norm reads 1: no 0 / 0).
+static int suffix_backward(Plan& P, const float* dy, void* const* grads, const int32_t* rows, long long cap, TState* g_out,
+                           hipStream_t st) {
+  Arena& A = P.A;
+  const gcl_maps_desc& M = *P.maps;
+  const int n_ops = (int)P.ops.size();
+  const long long n = M.n_rows[P.ops.back().level_out];
+  std::vector<std::pair<const float*, float*>> gathered;      // a saved operand two records read is gathered once
+  auto gather = [&](const float* src, int ld, int c, float pad) -> float* {
+    for (auto& e : gathered)
+      if (e.first == src) return e.second;
+    float* out = A.take_n<float>(cap * c);
+    if (!A.dry && gcl_gather_rows(src, ld, n, rows, cap, c, pad, out, (void*)st) != GCL_OK) return nullptr;
+    gathered.push_back({src, out});
+    return out;
+  };
+  std::vector<char> masked(P.ops.size(), 0);      // RELU record whose backward the consumer's epilogue has applied
+  TState g;
+  g.ptr = gather(dy, P.ops.back().cout, P.ops.back().cout, 0.f);
+  if (!g.ptr) return GCL_ERR_ARG;
+  int rc;
+  for (int i = n_ops - 1; i >= P.suffix_first && g.ptr; --i) {
+    const gcl_plan_op& op = P.ops[i];
+    switch (op.kind) {
+      case GCL_OP_ROWNORM: {
+        const float* y = gather(P.t[op.y].ptr, op.cout, op.cout, 0.f);
+        const float* norm = gather(P.saved[i].norm, 1, 1, 1.f);
+        float* dx = A.take_n<float>(cap * op.cin);
+        int32_t* slot = new_slot(P);
+        PLAN_CALL(gcl_row_normalize_bwd(y, g.ptr, norm, cap, op.cout, dx, slot, (void*)st));
+        g = TState();
+        g.ptr = dx;
+        g.amax = slot;
+        break;
+      }
+      case GCL_OP_RELU: {
+        if (masked[i]) break;      // g is the gradient of the ReLU's input already
+        const float* y = gather(P.t[op.y].ptr, P.t[op.y].ld ? P.t[op.y].ld : op.cout, op.cout, 0.f);
+        const long long numel = cap * op.cout;
+        float* gx = A.take_n<float>(numel);
+        int32_t* slot = new_slot(P);
+        if (!A.dry) {
+          hipLaunchKernelGGL(k_relu_bwd, dim3(grid_for(numel / 4)), dim3(256), 0, st, (const float4*)g.ptr, (const float4*)y,
+                             numel / 4, (float4*)gx, slot);
+          GCL_CHECK_LAUNCH();
+        }
+        g = TState();
+        g.ptr = gx;
+        g.amax = slot;
+        break;
+      }
+      case GCL_OP_CONV: {      // conv_backward with kernel_size 1 on cap rows
+        const TState& x = P.t[op.x];
+        const int wi = P.widx[op.w];
+        if ((rc = ensure_amax(P, g, cap * op.cout, st))) return rc;
+        const int32_t* w_amax = P.w_amax + (long long)wi * GCL_AMAX_WORDS;
+        const bool pl = op.cout >= P.presplit;
+        if (pl && P.made[op.x] && (rc = ensure_planes(P, g, cap, op.cout, st))) return rc;
+        const float* xc = gather(x.ptr, x.ld ? x.ld : op.cin, op.cin, 0.f);
+        if (!A.dry) GCL_CHECK_LAUNCH();
+        hipStream_t ws = fork_aux(P, st);      // behind the gathers the weight gradient reads
+        TState d;
+        if (P.made[op.x]) {
+          GCL_CHECK_ARG(P.wmode[wi] == 1, "gcl_plan_backward: record %d: input-gradient pack mode mismatch", i);
+          d.ptr = A.take_n<float>(cap * op.cin);
+          ProfScope ps(P, st, 0, (double)cap, op.cout, op.cin, cap, cap, op.K);
+          if (P.mask_from[i] >= 0) {
+            d.amax = new_slot(P);
+            PLAN_CALL(gcl_conv_fwd_fused(pl ? (const float*)g.planes : g.ptr, cap, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4,
+                                         g.amax, w_amax, nullptr, nullptr, nullptr, cap, op.K, op.cout, op.cin, nullptr, nullptr,
+                                         xc, 2, d.amax, d.ptr, nullptr, 0, (void*)st));
+            masked[P.mask_from[i]] = 1;
+          } else
+            PLAN_CALL(gcl_conv_fwd(pl ? (const float*)g.planes : g.ptr, cap, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4, g.amax,
+                                   w_amax, nullptr, nullptr, nullptr, cap, op.K, op.cout, op.cin, nullptr, d.ptr, nullptr, 0,
+                                   (void*)st));
+        }
+        {
+          float* scratch = A.take_n<float>(gcl_conv_bwd_weight_rows_scratch_len(op.cin, op.cout, 4, cap));
+          ProfScope ps(P, ws, 3, (double)cap, op.cin, op.cout, cap, cap, op.K);
+          PLAN_CALL(gcl_conv_bwd_weight_rows(xc, g.ptr, cap, op.cin, op.cout, 4, P.saved[i].x_amax, g.amax, scratch,
+                                             (float*)grads[op.w], (void*)ws));
+        }
+        if (op.bias >= 0) {
+          double* scratch = A.take_n<double>(gcl_bn_scratch_len(cap, op.cout));
+          PLAN_CALL(gcl_col_sum(g.ptr, cap, op.cout, scratch, (float*)grads[op.bias], (void*)ws));
+        }
+        g = d;
+        break;
+      }
+      default:
+        return GCL_ERR_ARG;
+    }
+  }
+  if (!A.dry) GCL_CHECK_LAUNCH();
+  *g_out = g;
+  return GCL_OK;
+}
+
+static int plan_backward(Plan& P, const float* dy, void* const* grads, int first, int last, hipStream_t st,
+                         const int32_t* rows = nullptr, long long cap = 0) {
   Arena& A = P.A;
   const gcl_maps_desc& M = *P.maps;
   const size_t nw = P.worder.size();
+  const int n_ops = (int)P.ops.size();
   if (last == (int)P.ops.size()) {
     P.g[P.ops.back().y] = TState();
     P.g[P.ops.back().y].ptr = (float*)dy;
@@ -1066,7 +1248,50 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
     }
     P.bwd_packed = true;
   }
-  for (int i = last - 1; i >= first; --i) {
+  // touched-row suffix: on the rows of the caller's list when there is one and it is short, else dense like every other record
+  int top = last - 1;
+  long long reserve_to = 0;
+  if (last == n_ops && !A.dry) P.suffix_rows_used = 0;
+  if (last == n_ops && P.suffix_first < n_ops && P.suffix_rows_ok && first <= P.suffix_first) {
+    const gcl_plan_op& head = P.ops[P.suffix_first];
+    const long long n = M.n_rows[head.level_in];
+    const long long off0 = A.off, slot0 = P.next_slot;
+    if (A.dry) {      // sizing: room for the largest list that takes this path (2 cap < n), or for the dense records
+      TState g;
+      const long long cap_max = (n - 1) / 2;
+      if (cap_max > 0) {
+        int rc = suffix_backward(P, dy, grads, nullptr, cap_max, &g, st);
+        if (rc) return rc;
+        A.take_n<float>(n * head.cin);
+        reserve_to = A.off;
+        A.off = off0;
+        P.next_slot = slot0;
+      }
+    } else if (rows && cap > 0 && 2 * cap < n) {
+      TState g;
+      A.dry = true;      // the same calls, counted: an arena sized for another bound keeps the dense records
+      int rc = suffix_backward(P, dy, grads, rows, cap, &g, st);
+      A.take_n<float>(n * head.cin);
+      const bool fits = rc == GCL_OK && A.off <= A.size;
+      A.dry = false;
+      A.off = off0;
+      P.next_slot = slot0;
+      if (fits) {
+        if ((rc = suffix_backward(P, dy, grads, rows, cap, &g, st))) return rc;
+        P.g[P.ops.back().y] = TState();
+        if (g.ptr) {      // one zero fill, one scatter: the dense gradient of the suffix's input, handed on as the records do
+          float* dx = A.take_n<float>(n * head.cin);
+          GCL_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)(n * head.cin) * sizeof(float), st));
+          if ((rc = gcl_scatter_rows(g.ptr, rows, cap, head.cin, n, dx, head.cin, (void*)st))) return rc;
+          if ((rc = give(P, head.x, dx, n * head.cin, st, g.amax, 0, head.cin))) return rc;
+        }
+        top = P.suffix_first - 1;
+        P.suffix_rows_used = cap;
+      }
+    }
+  }
+  for (int i = top; i >= first; --i) {
+    if (reserve_to && i == P.suffix_first - 1 && A.off < reserve_to) A.off = reserve_to;
     const gcl_plan_op& op = P.ops[i];
     const long long n_out = M.n_rows[op.level_out], n_in = M.n_rows[op.level_in];
     TState g = P.g[op.y];
@@ -1140,6 +1365,7 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
         return GCL_ERR_ARG;
     }
   }
+  if (reserve_to && A.off < reserve_to) A.off = reserve_to;
   return join_aux(P, st);      // the caller may hand the gradients of this segment to a collective / the optimizer next
 }
 
@@ -1312,6 +1538,30 @@ void* gcl_plan_create(const gcl_plan_op* ops_host, int32_t n_ops, int32_t n_tens
     set_error("gcl_plan_create: malformed or unsupported operator records");
     delete P;
     return nullptr;
+  }
+  // touched-row suffix: the longest chain of row-local records that ends at the last record (each one the only reader of the
+  // record in front of it), cut at the front until nothing but the chain reads its input (model/resunet.py:222-230: conv1_tr,
+  // MEF.relu, final, the row normalisation -- behind the ME.cat)
+  {
+    auto consumers = [&](int t) {
+      int c = 0;
+      for (const gcl_plan_op& o : P->ops) c += (o.x == t) + (o.x2 == t);
+      return c;
+    };
+    auto row_local = [](const gcl_plan_op& o) {
+      return o.kind == GCL_OP_ROWNORM || o.kind == GCL_OP_RELU ||
+             (o.kind == GCL_OP_CONV && o.K == 1 && !o.transpose && o.level_in == o.level_out && o.cin > 4);
+    };
+    int s = n_ops;
+    while (s > 0 && row_local(P->ops[s - 1]) &&
+           (s == n_ops || (P->ops[s].x == P->ops[s - 1].y && consumers(P->ops[s - 1].y) == 1)))
+      --s;
+    while (s < n_ops && consumers(P->ops[s].x) != 1) ++s;
+    P->suffix_first = s;
+    P->suffix_rows_ok = true;
+    for (int i = s; i < n_ops; ++i)
+      if (P->ops[i].kind == GCL_OP_CONV && gcl_conv_bwd_weight_rows_scratch_len(P->ops[i].cin, P->ops[i].cout, 4, 128) <= 0)
+        P->suffix_rows_ok = false;
   }
   for (size_t q = 0; q < nw; ++q) {
     if (!P->wK[q]) {
@@ -1506,7 +1756,12 @@ int gcl_plan_release(void* plan, void* arena) {
 int gcl_plan_backward(void* plan, void* arena, const float* dy, void* const* grads_host, int32_t first_op,
                       int32_t last_op, void* stream) {
   Plan* P = (Plan*)plan;
-  GCL_CHECK_ARG(P && grads_host, "gcl_plan_backward: null pointer");
+  GCL_CHECK_ARG(P, "gcl_plan_backward: null pointer");
+  const int32_t* rows = P->touched;      // the list is good for this call only
+  const long long cap = P->touched_cap;
+  P->touched = nullptr;
+  P->touched_cap = 0;
+  GCL_CHECK_ARG(grads_host, "gcl_plan_backward: null pointer");
   PassState* slot = nullptr;
   for (PassState* q : P->passes)
     if (q->forward_done && q->key == arena) slot = q;
@@ -1515,7 +1770,7 @@ int gcl_plan_backward(void* plan, void* arena, const float* dy, void* const* gra
   GCL_CHECK_ARG(last_op != (int)P->ops.size() || dy, "gcl_plan_backward: the last segment needs dy");
   static_cast<PassState&>(*P) = std::move(*slot);
   P->maps = &P->maps_copy;
-  int rc = plan_backward(*P, dy, grads_host, first_op, last_op, (hipStream_t)stream);
+  int rc = plan_backward(*P, dy, grads_host, first_op, last_op, (hipStream_t)stream, rows, cap);
   if (rc == GCL_OK && !P->A.fits()) {
     set_error("gcl_plan_backward: arena overrun");
     rc = GCL_ERR_ARENA;
@@ -1535,6 +1790,82 @@ int gcl_plan_set_aux_stream(void* plan, void* stream) {
   Plan* P = (Plan*)plan;
   GCL_CHECK_ARG(P, "gcl_plan_set_aux_stream: null plan");
   P->aux = (hipStream_t)stream;
+  return GCL_OK;
+}
+
+int gcl_plan_touched_suffix(const void* plan) {
+  if (!plan) return -1;
+  return ((const Plan*)plan)->suffix_first;
+}
+
+int gcl_gather_rows(const float* src, int32_t ld, int64_t n_src, const int32_t* rows, int64_t cap, int32_t c, float pad,
+                    float* out, void* stream) {
+  GCL_CHECK_ARG(src && rows && out && n_src > 0 && cap > 0 && c > 0 && ld >= c, "gcl_gather_rows: bad argument");
+  const bool vec = c % 4 == 0 && ld % 4 == 0 && (((uintptr_t)src | (uintptr_t)out) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(k_gather_rows<float4>, dim3(grid_for(cap * c / 4)), dim3(256), 0, (hipStream_t)stream, src, ld,
+                       (long long)n_src, (const int*)rows, (long long)cap, c / 4, pad, (float4*)out);
+  else
+    hipLaunchKernelGGL(k_gather_rows<float>, dim3(grid_for(cap * c)), dim3(256), 0, (hipStream_t)stream, src, ld,
+                       (long long)n_src, (const int*)rows, (long long)cap, c, pad, out);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_scatter_rows(const float* src, const int32_t* rows, int64_t cap, int32_t c, int64_t n_dst, float* dst, int32_t ld,
+                     void* stream) {
+  GCL_CHECK_ARG(src && rows && dst && n_dst > 0 && cap > 0, "gcl_scatter_rows: bad argument");
+  GCL_CHECK_ARG(c > 0 && c % 4 == 0 && ld >= c && ld % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
+                "gcl_scatter_rows: channel count and row pitch must be multiples of 4, the tensors 16-byte aligned");
+  hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(cap * c / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)src,
+                     (const int*)rows, (long long)cap, c / 4, (long long)n_dst, dst, ld);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_plan_suffix_rows_used(const void* plan) {
+  if (!plan) return -1;
+  return ((const Plan*)plan)->suffix_rows_used;
+}
+
+int gcl_plan_set_touched_rows(void* plan, const int32_t* rows, int64_t cap) {
+  Plan* P = (Plan*)plan;
+  GCL_CHECK_ARG(P, "gcl_plan_set_touched_rows: null plan");
+  GCL_CHECK_ARG((rows && cap > 0) || (!rows && cap == 0), "gcl_plan_set_touched_rows: a list needs a positive length");
+  P->touched = rows;
+  P->touched_cap = cap;
+  return GCL_OK;
+}
+
+int64_t gcl_touched_rows_scratch_len(int64_t n_rows) { return n_rows > 0 ? gcl_scan_scratch_len(n_rows) : 0; }
+
+int gcl_touched_rows(const int64_t* index, int64_t n_index, const int64_t* goff, int64_t n_groups, const int64_t* sel,
+                     int32_t n_sel, const int64_t* rows_a, int32_t n_a, const int64_t* rows_b, int32_t n_b, int64_t n_rows,
+                     int32_t* scratch, int32_t* rows, int64_t cap, int32_t* n_touched, void* stream) {
+  GCL_CHECK_ARG(scratch && rows && n_touched && n_rows > 0 && n_rows < (1ll << 31) && cap > 0,
+                "gcl_touched_rows: bad argument");
+  GCL_CHECK_ARG(n_sel >= 0 && n_a >= 0 && n_b >= 0 && n_index >= 0 && n_groups >= 0, "gcl_touched_rows: negative count");
+  GCL_CHECK_ARG(n_sel == 0 || (index && goff && sel), "gcl_touched_rows: group selections need index, goff and sel");
+  GCL_CHECK_ARG((n_a == 0 || rows_a) && (n_b == 0 || rows_b), "gcl_touched_rows: null row array");
+  hipStream_t st = (hipStream_t)stream;
+  int32_t *flag = scratch, *pos = scratch + n_rows, *bs = scratch + 2 * n_rows;
+  GCL_CHECK_HIP(hipMemsetAsync(flag, 0, (size_t)n_rows * sizeof(int32_t), st));
+  if (n_sel)
+    hipLaunchKernelGGL(k_touch_groups, dim3((unsigned)n_sel), dim3(64), 0, st, (const long long*)index, (long long)n_index,
+                       (const long long*)goff, (long long)n_groups, (const long long*)sel, (long long)n_rows, flag);
+  if (n_a)
+    hipLaunchKernelGGL(k_touch_rows, dim3((unsigned)cdiv(n_a, 256)), dim3(256), 0, st, (const long long*)rows_a, (long long)n_a,
+                       (long long)n_rows, flag);
+  if (n_b)
+    hipLaunchKernelGGL(k_touch_rows, dim3((unsigned)cdiv(n_b, 256)), dim3(256), 0, st, (const long long*)rows_b, (long long)n_b,
+                       (long long)n_rows, flag);
+  GCL_CHECK_LAUNCH();
+  int rc = gcl_exclusive_scan_i32(flag, n_rows, pos, bs, stream);
+  if (rc) return rc;
+  const long long items = n_rows > cap ? n_rows : cap;
+  hipLaunchKernelGGL(k_touch_emit, dim3((unsigned)cdiv(items, 256)), dim3(256), 0, st, (const int*)flag, (const int*)pos,
+                     (long long)n_rows, rows, (long long)cap, n_touched);
+  GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 

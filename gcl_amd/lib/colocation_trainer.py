@@ -42,6 +42,12 @@ def make_config(**overrides):
     return types.SimpleNamespace(**cfg)
 
 
+# (plan, cap) of the training step whose loss node is being built: the node's backward pass writes the rows of the selected
+# groups and of the two negative subsets only, and tells the plan so (NetworkPlan.touch_loss_rows) before the network's
+# backward pass reads its gradient.  Set and withdrawn by FinestContrastiveLossTrainer._train_step around forward_loss.
+_TOUCHED_REQUEST = None
+
+
 class _GCLLossFn(torch.autograd.Function):
     """(pos[s], fin[s], neg) of finest_contrastive_loss for fixed selections; one gradient buffer for all terms."""
 
@@ -81,6 +87,7 @@ class _GCLLossFn(torch.autograd.Function):
                    "gcl_neg_loss_fwd")
         ctx.save_for_backward(F, index, goff, flag, sel, sel1, sel2, dmin, arg, keep, out, pairpos)
         ctx.th = (pos_thresh, fin_thresh, neg_thresh, int(flags))
+        ctx.touched = _TOUCHED_REQUEST
         return pos, fin, out[0]
 
     @staticmethod
@@ -108,6 +115,9 @@ class _GCLLossFn(torch.autograd.Function):
         _lib.check(lib.gcl_neg_loss_bwd(_lib.ptr(F), c, _lib.ptr(sel1), _lib.ptr(sel2), _lib.ptr(arg), _lib.ptr(dmin),
                                         _lib.ptr(keep), sel1.shape[0], neg_thresh, _lib.ptr(out), _lib.ptr(g),
                                         _lib.ptr(dF), st), "gcl_neg_loss_bwd")
+        req, ctx.touched = getattr(ctx, "touched", None), None
+        if req is not None:        # every row written above: members of the selected groups, sel1, sel2[arg] (a subset of sel2)
+            req[0].touch_loss_rows(index, goff, sel, sel1, sel2, n, req[1])
         return dF
 
 
@@ -578,6 +588,21 @@ class FinestContrastiveLossTrainer:
         loss = self.pos_weight * pos + self.finest_weight * fin + self.neg_weight * neg
         return loss, (pos, fin, neg), F_out
 
+    def _touched_cap(self, input_dict, draws):
+        """Host-side bound of the number of output rows the loss backward writes, a multiple of 128: the sizes of the drawn
+        groups plus the two negative subsets (rows named twice are counted twice).  None when the loss is not the group
+        loss or the group sizes are on the device only (reading them back would stall the step)."""
+        if self.config.use_group_circle_loss or draws is None:
+            return None
+        sizes = input_dict.get("_group_host", input_dict["group"])
+        if isinstance(sizes, torch.Tensor):
+            if sizes.is_cuda:
+                return None
+            sizes = sizes.numpy()
+        pos_sel, sel_hn1, sel_hn2 = draws[:3]
+        cap = int(np.asarray(sizes)[np.asarray(pos_sel)].sum()) + len(sel_hn1) + len(sel_hn2)
+        return (cap + 127) // 128 * 128
+
     def _draw_for(self, input_dict):
         cfg = self.config
         if cfg.use_group_circle_loss:
@@ -829,6 +854,7 @@ class FinestContrastiveLossTrainer:
             return self._train_step(input_dict, draws)
 
     def _train_step(self, input_dict, draws=None):
+        global _TOUCHED_REQUEST
         self.model.train()
         micro = list(input_dict) if isinstance(input_dict, (list, tuple)) else [input_dict]
         n_micro = len(micro)
@@ -860,13 +886,18 @@ class FinestContrastiveLossTrainer:
                 plan.on_bucket = self.ddp.bucket_ready if overlap else None
             wait_for_batch(b)
             try:
+                cap = self._touched_cap(b, d) if plan is not None else None
+                _TOUCHED_REQUEST = (plan, cap) if cap else None
                 loss, parts, F_out = self.forward_loss(b, d, fused_total=(n_micro == 1))
+                _TOUCHED_REQUEST = None
                 if n_micro > 1:
                     parts = tuple(p / n_micro for p in parts)         # :875-877
                     loss = self.pos_weight * parts[0] + self.finest_weight * parts[1] + self.neg_weight * parts[2]
                 loss.backward()
             finally:
+                _TOUCHED_REQUEST = None
                 if plan is not None:
+                    plan.set_touched_rows(None, 0)      # a list no backward pass consumed (an exception on the way) must not outlive its step
                     plan.grad_targets = plan.bucket_of_param = plan.on_bucket = None
             if plan is not None and i > 0:
                 self._flat_grad.add_(self._flat_grad2)
@@ -921,6 +952,8 @@ def prefetch_to_device(batches, device, keys=("sinput_C", "sinput_F", "group", "
                     dst = buf[:n].view(v.shape)
                     dst.copy_(v, non_blocking=True)
                     out[k] = dst
+                    if k == "group":       # the sizes stay readable on the host (the trainer bounds the loss's row set with them)
+                        out["_group_host"] = v
             ev = torch.cuda.Event()
             ev.record(copy_stream)
         out["_h2d_event"], out["_h2d_slot"] = ev, (slot, i)

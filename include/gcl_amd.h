@@ -965,6 +965,38 @@ int gcl_plan_release(void* plan, void* arena);
  * operands by events, while `stream` continues with the input-gradient chain; every gcl_plan_backward call ends with
  * `stream` waiting for them.  NULL (default) = everything on one stream.  Results do not depend on it. */
 int gcl_plan_set_aux_stream(void* plan, void* stream);
+/* Touched rows.  The plan's touched-row suffix is the longest chain of row-local records -- GCL_OP_ROWNORM, GCL_OP_RELU,
+ * kernel_size-1 GCL_OP_CONV -- that ends at the last record and whose input nothing else reads (ResUNetBN2C: conv1_tr, ReLU,
+ * final, the row normalisation, behind the ME.cat); gcl_plan_touched_suffix returns its first record, or the number of records
+ * when there is none.  A zero row of dy gives a zero row of every gradient inside the suffix and adds nothing to its weight
+ * gradients, so a caller that knows which rows of dy can be non-zero (a loss that scatters into selected rows) names them:
+ * rows[cap] on the device = the distinct rows, ascending, padded with -1 (gcl_touched_rows makes it).  The NEXT
+ * gcl_plan_backward call then gathers those rows, runs the suffix on cap rows through the same entries, and scatters the
+ * result into the zero-filled gradient of the suffix's input: that gradient, and everything upstream, is bitwise the dense
+ * pass's; the suffix's weight and bias gradients are sums over fewer rows and differ from it in rounding.  The call clears the
+ * list (rows must stay allocated until it has returned).  It is ignored -- the dense records run -- without a suffix, when
+ * 2 cap >= n_rows, when the call's record range cuts the suffix, or when the pass's arena has no room for it.  A row of dy
+ * outside the list that is NOT zero is silently dropped: the list must cover them all.  NULL, 0 withdraws a list. */
+int gcl_plan_touched_suffix(const void* plan);
+int gcl_plan_set_touched_rows(void* plan, const int32_t* rows, int64_t cap);
+/* rows the suffix of the latest gcl_plan_backward call that held the last record ran on: cap, or 0 = the dense records */
+int64_t gcl_plan_suffix_rows_used(const void* plan);
+/* The list for the group losses above: the members index[goff[g] .. goff[g + 1]) of the n_sel selected groups g = sel[s],
+ * and the rows of two more index arrays (the negative subsets), as rows[cap] = the distinct rows in [0, n_rows), ascending,
+ * then -1; *n_touched (device) = their number -- more than cap means the caller's bound was wrong and the list is cut.
+ * Ids outside their array are skipped.  No host synchronisation.  scratch: int32[gcl_touched_rows_scratch_len(n_rows)]. */
+int64_t gcl_touched_rows_scratch_len(int64_t n_rows);
+int gcl_touched_rows(const int64_t* index, int64_t n_index, const int64_t* goff, int64_t n_groups, const int64_t* sel,
+                     int32_t n_sel, const int64_t* rows_a, int32_t n_a, const int64_t* rows_b, int32_t n_b, int64_t n_rows,
+                     int32_t* scratch, int32_t* rows, int64_t cap, int32_t* n_touched, void* stream);
+/* The two row moves of that path.  gcl_gather_rows: out[j, :] = src[rows[j], :] for j < cap, `pad` in every column where
+ * rows[j] is -1 or outside [0, n_src); src is [n_src, c] with row pitch ld floats (a column slice has ld > c), out is
+ * contiguous [cap, c].  gcl_scatter_rows: dst[rows[j], :] = src[j, :] for the rows[j] inside [0, n_dst), the others are
+ * skipped; dst has row pitch ld, c and ld multiples of 4; a row named twice receives one of its sources. */
+int gcl_gather_rows(const float* src, int32_t ld, int64_t n_src, const int32_t* rows, int64_t cap, int32_t c, float pad,
+                    float* out, void* stream);
+int gcl_scatter_rows(const float* src, const int32_t* rows, int64_t cap, int32_t c, int64_t n_dst, float* dst, int32_t ld,
+                     void* stream);
 /* a stream whose kernels run on the lowest `percent` % of the device's CUs (hipExtStreamCreateWithCUMask) -- measurement hook
  * for the weight-gradient stream (GCL_AUX_CU_PCT); gcl_stream_destroy frees it */
 int gcl_stream_create_cu_share(int32_t percent, int32_t low_priority, void** stream_out);
