@@ -15,6 +15,11 @@ One exception to "the same launches": a caller that knows which rows of the outp
 (``NetworkPlan.set_touched_rows`` / ``touch_loss_rows``: the trainer's group loss writes ~7 % of the rows) has the row-local
 records at the network's end -- conv1_tr, ReLU, final, the row normalisation -- run on those rows only.  Everything upstream stays
 bitwise; the gradients of those records' own parameters become sums over fewer rows (tests/test_gpu_head_touched_rows.py).
+A list set BEFORE ``run`` takes the forward pass of those records along: the output is still [n, c], with the features on
+the rows of the list and exact zeros everywhere else, the pass keeps the compact activations and its backward pass needs no
+second list.  Features and gradients then differ from the dense pass's in rounding (tests/test_gpu_head_forward_touched_rows.py).
+``run`` withholds the list from the forward pass when the backward pass is cut into bucket segments inside those records
+(``forward_list_ok``): the native side has no dense operands to fall back to there.
 """
 import ctypes
 import os
@@ -141,7 +146,7 @@ class NativeMaps:
 class _PlanRun:
     """One forward pass of a plan that is waiting for its backward pass (keeps the arena and the maps alive)."""
 
-    __slots__ = ("plan", "arena", "maps", "y", "x", "grad_targets", "segments", "done")
+    __slots__ = ("plan", "arena", "maps", "y", "x", "grad_targets", "segments", "done", "touched")
 
     def __del__(self):          # the output was dropped without a backward pass: un-park the pass on the native side
         try:
@@ -207,6 +212,7 @@ class NetworkPlan:
         self._aux = None
         self._eval_key = None
         self._touched = None
+        self._touched_cap = 0
 
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
@@ -369,9 +375,17 @@ class NetworkPlan:
         if self.profile_next:
             lib.gcl_plan_profile(self.handle, 1)
         y_ptr = ctypes.c_void_p()
-        _lib.check(lib.gcl_plan_forward(self.handle, ctypes.byref(maps.desc), _lib.ptr(x, torch.float32), pp, bp,
-                                        _lib.ptr(self._state), _lib.ptr(arena), arena.numel(), ctypes.byref(y_ptr),
-                                        _lib.stream()), "gcl_plan_forward")
+        held = None
+        if self._touched is not None and not (torch.is_grad_enabled() and self.forward_list_ok()):
+            held, cap = self._touched, self._touched_cap      # this forward pass must run dense: the list waits for the backward
+            self.set_touched_rows(None, 0)
+        try:
+            _lib.check(lib.gcl_plan_forward(self.handle, ctypes.byref(maps.desc), _lib.ptr(x, torch.float32), pp, bp,
+                                            _lib.ptr(self._state), _lib.ptr(arena), arena.numel(), ctypes.byref(y_ptr),
+                                            _lib.stream()), "gcl_plan_forward")
+        finally:
+            if held is not None:
+                self.set_touched_rows(held, cap)
         for m in self.bn_modules:          # what MinkowskiBatchNorm.forward keeps on the host per training forward
             m._pending_batches += 1
             m._train_forwards += 1
@@ -384,6 +398,10 @@ class NetworkPlan:
         run = _PlanRun()
         run.plan, run.arena, run.maps, run.y, run.x = self, arena, maps, y, x
         run.grad_targets, run.done = self.grad_targets, False
+        # a pass that ran the head on the list keeps it alive (the native side parked the pointer with the pass)
+        run.touched = None
+        if self._touched is not None and lib.gcl_plan_suffix_fwd_rows_used(self.handle) > 0:
+            run.touched, self._touched, self._touched_cap = self._touched, None, 0
         run.segments = self._segments()
         if run.grad_targets is not None:
             # seated gradients are written in place: the parameters stay out of the autograd node (autograd would run their
@@ -478,12 +496,25 @@ class NetworkPlan:
             segs.append((0, hi, []))
         return segs
 
+    def forward_list_ok(self):
+        """True when no bucket segment of the backward pass cuts the row-local records at the network's end, i.e. a list may
+        be handed to the forward pass (``bucket_of_param`` / ``on_bucket`` are set before the forward pass)."""
+        n, s = len(self.records), _lib.load().gcl_plan_touched_suffix(self.handle)
+        return all(last <= s or (first <= s and last == n) for first, last, _ in self._segments())
+
+    def output_rows(self, maps):
+        """Rows of the output of a pass on ``maps``."""
+        return int(maps.desc.n_rows[self.records[-1]["level_out"]])
+
     def set_touched_rows(self, rows, cap):
         """``rows`` (int32 device tensor, at least ``cap`` entries: the distinct rows of the output whose gradient can be
-        non-zero, ascending, -1 behind them) for the NEXT backward pass of this plan, which then runs the row-local records
-        at the network's end on those rows only (include/gcl_amd.h, "Touched rows").  The pass clears the list."""
+        non-zero, ascending, -1 behind them) for the NEXT pass of this plan.  Set before ``run``: the forward pass runs the
+        row-local records at the network's end on those rows only, leaves every other row of the output zero, and its backward
+        pass does the same with no second call.  Set between ``run`` and the backward pass: the backward pass alone does
+        (include/gcl_amd.h, "Touched rows").  The pass that uses the list clears it."""
         lib = _lib.load()
         self._touched = rows            # alive until the pass that reads it is enqueued
+        self._touched_cap = int(cap)
         _lib.check(lib.gcl_plan_set_touched_rows(self.handle, _lib.ptr(rows, torch.int32), int(cap)),
                    "gcl_plan_set_touched_rows")
 
@@ -522,7 +553,7 @@ class NetworkPlan:
                                              last, st), "gcl_plan_backward")
             for b in buckets:
                 self.on_bucket(b)
-        self._touched = None
+        self._touched = run.touched = None
         if self.profile_next:
             self.profile_next = False
             self._profile_pending = True

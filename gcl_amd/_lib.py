@@ -151,6 +151,7 @@ SIGNATURES = {
     "gcl_plan_touched_suffix": (_i32, [_vp]),
     "gcl_plan_set_touched_rows": (_i32, [_vp, _vp, _i64]),
     "gcl_plan_suffix_rows_used": (_i64, [_vp]),
+    "gcl_plan_suffix_fwd_rows_used": (_i64, [_vp]),
     "gcl_gather_rows": (_i32, [_vp, _i32, _i64, _vp, _i64, _i32, _f32, _vp, _vp]),
     "gcl_scatter_rows": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp]),
     "gcl_touched_rows_scratch_len": (_i64, [_i64]),

@@ -166,6 +166,25 @@ __global__ void __launch_bounds__(256) k_scatter_rows(const float4* __restrict__
     if (r >= 0 && r < n_dst) reinterpret_cast<float4*>(dst + r * ld)[q] = src[i];
   }
 }
+// k_scatter_rows for the output of a forward pass that ran the row normalisation on the rows of a list: the same move, and
+// the rows of the compact tensors that belong to no row of dst (-1 padding, ids outside dst) are made inert in place --
+// y[j] = 0, norm[j] = 1 -- whatever the normalisation left there (0 / 0 when the row in front of it is zero)
+__global__ void __launch_bounds__(256) k_scatter_rows_inert(float4* __restrict__ y, float* __restrict__ norm,
+                                                            const int* __restrict__ rows, long long cap, int c4,
+                                                            long long n_dst, float* __restrict__ dst, int ld) {
+  const long long total = cap * c4;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long j = i / c4;
+    const int q = (int)(i - j * c4);
+    const long long r = rows[j];
+    if (r >= 0 && r < n_dst) {
+      reinterpret_cast<float4*>(dst + r * ld)[q] = y[i];
+    } else {
+      y[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (q == 0) norm[j] = 1.f;
+    }
+  }
+}
 // touched-row list (gcl_touched_rows): flag[r] = 1 for every row an index array names; ids outside [0, n) are dropped
 __global__ void __launch_bounds__(256) k_touch_rows(const long long* __restrict__ ids, long long count, long long n,
                                                     int* __restrict__ flag) {
@@ -528,6 +547,10 @@ struct PassState {        // everything one forward pass leaves behind for its b
   bool fwd_packs_pending = false;
   int32_t* not_ones = nullptr;      // per input row of the pass: its cloud has a feature that differs from 1.0f (table path)
   void* key = nullptr;              // the pass's arena: how gcl_plan_backward / gcl_plan_release find it
+  // forward pass that ran the touched-row suffix on the rows of a list (fwd_cap > 0): the list, parked with the pass.  The
+  // tensors of the suffix -- its input included -- and its saved operands are then compact [fwd_cap, c] tensors
+  const int32_t* fwd_rows = nullptr;
+  long long fwd_cap = 0;
 };
 
 struct Plan : PassState {   // the base part is the pass being enqueued right now
@@ -566,6 +589,7 @@ struct Plan : PassState {   // the base part is the pass being enqueued right no
   const int32_t* touched = nullptr;
   long long touched_cap = 0;
   long long suffix_rows_used = 0;   // rows the suffix of the latest backward pass ran on (0: all of them, the dense records)
+  long long suffix_fwd_rows_used = 0;   // ... of the latest training-mode forward pass
   // profiling
   bool profile = false;
   std::vector<ProfRec> prof;
@@ -664,12 +688,14 @@ static int stem_flag(Plan& P, const gcl_plan_op& op, const gcl_map_desc& m, cons
 }
 
 // the convolution of a CONVBN / CONV record (ops._SparseConvFn.forward); returns its output in *y_out
-static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStream_t st, int32_t** relu_amax_out) {
+// rows > 0: a kernel_size-1 record of the touched-row suffix whose input is a compact [rows, cin] tensor
+static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStream_t st, int32_t** relu_amax_out,
+                        long long rows = 0) {
   Arena& A = P.A;
   const gcl_plan_op& op = P.ops[i];
   const gcl_maps_desc& M = *P.maps;
   const gcl_map_desc& m = M.maps[op.map];
-  const long long n_in = M.n_rows[op.level_in], n_out = M.n_rows[op.level_out];
+  const long long n_in = rows > 0 ? rows : M.n_rows[op.level_in], n_out = rows > 0 ? rows : M.n_rows[op.level_out];
   TState& x = P.t[op.x];
   float* y = A.take_n<float>(n_out * op.cout);
   *y_out = y;
@@ -811,7 +837,20 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
   bool late_pending = !A.dry && M.ready_event && M.late_mask;
   for (size_t i = 0; i < P.ops.size(); ++i) {
     const gcl_plan_op& op = P.ops[i];
-    const long long n_out = M.n_rows[op.level_out];
+    // touched-row suffix on the rows of the pass's list: its input gathered once (the dense tensor's max-abs slot bounds the
+    // rows picked from it: no gcl_amax pass), then the records below with fwd_cap rows
+    const bool compact = P.fwd_cap > 0 && (int)i >= P.suffix_first;
+    const long long n_out = compact ? P.fwd_cap : M.n_rows[op.level_out];
+    if (compact && (int)i == P.suffix_first) {
+      TState& xs = P.t[op.x];
+      float* cx = A.take_n<float>(P.fwd_cap * op.cin);
+      PLAN_CALL(gcl_gather_rows(xs.ptr, xs.ld ? xs.ld : op.cin, M.n_rows[op.level_in], P.fwd_rows, P.fwd_cap, op.cin, 0.f, cx,
+                                (void*)st));
+      int32_t* slot = xs.amax;
+      xs = TState();      // nothing but the suffix reads this tensor, in either pass
+      xs.ptr = cx;
+      xs.amax = slot;
+    }
     if (late_pending && (op.kind == GCL_OP_CONVBN || op.kind == GCL_OP_CONV) && ((M.late_mask >> op.map) & 1)) {
       GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));
       late_pending = false;
@@ -919,7 +958,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
       case GCL_OP_CONV: {
         float *cy, *stats;
         int32_t* relu_amax;
-        if ((rc = conv_forward(P, (int)i, &cy, &stats, st, &relu_amax))) return rc;
+        if ((rc = conv_forward(P, (int)i, &cy, &stats, st, &relu_amax, compact ? P.fwd_cap : 0))) return rc;
         y.ptr = cy;
         if (relu_amax) {      // the epilogue applied the ReLU record that follows: both tensor ids name relu(conv(x))
           y.amax = relu_amax;
@@ -928,7 +967,10 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
         break;
       }
       case GCL_OP_RELU: {
-        if (i > 0 && P.fuse_relu[i - 1]) break;      // written by the convolution in front of it
+        if (i > 0 && P.fuse_relu[i - 1]) {      // written by the convolution in front of it
+          if (compact) y = P.t[op.x];           // (the gathered rows of it when the suffix starts here)
+          break;
+        }
         const long long n4 = n_out * op.cout / 4;
         y.ptr = A.take_n<float>(n_out * op.cout);
         y.amax = new_slot(P);        // published by the kernel itself: the consumer needs no gcl_amax pass
@@ -976,6 +1018,24 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
   }
   if (late_pending) GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));      // (the arena outlives the side stream's work)
   *y_out = P.t[P.ops.back().y].ptr;
+  if (P.fwd_cap > 0) {      // the pass's output stays dense: the rows of the list hold the features, every other row is zero
+    const gcl_plan_op& last = P.ops.back();
+    const long long n = M.n_rows[last.level_out];
+    float* yc = *y_out;
+    float* out = A.take_n<float>(n * last.cout);
+    if (!A.dry) {
+      GCL_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)(n * last.cout) * sizeof(float), st));
+      if (last.kind == GCL_OP_ROWNORM) {      // ... and the padding rows of the saved y and norm become (0, 1)
+        hipLaunchKernelGGL(k_scatter_rows_inert, dim3(grid_for(P.fwd_cap * last.cout / 4)), dim3(256), 0, st, (float4*)yc,
+                           P.saved[P.ops.size() - 1].norm, (const int*)P.fwd_rows, P.fwd_cap, last.cout / 4, n, out, last.cout);
+        GCL_CHECK_LAUNCH();
+      } else {
+        int rc = gcl_scatter_rows(yc, P.fwd_rows, P.fwd_cap, last.cout, n, out, last.cout, (void*)st);
+        if (rc) return rc;
+      }
+    }
+    *y_out = out;
+  }
   return GCL_OK;
 }
 
@@ -1127,14 +1187,18 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
 // of a launch, and a row of dy that is zero gives a zero row of every gradient and adds nothing to a weight gradient: the
 // input gradient is the dense pass's row for row, the weight gradients are its sums over fewer rows in other groups.  The
 // -1 padding rows are zero rows throughout (their norm reads 1: no 0 / 0).
+// After a forward pass that ran the suffix on this list (P.fwd_cap > 0) the saved operands ARE the compact tensors, with
+// inert padding rows, and only dy is gathered.
 static int suffix_backward(Plan& P, const float* dy, void* const* grads, const int32_t* rows, long long cap, TState* g_out,
                            hipStream_t st) {
   Arena& A = P.A;
   const gcl_maps_desc& M = *P.maps;
   const int n_ops = (int)P.ops.size();
   const long long n = M.n_rows[P.ops.back().level_out];
+  const bool parked = P.fwd_cap > 0;
   std::vector<std::pair<const float*, float*>> gathered;      // a saved operand two records read is gathered once
   auto gather = [&](const float* src, int ld, int c, float pad) -> float* {
+    if (parked && src != dy) return (float*)src;
     for (auto& e : gathered)
       if (e.first == src) return e.second;
     float* out = A.take_n<float>(cap * c);
@@ -1256,7 +1320,22 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
     const gcl_plan_op& head = P.ops[P.suffix_first];
     const long long n = M.n_rows[head.level_in];
     const long long off0 = A.off, slot0 = P.next_slot;
-    if (A.dry) {      // sizing: room for the largest list that takes this path (2 cap < n), or for the dense records
+    if (P.fwd_cap > 0) {      // the forward pass ran the suffix on its list and sized the arena for these calls (dry: that sizing)
+      TState g;
+      int rc = suffix_backward(P, dy, grads, P.fwd_rows, P.fwd_cap, &g, st);
+      if (rc) return rc;
+      P.g[P.ops.back().y] = TState();
+      if (g.ptr) {
+        float* dx = A.take_n<float>(n * head.cin);
+        if (!A.dry) {
+          GCL_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)(n * head.cin) * sizeof(float), st));
+          if ((rc = gcl_scatter_rows(g.ptr, P.fwd_rows, P.fwd_cap, head.cin, n, dx, head.cin, (void*)st))) return rc;
+        }
+        if ((rc = give(P, head.x, dx, n * head.cin, st, g.amax, 0, head.cin))) return rc;
+      }
+      top = P.suffix_first - 1;
+      if (!A.dry) P.suffix_rows_used = P.fwd_cap;
+    } else if (A.dry) {      // sizing: room for the largest list that takes this path (2 cap < n), or for the dense records
       TState g;
       const long long cap_max = (n - 1) / 2;
       if (cap_max > 0) {
@@ -1647,9 +1726,42 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
       return GCL_ERR_ARENA;
     }
   }
+  // a list handed over before the pass: the touched-row suffix runs on its rows in this pass too, under the rules of the
+  // backward pass -- a suffix, shapes the row-stream weight gradient takes, 2 cap < n_rows, and room in the arena for both
+  // passes (the same calls, counted)
+  const int n_ops = (int)P->ops.size();
+  P->suffix_fwd_rows_used = 0;
+  if (P->touched && P->touched_cap > 0 && P->suffix_first < n_ops && P->suffix_rows_ok && P->ops.back().cout % 4 == 0 &&
+      2 * P->touched_cap < maps_host->n_rows[P->ops[P->suffix_first].level_in]) {
+    Arena real = P->A;
+    P->A = Arena{DRY_BASE, 0, 0, true};
+    P->fwd_rows = P->touched;
+    P->fwd_cap = P->touched_cap;
+    std::vector<void*> gn(P->n_params, nullptr);
+    float* yy = nullptr;
+    const bool prof = P->profile;
+    P->profile = false;
+    rc = plan_forward(*P, x, bn_stats_host, &yy, nullptr);
+    if (rc == GCL_OK) rc = plan_backward(*P, (const float*)DRY_BASE, gn.data(), 0, n_ops, nullptr);
+    P->profile = prof;
+    if (rc != GCL_OK || P->A.off > arena_bytes) {
+      P->fwd_rows = nullptr;
+      P->fwd_cap = 0;
+    }
+    P->A = real;
+  }
   rc = plan_forward(*P, x, bn_stats_host, y_out_host, (hipStream_t)stream);
   P->forward_done = rc == GCL_OK;
-  if (rc != GCL_OK) return rc;
+  if (rc != GCL_OK) {
+    P->fwd_rows = nullptr;
+    P->fwd_cap = 0;
+    return rc;
+  }
+  if (P->fwd_cap > 0) {      // the list is parked with the pass; its backward pass needs no second one
+    P->suffix_fwd_rows_used = P->fwd_cap;
+    P->touched = nullptr;
+    P->touched_cap = 0;
+  }
   // park the pass under its arena until gcl_plan_backward / gcl_plan_release asks for it
   PassState* slot = nullptr;
   for (PassState* q : P->passes)
@@ -1768,6 +1880,14 @@ int gcl_plan_backward(void* plan, void* arena, const float* dy, void* const* gra
   GCL_CHECK_ARG(slot, "gcl_plan_backward: no forward pass to differentiate in this arena");
   GCL_CHECK_ARG(first_op >= 0 && first_op < last_op && last_op <= (int)P->ops.size(), "gcl_plan_backward: bad record range");
   GCL_CHECK_ARG(last_op != (int)P->ops.size() || dy, "gcl_plan_backward: the last segment needs dy");
+  if (slot->fwd_cap > 0) {      // the forward pass ran the suffix on its own list: dense operands do not exist
+    GCL_CHECK_ARG(!rows || (rows == slot->fwd_rows && cap == slot->fwd_cap),
+                  "gcl_plan_backward: the forward pass of this arena ran the touched-row suffix on another list");
+    GCL_CHECK_ARG(last_op <= P->suffix_first || (first_op <= P->suffix_first && last_op == (int)P->ops.size()),
+                  "gcl_plan_backward: the record range [%d, %d) cuts the touched-row suffix [%d, %d), which the forward pass "
+                  "ran on the rows of a list: there are no dense operands to fall back to",
+                  (int)first_op, (int)last_op, P->suffix_first, (int)P->ops.size());
+  }
   static_cast<PassState&>(*P) = std::move(*slot);
   P->maps = &P->maps_copy;
   int rc = plan_backward(*P, dy, grads_host, first_op, last_op, (hipStream_t)stream, rows, cap);
@@ -1826,6 +1946,11 @@ int gcl_scatter_rows(const float* src, const int32_t* rows, int64_t cap, int32_t
 int64_t gcl_plan_suffix_rows_used(const void* plan) {
   if (!plan) return -1;
   return ((const Plan*)plan)->suffix_rows_used;
+}
+
+int64_t gcl_plan_suffix_fwd_rows_used(const void* plan) {
+  if (!plan) return -1;
+  return ((const Plan*)plan)->suffix_fwd_rows_used;
 }
 
 int gcl_plan_set_touched_rows(void* plan, const int32_t* rows, int64_t cap) {

@@ -44,7 +44,8 @@ def make_config(**overrides):
 
 # (plan, cap) of the training step whose loss node is being built: the node's backward pass writes the rows of the selected
 # groups and of the two negative subsets only, and tells the plan so (NetworkPlan.touch_loss_rows) before the network's
-# backward pass reads its gradient.  Set and withdrawn by FinestContrastiveLossTrainer._train_step around forward_loss.
+# backward pass reads its gradient.  Set and withdrawn by FinestContrastiveLossTrainer._train_step around forward_loss --
+# only for a step whose list could not be handed to the plan before the forward pass (_touch_forward), which is the rule.
 _TOUCHED_REQUEST = None
 
 
@@ -228,7 +229,7 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
                             points=None, batch_lengths=None, pos_thresh=0.1, neg_thresh=1.4, finest_thresh=0.2,
                             draws=None, square_loss=True, block_finest_gradient=False,
                             use_pair_group_positive_loss=False, use_hard_negative=True, finest_term=True,
-                            prepared=None, total_weights=None):
+                            prepared=None, total_weights=None, selections=None):
     """(pos_loss, finest_loss, neg_loss) of lib/colocation_trainer.py:430-535 with its four config switches
     (defaults = scripts/train_gcl_kitti.sh:96-105).  ``finest_term=False`` gives ``location_contrastive_loss``
     (:734-809) when combined with ``square_loss=False``.
@@ -241,7 +242,8 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
     (``random_negative_term``; pinned by a golden captured from the reference).  ``index_hash``, ``points`` and
     ``batch_lengths`` are unused (see module docstring).  ``total_weights=(w_pos, w_fin, w_neg)`` (the trainer's step, with
     hard negatives): returns ``(total, pos, fin, neg)`` from one autograd node instead -- same values, the scalar arithmetic
-    in one launch each way; only ``total`` carries a gradient.
+    in one launch each way; only ``total`` carries a gradient.  ``selections``: the device tensor ``upload_selections`` made of
+    ``draws[:3]`` earlier in the step (the trainer builds the network's touched-row list from it before the forward pass).
     """
     dev = F_out.device
     n_out = F_out.shape[0]
@@ -265,11 +267,8 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
     goff, index, flag = prepared if prepared is not None else prepare_loss_inputs(group, index, finest_flag, dev)
     to_dev32 = lambda a: None if a is None else \
         torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev, non_blocking=True)
-    n_pos, n_hn = len(pos_sel), len(sel_hn1)                   # the three selections travel in ONE host -> device copy
-    sel_host = torch.empty(n_pos + 2 * n_hn, dtype=torch.int64, pin_memory=True)     # pinned: the copy is asynchronous
-    np.concatenate([np.asarray(pos_sel, dtype=np.int64), np.asarray(sel_hn1, dtype=np.int64),
-                    np.asarray(sel_hn2, dtype=np.int64)], out=sel_host.numpy())
-    sel_all = sel_host.to(dev, non_blocking=True)
+    n_pos, n_hn = len(pos_sel), len(sel_hn1)
+    sel_all = selections if selections is not None else upload_selections(pos_sel, sel_hn1, sel_hn2, dev)
     if total_weights is not None and use_hard_negative:
         # the trainer's step: (total, pos, fin, neg) from one autograd node (``_GCLTotalLossFn``); only total has a gradient
         return _GCLTotalLossFn.apply(F_out, index, goff, flag, sel_all[:n_pos], sel_all[n_pos:n_pos + n_hn],
@@ -283,6 +282,15 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
         neg = random_negative_term(F_out, sel_all[n_pos:n_pos + n_hn], sel_all[n_pos + n_hn:], rand_cols, group, index,
                                    index_hash, float(neg_thresh))
     return pos.sum() / len(pos_sel), fin.sum() / len(pos_sel), neg
+
+
+def upload_selections(pos_sel, sel_hn1, sel_hn2, dev):
+    """The three selections of a draw as one int64 device tensor [pos_sel | sel_hn1 | sel_hn2]: ONE host -> device copy."""
+    n_pos, n_hn = len(pos_sel), len(sel_hn1)
+    sel_host = torch.empty(n_pos + 2 * n_hn, dtype=torch.int64, pin_memory=True)     # pinned: the copy is asynchronous
+    np.concatenate([np.asarray(pos_sel, dtype=np.int64), np.asarray(sel_hn1, dtype=np.int64),
+                    np.asarray(sel_hn2, dtype=np.int64)], out=sel_host.numpy())
+    return sel_host.to(dev, non_blocking=True)
 
 
 class _RandomNegFn(torch.autograd.Function):
@@ -549,7 +557,7 @@ class FinestContrastiveLossTrainer:
         return self._bucket_map
 
     def location_loss(self, F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
-                      points=None, batch_lengths=None, draws=None, prepared=None, total_weights=None):
+                      points=None, batch_lengths=None, draws=None, prepared=None, total_weights=None, selections=None):
         cfg = self.config
         if cfg.use_group_circle_loss:         # lib/colocation_trainer.py:423-424
             return location_circle_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
@@ -563,11 +571,13 @@ class FinestContrastiveLossTrainer:
         return finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
                                        points, batch_lengths, cfg.pos_thresh, cfg.neg_thresh, cfg.finest_thresh, draws,
                                        cfg.square_loss, cfg.block_finest_gradient, cfg.use_pair_group_positive_loss,
-                                       cfg.use_hard_negative, prepared=prepared, total_weights=total_weights)
+                                       cfg.use_hard_negative, prepared=prepared, total_weights=total_weights,
+                                       selections=selections)
 
-    def forward_loss(self, input_dict, draws=None, fused_total=False):
+    def forward_loss(self, input_dict, draws=None, fused_total=False, selections=None):
         """``fused_total``: the weighted total comes out of the loss node itself (one optimizer step on one batch; with
-        gradient accumulation the terms are rescaled first, :875-877, and the sum stays in torch)."""
+        gradient accumulation the terms are rescaled first, :875-877, and the sum stays in torch).  ``selections``: the
+        draws' selections on the device already (``_touch_forward``)."""
         cfg = self.config
         sinput = ME.SparseTensor(input_dict["sinput_F"].to(self.device, non_blocking=True),
                                  coordinates=input_dict["sinput_C"].to(self.device, non_blocking=True),
@@ -581,7 +591,7 @@ class FinestContrastiveLossTrainer:
             max_hn_samples=cfg.num_hn_samples_per_batch * cfg.batch_size,
             points=input_dict["sinput_C"][:, 1:] if cfg.use_group_circle_loss else None,
             batch_lengths=input_dict.get("batch_lengths"), draws=draws, prepared=input_dict.get("_loss_inputs"),
-            total_weights=(self.pos_weight, self.finest_weight, self.neg_weight) if fuse else None)
+            total_weights=(self.pos_weight, self.finest_weight, self.neg_weight) if fuse else None, selections=selections)
         if len(terms) == 4:
             return terms[0], tuple(terms[1:]), F_out
         pos, fin, neg = terms
@@ -602,6 +612,25 @@ class FinestContrastiveLossTrainer:
         pos_sel, sel_hn1, sel_hn2 = draws[:3]
         cap = int(np.asarray(sizes)[np.asarray(pos_sel)].sum()) + len(sel_hn1) + len(sel_hn2)
         return (cap + 127) // 128 * 128
+
+    def _touch_forward(self, plan, input_dict, draws, cap):
+        """The plan's touched-row list of this (micro-)batch, made before the network's forward pass from the batch's prepared
+        loss inputs and ONE upload of the draws' selections, which the loss then reads too (returned: [pos_sel | sel_hn1 |
+        sel_hn2] on the device).  None = the list cannot go forward -- no prepared inputs or native maps, another loss, a
+        backward pass cut into segments inside the head, a list too long to pay -- and the loss node builds it instead."""
+        prep, mgr = input_dict.get("_loss_inputs"), input_dict.get("_coordinate_manager")
+        maps = getattr(mgr, "native", None)
+        if prep is None or maps is None or self.config.finest_weight == 0 or not plan.forward_list_ok():
+            return None
+        n_rows = plan.output_rows(maps)
+        if 2 * cap >= n_rows:
+            return None
+        pos_sel, sel_hn1, sel_hn2 = draws[:3]
+        n_pos, n_hn = len(pos_sel), len(sel_hn1)
+        sel_all = upload_selections(pos_sel, sel_hn1, sel_hn2, self.device)
+        goff, index, _ = prep
+        plan.touch_loss_rows(index, goff, sel_all[:n_pos], sel_all[n_pos:n_pos + n_hn], sel_all[n_pos + n_hn:], n_rows, cap)
+        return sel_all
 
     def _draw_for(self, input_dict):
         cfg = self.config
@@ -887,8 +916,11 @@ class FinestContrastiveLossTrainer:
             wait_for_batch(b)
             try:
                 cap = self._touched_cap(b, d) if plan is not None else None
-                _TOUCHED_REQUEST = (plan, cap) if cap else None
-                loss, parts, F_out = self.forward_loss(b, d, fused_total=(n_micro == 1))
+                # the list goes to the plan BEFORE the forward pass (the head then runs on its rows in both passes); where it
+                # cannot, the loss node builds it in its backward pass, in front of the network's
+                sel_dev = self._touch_forward(plan, b, d, cap) if cap else None
+                _TOUCHED_REQUEST = (plan, cap) if cap and sel_dev is None else None
+                loss, parts, F_out = self.forward_loss(b, d, fused_total=(n_micro == 1), selections=sel_dev)
                 _TOUCHED_REQUEST = None
                 if n_micro > 1:
                     parts = tuple(p / n_micro for p in parts)         # :875-877

@@ -976,11 +976,28 @@ int gcl_plan_set_aux_stream(void* plan, void* stream);
  * pass's; the suffix's weight and bias gradients are sums over fewer rows and differ from it in rounding.  The call clears the
  * list (rows must stay allocated until it has returned).  It is ignored -- the dense records run -- without a suffix, when
  * 2 cap >= n_rows, when the call's record range cuts the suffix, or when the pass's arena has no room for it.  A row of dy
- * outside the list that is NOT zero is silently dropped: the list must cover them all.  NULL, 0 withdraws a list. */
+ * outside the list that is NOT zero is silently dropped: the list must cover them all.  NULL, 0 withdraws a list.
+ *
+ * A list handed over BEFORE gcl_plan_forward (training mode; gcl_plan_forward_eval ignores it) makes the forward pass run
+ * the suffix on those rows too, under the same rules (a suffix, 2 cap < n_rows, room in the arena -- gcl_plan_arena_bytes
+ * keeps sizing for the dense pass, the upper bound): the suffix's input is gathered once into [cap, cin] (its max-abs slot is
+ * the dense tensor's, a valid bound), the records run through the same entries with cap rows, and the result is scattered
+ * into the zero-filled output.  *y_out is still a dense [n_rows, cout] tensor: THE ROWS OF THE LIST HOLD THE FEATURES, EVERY
+ * OTHER ROW IS EXACTLY ZERO -- for a caller that reads nothing else (the group losses above).  The pass parks the list and
+ * the compact saved operands with its arena; their padding rows are inert (zero input and activations, y = 0 and norm = 1 out
+ * of the row normalisation).  gcl_plan_backward on that arena then gathers dy only and needs no second
+ * gcl_plan_set_touched_rows call (one that names the same rows and cap is accepted; another list is GCL_ERR_ARG), so rows must
+ * stay allocated until that call has returned.  The features of the listed rows and every gradient differ from the dense
+ * pass's in rounding only (the second convolution's input max-abs is taken over fewer rows).  A gcl_plan_backward call whose
+ * record range cuts the suffix of such a pass returns GCL_ERR_ARG: there are no dense operands to fall back to -- hand the list
+ * over after the forward pass when the backward pass is segmented there.  When the rules are not met the forward pass runs
+ * dense and leaves the list for the backward pass, as above. */
 int gcl_plan_touched_suffix(const void* plan);
 int gcl_plan_set_touched_rows(void* plan, const int32_t* rows, int64_t cap);
-/* rows the suffix of the latest gcl_plan_backward call that held the last record ran on: cap, or 0 = the dense records */
+/* rows the suffix of the latest gcl_plan_backward call that held the last record ran on: cap, or 0 = the dense records;
+ * gcl_plan_suffix_fwd_rows_used: the same for the latest gcl_plan_forward call */
 int64_t gcl_plan_suffix_rows_used(const void* plan);
+int64_t gcl_plan_suffix_fwd_rows_used(const void* plan);
 /* The list for the group losses above: the members index[goff[g] .. goff[g + 1]) of the n_sel selected groups g = sel[s],
  * and the rows of two more index arrays (the negative subsets), as rows[cap] = the distinct rows in [0, n_rows), ascending,
  * then -1; *n_touched (device) = their number -- more than cap means the caller's bound was wrong and the list is cut.
