@@ -687,6 +687,16 @@ static int stem_flag(Plan& P, const gcl_plan_op& op, const gcl_map_desc& m, cons
   return GCL_OK;
 }
 
+// the mask-sorted table of a map a launch walks: over the map's output rows, or (transposed) over its input rows; a
+// kernel_size-1 map has none
+struct SortedTable {
+  const int32_t *tbl = nullptr, *order = nullptr, *mask = nullptr;
+};
+static SortedTable sorted_table(const gcl_map_desc& m, bool transposed) {
+  if (m.kernel_size == 1) return SortedTable();
+  return transposed ? SortedTable{m.tbl_t, m.order_t, m.mask_t} : SortedTable{m.tbl_n, m.order_n, m.mask_n};
+}
+
 // the convolution of a CONVBN / CONV record (ops._SparseConvFn.forward); returns its output in *y_out
 // rows > 0: a kernel_size-1 record of the touched-row suffix whose input is a compact [rows, cin] tensor
 static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStream_t st, int32_t** relu_amax_out,
@@ -722,20 +732,15 @@ static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStr
   float* stats = nullptr;
   if (op.kind == GCL_OP_CONVBN) stats = A.take_n<float>(cdiv(n_out, 128) * 4 * op.cout);      // sum, squares, min, max per column and 128-row tile
   *stats_out = stats;
-  const int32_t *tbl = nullptr, *order = nullptr, *mask = nullptr;
-  if (m.kernel_size > 1) {
-    tbl = op.transpose ? m.tbl_t : m.tbl_n;
-    order = op.transpose ? m.order_t : m.order_n;
-    mask = op.transpose ? m.mask_t : m.mask_n;
-    GCL_CHECK_ARG(A.dry || tbl, "gcl_plan_forward: record %d needs a sorted table the maps do not carry", i);
-  }
+  const SortedTable T = sorted_table(m, op.transpose);
+  GCL_CHECK_ARG(A.dry || m.kernel_size == 1 || T.tbl, "gcl_plan_forward: record %d needs a sorted table the maps do not carry", i);
   const float* bias = op.bias >= 0 ? (const float*)P.params[op.bias] : nullptr;
   ProfScope ps(P, st, 0, (double)(m.kernel_size > 1 ? m.n_pairs : n_out), op.cin, op.cout, n_in, n_out, op.K);
   int32_t* relu_amax = (op.kind == GCL_OP_CONV && P.fuse_relu[i]) ? new_slot(P) : nullptr;
   *relu_amax_out = relu_amax;
   PLAN_CALL(gcl_conv_fwd_fused(pl ? (const float*)x.planes : x.ptr, n_in, pl ? 1 : 0, P.pack_fwd + P.off_fwd[wi], 4, x.amax,
-                               P.w_amax + (long long)wi * GCL_AMAX_WORDS, tbl, order, mask, n_out, op.K, op.cin, op.cout, bias,
-                               nullptr, nullptr, relu_amax ? 1 : 0, relu_amax, y, stats, 0, (void*)st));
+                               P.w_amax + (long long)wi * GCL_AMAX_WORDS, T.tbl, T.order, T.mask, n_out, op.K, op.cin, op.cout,
+                               bias, nullptr, nullptr, relu_amax ? 1 : 0, relu_amax, y, stats, 0, (void*)st));
   return GCL_OK;
 }
 
@@ -767,6 +772,23 @@ static int upload_tables(Plan& P, hipStream_t st) {
     GCL_CHECK_HIP(hipStreamSynchronize(st));
     P.uploaded = h;
   }
+  return GCL_OK;
+}
+
+// The compact [cap, c] result of the touched-row suffix as a dense tensor: *out = a zero-filled [n, c] tensor that holds
+// src[j] in row rows[j].  norm (the forward pass behind a row normalisation): src and norm are the saved y and norm, whose
+// rows that belong to no row of the output are made inert on the way (k_scatter_rows_inert)
+static int spread_rows(Plan& P, float* src, float* norm, const int32_t* rows, long long cap, int c, long long n, float** out,
+                       hipStream_t st) {
+  Arena& A = P.A;
+  float* dst = A.take_n<float>(n * c);
+  *out = dst;
+  if (A.dry) return GCL_OK;
+  GCL_CHECK_HIP(hipMemsetAsync(dst, 0, (size_t)(n * c) * sizeof(float), st));
+  if (!norm) return gcl_scatter_rows(src, rows, cap, c, n, dst, c, (void*)st);
+  hipLaunchKernelGGL(k_scatter_rows_inert, dim3(grid_for(cap * c / 4)), dim3(256), 0, st, (float4*)src, norm, (const int*)rows,
+                     cap, c / 4, n, dst, c);
+  GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
 
@@ -880,19 +902,15 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
           }
           const int wi = P.widx[op.w];
           if ((rc = ensure_amax(P, x, n_in * op.cin, st))) return rc;
-          const int32_t *tbl = nullptr, *order = nullptr, *mask = nullptr;
-          if (m.kernel_size > 1) {
-            tbl = op.transpose ? m.tbl_t : m.tbl_n;
-            order = op.transpose ? m.order_t : m.order_n;
-            mask = op.transpose ? m.mask_t : m.mask_n;
-            GCL_CHECK_ARG(A.dry || tbl, "gcl_plan_forward_eval: record %d needs a sorted table the maps do not carry", (int)i);
-          }
+          const SortedTable T = sorted_table(m, op.transpose);
+          GCL_CHECK_ARG(A.dry || m.kernel_size == 1 || T.tbl,
+                        "gcl_plan_forward_eval: record %d needs a sorted table the maps do not carry", (int)i);
           // scratch of the offset-group launches (small deep layers of an inference pass; 0: the shape / size takes another kernel)
-          const long long gs_len = tbl ? gcl_conv_fwd_groups_scratch_len(n_out, op.K, op.cin, c) : 0;
+          const long long gs_len = T.tbl ? gcl_conv_fwd_groups_scratch_len(n_out, op.K, op.cin, c) : 0;
           float* gscratch = gs_len > 0 ? A.take_n<float>(gs_len) : nullptr;
           ProfScope ps(P, st, 0, (double)(m.kernel_size > 1 ? m.n_pairs : n_out), op.cin, c, n_in, n_out, op.K);
           PLAN_CALL(gcl_conv_fwd_fused(x.ptr, n_in, 0, P.pack_fwd + P.off_fwd[wi], 4, x.amax,
-                                       P.w_amax + (long long)wi * GCL_AMAX_WORDS, tbl, order, mask, n_out, op.K, op.cin, c,
+                                       P.w_amax + (long long)wi * GCL_AMAX_WORDS, T.tbl, T.order, T.mask, n_out, op.K, op.cin, c,
                                        (const float*)be[1], (const float*)be[0], res, op.relu, y.amax, y.ptr, gscratch,
                                        GCL_CONV_TALL, (void*)st));
           break;
@@ -1019,22 +1037,9 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
   if (late_pending) GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));      // (the arena outlives the side stream's work)
   *y_out = P.t[P.ops.back().y].ptr;
   if (P.fwd_cap > 0) {      // the pass's output stays dense: the rows of the list hold the features, every other row is zero
-    const gcl_plan_op& last = P.ops.back();
-    const long long n = M.n_rows[last.level_out];
-    float* yc = *y_out;
-    float* out = A.take_n<float>(n * last.cout);
-    if (!A.dry) {
-      GCL_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)(n * last.cout) * sizeof(float), st));
-      if (last.kind == GCL_OP_ROWNORM) {      // ... and the padding rows of the saved y and norm become (0, 1)
-        hipLaunchKernelGGL(k_scatter_rows_inert, dim3(grid_for(P.fwd_cap * last.cout / 4)), dim3(256), 0, st, (float4*)yc,
-                           P.saved[P.ops.size() - 1].norm, (const int*)P.fwd_rows, P.fwd_cap, last.cout / 4, n, out, last.cout);
-        GCL_CHECK_LAUNCH();
-      } else {
-        int rc = gcl_scatter_rows(yc, P.fwd_rows, P.fwd_cap, last.cout, n, out, last.cout, (void*)st);
-        if (rc) return rc;
-      }
-    }
-    *y_out = out;
+    const gcl_plan_op& last = P.ops.back();      // ... and the padding rows of a saved y and norm become (0, 1)
+    return spread_rows(P, *y_out, last.kind == GCL_OP_ROWNORM ? P.saved[P.ops.size() - 1].norm : nullptr, P.fwd_rows, P.fwd_cap,
+                       last.cout, M.n_rows[last.level_out], y_out, st);
   }
   return GCL_OK;
 }
@@ -1086,13 +1091,49 @@ static int contiguous(Plan& P, TState& g, long long rows, int c, hipStream_t st)
   return GCL_OK;
 }
 
+// The rows the backward of a record runs on, and where its saved operands come from.  cap == 0: every row of the record's
+// level, the saved tensors as they are.  cap > 0: the rows of a list (rows[cap]: distinct rows of [0, n) ascending, -1
+// padding) -- the records of the touched-row suffix run through the entries the dense pass calls, with cap rows, on compact
+// [cap, c] tensors.  A row's results do not depend on the other rows of a launch, and a row of dy that is zero gives a zero
+// row of every gradient and adds nothing to a weight gradient: the input gradient is the dense pass's row for row, the weight
+// gradients are its sums over fewer rows in other groups.  The -1 padding rows are zero rows throughout (their norm reads 1:
+// no 0 / 0).  The saved operands are gathered onto the list, each once (`gathered`); after a forward pass that ran the
+// suffix on this list (`parked`, P.fwd_cap > 0) they ARE the compact tensors, with inert padding rows.
+struct RowView {
+  const int32_t* rows = nullptr;
+  long long cap = 0, n = 0;
+  bool parked = false;
+  std::vector<std::pair<const float*, float*>> gathered;
+  long long n_rows(const gcl_maps_desc& M, int level) const { return cap > 0 ? cap : M.n_rows[level]; }
+};
+
+// *out = the saved operand src ([n, c], row pitch ld) on the rows of V; pad: the value of its padding rows
+static int saved_rows(Plan& P, RowView& V, const float* src, int ld, int c, float pad, hipStream_t st, const float** out) {
+  Arena& A = P.A;
+  *out = src;
+  if (V.cap <= 0 || V.parked) return GCL_OK;
+  for (auto& e : V.gathered)
+    if (e.first == src) {
+      *out = e.second;
+      return GCL_OK;
+    }
+  float* rows = A.take_n<float>(V.cap * c);
+  PLAN_CALL(gcl_gather_rows(src, ld, V.n, V.rows, V.cap, c, pad, rows, (void*)st));
+  V.gathered.push_back({src, rows});
+  *out = rows;
+  return GCL_OK;
+}
+static int saved_rows(Plan& P, RowView& V, const TState& t, int c, hipStream_t st, const float** out) {
+  return saved_rows(P, V, t.ptr, t.ld ? t.ld : c, c, 0.f, st, out);
+}
+
 // ops._SparseConvFn.backward for record i with output gradient dy (dy.amax set when a producer published it)
-static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStream_t st) {
+static int conv_backward(Plan& P, int i, TState dy, RowView& V, void* const* grads, hipStream_t st) {
   Arena& A = P.A;
   const gcl_plan_op& op = P.ops[i];
   const gcl_maps_desc& M = *P.maps;
   const gcl_map_desc& m = M.maps[op.map];
-  const long long n_in = M.n_rows[op.level_in], n_out = M.n_rows[op.level_out];
+  const long long n_in = V.n_rows(M, op.level_in), n_out = V.n_rows(M, op.level_out);
   TState& x = P.t[op.x];
   float* dW = (float*)grads[op.w];
   int rc;
@@ -1108,22 +1149,24 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
   if ((rc = ensure_amax(P, dy, n_out * op.cout, st))) return rc;
   const int32_t* w_amax = P.w_amax + (long long)wi * GCL_AMAX_WORDS;
   const double pairs = (double)(m.kernel_size > 1 ? m.n_pairs : n_out);
-  const bool pl_w = op.cin >= P.presplit && op.cout >= P.presplit;      // weight gradient on plane images
+  // kernel_size 1: both operands of the weight gradient streamed once in fp32, no pair list (as ops._ConvFn.backward decides)
+  const long long rows_len = m.kernel_size == 1 ? gcl_conv_bwd_weight_rows_scratch_len(op.cin, op.cout, 4, n_in) : 0;
+  const bool pl_w = rows_len <= 0 && op.cin >= P.presplit && op.cout >= P.presplit;      // weight gradient on plane images
   const bool pl_x = op.cout >= P.presplit;                              // input gradient reads dy's plane image
   if ((pl_w || (pl_x && P.made[op.x])) && (rc = ensure_planes(P, dy, n_out, op.cout, st))) return rc;
   if (pl_w) {
     x.amax = P.saved[i].x_amax;
     if ((rc = ensure_planes(P, x, n_in, op.cin, st))) return rc;
   }
+  const float* xr;      // the fp32 rows of x: what the row-stream weight gradient and a ReLU mask in the epilogue read
+  if ((rc = saved_rows(P, V, x, op.cin, st, &xr))) return rc;
   // every operand of the weight gradient is enqueued: fork here, so that it runs beside the input gradient below
   hipStream_t ws = fork_aux(P, st);
   if (P.made[op.x]) {      // input gradient: the same output-stationary kernel over the opposite table
-    int mode;
-    const int32_t *tbl = nullptr, *order = nullptr, *mask = nullptr;
-    if (m.kernel_size == 1) mode = 1;
-    else if (op.transpose) { mode = 1; tbl = m.tbl_n; order = m.order_n; mask = m.mask_n; }
-    else if (m.stride == 1) { mode = 2; tbl = m.tbl_n; order = m.order_n; mask = m.mask_n; }
-    else { mode = 1; tbl = m.tbl_t; order = m.order_t; mask = m.mask_t; }
+    // mirrored offsets over the same table on a stride-1 map, the plain transpose over the opposite table otherwise
+    const int mode = (m.kernel_size > 1 && !op.transpose && m.stride == 1) ? 2 : 1;
+    const SortedTable T = sorted_table(m, !op.transpose && m.stride != 1);
+    const int32_t *tbl = T.tbl, *order = T.order, *mask = T.mask;
     GCL_CHECK_ARG(mode == P.wmode[wi], "gcl_plan_backward: record %d: input-gradient pack mode mismatch", i);
     GCL_CHECK_ARG(A.dry || m.kernel_size == 1 || tbl, "gcl_plan_backward: record %d needs a sorted table the maps do not carry", i);
     const bool pl = pl_x;
@@ -1141,7 +1184,7 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
         // x came out of a ReLU that nothing else reads: its backward (g where y > 0) in this epilogue, max|g| published
         dx_amax = new_slot(P);
         PLAN_CALL(gcl_conv_fwd_fused(pl ? (const float*)dy.planes : dy.ptr, n_out, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4,
-                                     dy.amax, w_amax, tbl, order, mask, n_in, op.K, op.cout, op.cin, nullptr, nullptr, x.ptr, 2,
+                                     dy.amax, w_amax, tbl, order, mask, n_in, op.K, op.cout, op.cin, nullptr, nullptr, xr, 2,
                                      dx_amax, dx, nullptr, 0, (void*)st));
         if (P.relu_masked.size() != P.ops.size()) P.relu_masked.assign(P.ops.size(), 0);
         P.relu_masked[P.mask_from[i]] = 1;
@@ -1153,13 +1196,13 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
     P.g[op.x].ptr = dx;
     P.g[op.x].amax = dx_amax;
   }
-  const long long rows_len = m.kernel_size == 1 ? gcl_conv_bwd_weight_rows_scratch_len(op.cin, op.cout, 4, n_in) : 0;
-  if (rows_len > 0) {      // kernel_size 1: both operands streamed once, no pair list (as ops._ConvFn.backward decides)
+  if (rows_len > 0) {
     float* scratch = A.take_n<float>(rows_len);
     ProfScope ps(P, ws, 3, pairs, op.cin, op.cout, n_in, n_out, op.K);
-    PLAN_CALL(gcl_conv_bwd_weight_rows(x.ptr, dy.ptr, n_in, op.cin, op.cout, 4, P.saved[i].x_amax, dy.amax, scratch, dW,
+    PLAN_CALL(gcl_conv_bwd_weight_rows(xr, dy.ptr, n_in, op.cin, op.cout, 4, P.saved[i].x_amax, dy.amax, scratch, dW,
                                        (void*)ws));
   } else {      // weight gradient over the compacted pair lists
+    GCL_CHECK_ARG(V.cap <= 0, "gcl_plan_backward: record %d: the pair-list weight gradient does not run on a row list", i);
     const int32_t *pa = m.pair_in, *pb = m.pair_out;
     if (op.transpose) { pa = m.pair_out; pb = m.pair_in; }
     GCL_CHECK_ARG(A.dry || (pa && pb), "gcl_plan_backward: record %d needs pair lists the maps do not carry", i);
@@ -1181,112 +1224,111 @@ static int conv_backward(Plan& P, int i, TState dy, void* const* grads, hipStrea
   return GCL_OK;
 }
 
-// The records of the touched-row suffix on the rows of a list (rows[cap]: distinct rows ascending, -1 padding): dy and every
-// saved operand are gathered once into compact [cap, c] tensors, the records run through the entries the dense pass calls,
-// with cap rows, and *g_out is the compact gradient of the suffix's input.  A row's results do not depend on the other rows
-// of a launch, and a row of dy that is zero gives a zero row of every gradient and adds nothing to a weight gradient: the
-// input gradient is the dense pass's row for row, the weight gradients are its sums over fewer rows in other groups.  The
-// -1 padding rows are zero rows throughout (their norm reads 1: no 0 / 0).
-// After a forward pass that ran the suffix on this list (P.fwd_cap > 0) the saved operands ARE the compact tensors, with
-// inert padding rows, and only dy is gathered.
-static int suffix_backward(Plan& P, const float* dy, void* const* grads, const int32_t* rows, long long cap, TState* g_out,
-                           hipStream_t st) {
+// Tape.backward for record i on the rows of V: takes the gradient of the record's output out of P.g and gives the gradients
+// of its inputs
+static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipStream_t st) {
   Arena& A = P.A;
   const gcl_maps_desc& M = *P.maps;
-  const int n_ops = (int)P.ops.size();
-  const long long n = M.n_rows[P.ops.back().level_out];
-  const bool parked = P.fwd_cap > 0;
-  std::vector<std::pair<const float*, float*>> gathered;      // a saved operand two records read is gathered once
-  auto gather = [&](const float* src, int ld, int c, float pad) -> float* {
-    if (parked && src != dy) return (float*)src;
-    for (auto& e : gathered)
-      if (e.first == src) return e.second;
-    float* out = A.take_n<float>(cap * c);
-    if (!A.dry && gcl_gather_rows(src, ld, n, rows, cap, c, pad, out, (void*)st) != GCL_OK) return nullptr;
-    gathered.push_back({src, out});
-    return out;
-  };
-  std::vector<char> masked(P.ops.size(), 0);      // RELU record whose backward the consumer's epilogue has applied
-  TState g;
-  g.ptr = gather(dy, P.ops.back().cout, P.ops.back().cout, 0.f);
-  if (!g.ptr) return GCL_ERR_ARG;
+  const gcl_plan_op& op = P.ops[i];
+  const long long n_out = V.n_rows(M, op.level_out), n_in = V.n_rows(M, op.level_in);
+  TState g = P.g[op.y];
+  P.g[op.y] = TState();
+  if (!g.ptr) return GCL_OK;
   int rc;
-  for (int i = n_ops - 1; i >= P.suffix_first && g.ptr; --i) {
-    const gcl_plan_op& op = P.ops[i];
-    switch (op.kind) {
-      case GCL_OP_ROWNORM: {
-        const float* y = gather(P.t[op.y].ptr, op.cout, op.cout, 0.f);
-        const float* norm = gather(P.saved[i].norm, 1, 1, 1.f);
-        float* dx = A.take_n<float>(cap * op.cin);
-        int32_t* slot = new_slot(P);
-        PLAN_CALL(gcl_row_normalize_bwd(y, g.ptr, norm, cap, op.cout, dx, slot, (void*)st));
-        g = TState();
-        g.ptr = dx;
-        g.amax = slot;
-        break;
-      }
-      case GCL_OP_RELU: {
-        if (masked[i]) break;      // g is the gradient of the ReLU's input already
-        const float* y = gather(P.t[op.y].ptr, P.t[op.y].ld ? P.t[op.y].ld : op.cout, op.cout, 0.f);
-        const long long numel = cap * op.cout;
-        float* gx = A.take_n<float>(numel);
-        int32_t* slot = new_slot(P);
-        if (!A.dry) {
-          hipLaunchKernelGGL(k_relu_bwd, dim3(grid_for(numel / 4)), dim3(256), 0, st, (const float4*)g.ptr, (const float4*)y,
-                             numel / 4, (float4*)gx, slot);
-          GCL_CHECK_LAUNCH();
-        }
-        g = TState();
-        g.ptr = gx;
-        g.amax = slot;
-        break;
-      }
-      case GCL_OP_CONV: {      // conv_backward with kernel_size 1 on cap rows
-        const TState& x = P.t[op.x];
-        const int wi = P.widx[op.w];
-        if ((rc = ensure_amax(P, g, cap * op.cout, st))) return rc;
-        const int32_t* w_amax = P.w_amax + (long long)wi * GCL_AMAX_WORDS;
-        const bool pl = op.cout >= P.presplit;
-        if (pl && P.made[op.x] && (rc = ensure_planes(P, g, cap, op.cout, st))) return rc;
-        const float* xc = gather(x.ptr, x.ld ? x.ld : op.cin, op.cin, 0.f);
-        if (!A.dry) GCL_CHECK_LAUNCH();
-        hipStream_t ws = fork_aux(P, st);      // behind the gathers the weight gradient reads
-        TState d;
-        if (P.made[op.x]) {
-          GCL_CHECK_ARG(P.wmode[wi] == 1, "gcl_plan_backward: record %d: input-gradient pack mode mismatch", i);
-          d.ptr = A.take_n<float>(cap * op.cin);
-          ProfScope ps(P, st, 0, (double)cap, op.cout, op.cin, cap, cap, op.K);
-          if (P.mask_from[i] >= 0) {
-            d.amax = new_slot(P);
-            PLAN_CALL(gcl_conv_fwd_fused(pl ? (const float*)g.planes : g.ptr, cap, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4,
-                                         g.amax, w_amax, nullptr, nullptr, nullptr, cap, op.K, op.cout, op.cin, nullptr, nullptr,
-                                         xc, 2, d.amax, d.ptr, nullptr, 0, (void*)st));
-            masked[P.mask_from[i]] = 1;
-          } else
-            PLAN_CALL(gcl_conv_fwd(pl ? (const float*)g.planes : g.ptr, cap, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4, g.amax,
-                                   w_amax, nullptr, nullptr, nullptr, cap, op.K, op.cout, op.cin, nullptr, d.ptr, nullptr, 0,
-                                   (void*)st));
-        }
-        {
-          float* scratch = A.take_n<float>(gcl_conv_bwd_weight_rows_scratch_len(op.cin, op.cout, 4, cap));
-          ProfScope ps(P, ws, 3, (double)cap, op.cin, op.cout, cap, cap, op.K);
-          PLAN_CALL(gcl_conv_bwd_weight_rows(xc, g.ptr, cap, op.cin, op.cout, 4, P.saved[i].x_amax, g.amax, scratch,
-                                             (float*)grads[op.w], (void*)ws));
-        }
-        if (op.bias >= 0) {
-          double* scratch = A.take_n<double>(gcl_bn_scratch_len(cap, op.cout));
-          PLAN_CALL(gcl_col_sum(g.ptr, cap, op.cout, scratch, (float*)grads[op.bias], (void*)ws));
-        }
-        g = d;
-        break;
-      }
-      default:
-        return GCL_ERR_ARG;
+  switch (op.kind) {
+    case GCL_OP_CONVBN: {
+      const OpSaved& sv = P.saved[i];
+      const int c = op.cout;
+      float* sum_g = (float*)grads[op.bn_b];
+      float* sum_gx = (float*)grads[op.bn_w];
+      double* scratch = A.take_n<double>(gcl_bn_scratch_len(n_out, c));
+      // bound mode: dx is read as a plane image by the input gradient (and by the weight gradient when both widths allow)
+      const bool bound = sv.xrange && c >= P.presplit && !is_stem(op, M.maps[op.map]);
+      TState d;
+      d.ptr = A.take_n<float>(n_out * c);
+      d.amax = new_slot(P);
+      PLAN_CALL(gcl_bn_bwd_reduce_range(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean, sv.rstd,
+                                        op.relu, scratch, sum_g, sum_gx, sv.xrange, (const float*)P.params[op.bn_w],
+                                        bound ? d.amax : nullptr, (void*)st));
+      if (bound) d.planes = A.take(n_out * c * 4);
+      float* dres = op.x2 >= 0 ? A.take_n<float>(n_out * c) : nullptr;
+      PLAN_CALL(gcl_bn_bwd_apply_planes(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean,
+                                        sv.rstd, (const float*)P.params[op.bn_w], sum_g, sum_gx, op.relu, d.ptr, dres,
+                                        d.amax, d.planes, (void*)st));
+      if ((rc = conv_backward(P, i, d, V, grads, st))) return rc;
+      return give(P, op.x2, dres, n_out * c, st, nullptr, 0, c);
     }
+    case GCL_OP_CONV:
+      if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
+      return conv_backward(P, i, g, V, grads, st);
+    case GCL_OP_RELU: {
+      if ((size_t)i < P.relu_masked.size() && P.relu_masked[i]) {      // applied by the consumer's input-gradient epilogue
+        P.relu_masked[i] = 0;
+        return give(P, op.x, g.ptr, n_out * op.cout, st, g.amax, g.ld, op.cout);
+      }
+      if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
+      const float* y;
+      if ((rc = saved_rows(P, V, P.t[op.y], op.cout, st, &y))) return rc;
+      const long long numel = n_out * op.cout;
+      float* gx = A.take_n<float>(numel);
+      int32_t* slot = new_slot(P);
+      if (!A.dry) {
+        hipLaunchKernelGGL(k_relu_bwd, dim3(grid_for(numel / 4)), dim3(256), 0, st, (const float4*)g.ptr, (const float4*)y,
+                           numel / 4, (float4*)gx, slot);
+        GCL_CHECK_LAUNCH();
+      }
+      return give(P, op.x, gx, numel, st, slot, 0, op.cout);
+    }
+    case GCL_OP_CAT: {
+      // the gradients of the two inputs ARE the column slices of g: handed on as views (row pitch = the cat's width); their
+      // readers -- the BatchNorm backward kernels, a convolution epilogue that adds a waiting gradient -- take the pitch
+      const int ca = op.cin, cb = op.cout - op.cin;
+      if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
+      if ((rc = give(P, op.x, g.ptr, n_out * ca, st, nullptr, op.cout, ca))) return rc;
+      return give(P, op.x2, g.ptr + ca, n_out * cb, st, nullptr, op.cout, cb);
+    }
+    case GCL_OP_ROWNORM: {
+      if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
+      const float *y, *norm;
+      if ((rc = saved_rows(P, V, P.t[op.y], op.cout, st, &y))) return rc;
+      if ((rc = saved_rows(P, V, P.saved[i].norm, 1, 1, 1.f, st, &norm))) return rc;
+      float* dx = A.take_n<float>(n_in * op.cin);
+      int32_t* slot = new_slot(P);
+      PLAN_CALL(gcl_row_normalize_bwd(y, g.ptr, norm, n_out, op.cout, dx, slot, (void*)st));
+      return give(P, op.x, dx, n_in * op.cin, st, slot, 0, op.cin);
+    }
+    default:
+      set_error("gcl_plan_backward: unknown record kind %d", op.kind);
+      return GCL_ERR_ARG;
   }
-  if (!A.dry) GCL_CHECK_LAUNCH();
-  *g_out = g;
-  return GCL_OK;
+}
+
+// The touched-row suffix on the rows of a list: dy gathered onto it, the records on cap rows (RowView), and the compact
+// gradient of the suffix's input scattered into a zero-filled dense one that is handed on as the records hand theirs on
+static int suffix_backward(Plan& P, const float* dy, void* const* grads, const int32_t* rows, long long cap, hipStream_t st) {
+  Arena& A = P.A;
+  const gcl_plan_op &head = P.ops[P.suffix_first], &tail = P.ops.back();
+  RowView V;
+  V.rows = rows;
+  V.cap = cap;
+  V.n = P.maps->n_rows[head.level_in];
+  V.parked = P.fwd_cap > 0;
+  float* dyc = A.take_n<float>(cap * tail.cout);
+  PLAN_CALL(gcl_gather_rows(dy, tail.cout, V.n, rows, cap, tail.cout, 0.f, dyc, (void*)st));
+  P.g[tail.y] = TState();
+  P.g[tail.y].ptr = dyc;
+  int rc;
+  for (int i = (int)P.ops.size() - 1; i >= P.suffix_first; --i)
+    if ((rc = backward_record(P, i, V, grads, st))) return rc;
+  const TState g = P.g[head.x];      // nothing but the suffix reads this tensor: the compact gradient is all of it
+  P.g[head.x] = TState();
+  if (!g.ptr) {      // the suffix's input wants no gradient (the sizing reserves the room all the same)
+    A.take_n<float>(V.n * head.cin);
+    return GCL_OK;
+  }
+  float* dx;
+  if ((rc = spread_rows(P, g.ptr, nullptr, rows, cap, head.cin, V.n, &dx, st))) return rc;
+  return give(P, head.x, dx, V.n * head.cin, st, g.amax, 0, head.cin);
 }
 
 static int plan_backward(Plan& P, const float* dy, void* const* grads, int first, int last, hipStream_t st,
@@ -1312,137 +1354,53 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
     }
     P.bwd_packed = true;
   }
-  // touched-row suffix: on the rows of the caller's list when there is one and it is short, else dense like every other record
-  int top = last - 1;
+  // touched-row suffix: on the rows of a list when there is one and it is short, else dense like every other record
+  int top = last - 1, rc;
   long long reserve_to = 0;
   if (last == n_ops && !A.dry) P.suffix_rows_used = 0;
   if (last == n_ops && P.suffix_first < n_ops && P.suffix_rows_ok && first <= P.suffix_first) {
-    const gcl_plan_op& head = P.ops[P.suffix_first];
-    const long long n = M.n_rows[head.level_in];
-    const long long off0 = A.off, slot0 = P.next_slot;
-    if (P.fwd_cap > 0) {      // the forward pass ran the suffix on its list and sized the arena for these calls (dry: that sizing)
-      TState g;
-      int rc = suffix_backward(P, dy, grads, P.fwd_rows, P.fwd_cap, &g, st);
-      if (rc) return rc;
-      P.g[P.ops.back().y] = TState();
-      if (g.ptr) {
-        float* dx = A.take_n<float>(n * head.cin);
-        if (!A.dry) {
-          GCL_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)(n * head.cin) * sizeof(float), st));
-          if ((rc = gcl_scatter_rows(g.ptr, P.fwd_rows, P.fwd_cap, head.cin, n, dx, head.cin, (void*)st))) return rc;
-        }
-        if ((rc = give(P, head.x, dx, n * head.cin, st, g.amax, 0, head.cin))) return rc;
+    const long long n = M.n_rows[P.ops[P.suffix_first].level_in];
+    // counted: the same calls without a launch, which leave nothing behind but *end, the arena offset they reached
+    auto run = [&](const int32_t* r, long long c, bool counted, long long* end) {
+      const Arena a0 = A;
+      const long long slot0 = P.next_slot;
+      std::vector<TState> g0;
+      std::vector<char> masked0;
+      if (counted) {
+        g0 = P.g;
+        masked0 = P.relu_masked;
+        A.dry = true;
       }
-      top = P.suffix_first - 1;
-      if (!A.dry) P.suffix_rows_used = P.fwd_cap;
-    } else if (A.dry) {      // sizing: room for the largest list that takes this path (2 cap < n), or for the dense records
-      TState g;
-      const long long cap_max = (n - 1) / 2;
-      if (cap_max > 0) {
-        int rc = suffix_backward(P, dy, grads, nullptr, cap_max, &g, st);
-        if (rc) return rc;
-        A.take_n<float>(n * head.cin);
-        reserve_to = A.off;
-        A.off = off0;
+      const int rcs = suffix_backward(P, dy, grads, r, c, st);
+      *end = A.off;
+      if (counted) {
+        A = a0;
         P.next_slot = slot0;
+        P.g = g0;
+        P.relu_masked = masked0;
       }
-    } else if (rows && cap > 0 && 2 * cap < n) {
-      TState g;
-      A.dry = true;      // the same calls, counted: an arena sized for another bound keeps the dense records
-      int rc = suffix_backward(P, dy, grads, rows, cap, &g, st);
-      A.take_n<float>(n * head.cin);
-      const bool fits = rc == GCL_OK && A.off <= A.size;
-      A.dry = false;
-      A.off = off0;
-      P.next_slot = slot0;
-      if (fits) {
-        if ((rc = suffix_backward(P, dy, grads, rows, cap, &g, st))) return rc;
-        P.g[P.ops.back().y] = TState();
-        if (g.ptr) {      // one zero fill, one scatter: the dense gradient of the suffix's input, handed on as the records do
-          float* dx = A.take_n<float>(n * head.cin);
-          GCL_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)(n * head.cin) * sizeof(float), st));
-          if ((rc = gcl_scatter_rows(g.ptr, rows, cap, head.cin, n, dx, head.cin, (void*)st))) return rc;
-          if ((rc = give(P, head.x, dx, n * head.cin, st, g.amax, 0, head.cin))) return rc;
-        }
-        top = P.suffix_first - 1;
-        P.suffix_rows_used = cap;
-      }
+      return rcs;
+    };
+    long long end = 0;
+    if (P.fwd_cap > 0) {      // the forward pass ran the suffix on its list and sized the arena for these calls (dry: that sizing)
+      rows = P.fwd_rows;
+      cap = P.fwd_cap;
+    } else if (A.dry) {      // sizing: room for the largest list that takes this path (2 cap < n), or for the dense records
+      cap = 0;
+      if ((n - 1) / 2 > 0 && (rc = run(nullptr, (n - 1) / 2, true, &reserve_to))) return rc;
+    } else if (!rows || cap <= 0 || 2 * cap >= n || run(rows, cap, true, &end) != GCL_OK || end > A.size) {
+      cap = 0;      // no list, a long one, or an arena sized for another bound: the dense records
+    }
+    if (cap > 0) {
+      if ((rc = run(rows, cap, false, &end))) return rc;
+      top = P.suffix_first - 1;
+      if (!A.dry) P.suffix_rows_used = cap;
     }
   }
+  RowView dense;
   for (int i = top; i >= first; --i) {
     if (reserve_to && i == P.suffix_first - 1 && A.off < reserve_to) A.off = reserve_to;
-    const gcl_plan_op& op = P.ops[i];
-    const long long n_out = M.n_rows[op.level_out], n_in = M.n_rows[op.level_in];
-    TState g = P.g[op.y];
-    P.g[op.y] = TState();
-    if (!g.ptr) continue;
-    int rc;
-    switch (op.kind) {
-      case GCL_OP_CONVBN: {
-        const OpSaved& sv = P.saved[i];
-        const int c = op.cout;
-        float* sum_g = (float*)grads[op.bn_b];
-        float* sum_gx = (float*)grads[op.bn_w];
-        double* scratch = A.take_n<double>(gcl_bn_scratch_len(n_out, c));
-        // bound mode: dx is read as a plane image by the input gradient (and by the weight gradient when both widths allow)
-        const bool bound = sv.xrange && c >= P.presplit && !is_stem(op, M.maps[op.map]);
-        TState d;
-        d.ptr = A.take_n<float>(n_out * c);
-        d.amax = new_slot(P);
-        PLAN_CALL(gcl_bn_bwd_reduce_range(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean, sv.rstd,
-                                          op.relu, scratch, sum_g, sum_gx, sv.xrange, (const float*)P.params[op.bn_w],
-                                          bound ? d.amax : nullptr, (void*)st));
-        if (bound) d.planes = A.take(n_out * c * 4);
-        float* dres = op.x2 >= 0 ? A.take_n<float>(n_out * c) : nullptr;
-        PLAN_CALL(gcl_bn_bwd_apply_planes(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean,
-                                          sv.rstd, (const float*)P.params[op.bn_w], sum_g, sum_gx, op.relu, d.ptr, dres,
-                                          d.amax, d.planes, (void*)st));
-        if ((rc = conv_backward(P, i, d, grads, st))) return rc;
-        if ((rc = give(P, op.x2, dres, n_out * c, st, nullptr, 0, c))) return rc;
-        break;
-      }
-      case GCL_OP_CONV:
-        if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
-        if ((rc = conv_backward(P, i, g, grads, st))) return rc;
-        break;
-      case GCL_OP_RELU: {
-        if ((size_t)i < P.relu_masked.size() && P.relu_masked[i]) {      // applied by the consumer's input-gradient epilogue
-          P.relu_masked[i] = 0;
-          if ((rc = give(P, op.x, g.ptr, n_out * op.cout, st, g.amax, g.ld, op.cout))) return rc;
-          break;
-        }
-        if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
-        const long long numel = n_out * op.cout;
-        float* gx = A.take_n<float>(numel);
-        int32_t* slot = new_slot(P);
-        if (!A.dry) {
-          hipLaunchKernelGGL(k_relu_bwd, dim3(grid_for(numel / 4)), dim3(256), 0, st, (const float4*)g.ptr,
-                             (const float4*)P.t[op.y].ptr, numel / 4, (float4*)gx, slot);
-          GCL_CHECK_LAUNCH();
-        }
-        if ((rc = give(P, op.x, gx, numel, st, slot, 0, op.cout))) return rc;
-        break;
-      }
-      case GCL_OP_CAT: {
-        // the gradients of the two inputs ARE the column slices of g: handed on as views (row pitch = the cat's width); their
-        // readers -- the BatchNorm backward kernels, a convolution epilogue that adds a waiting gradient -- take the pitch
-        const int ca = op.cin, cb = op.cout - op.cin;
-        if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
-        if ((rc = give(P, op.x, g.ptr, n_out * ca, st, nullptr, op.cout, ca))) return rc;
-        if ((rc = give(P, op.x2, g.ptr + ca, n_out * cb, st, nullptr, op.cout, cb))) return rc;
-        break;
-      }
-      case GCL_OP_ROWNORM: {
-        if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
-        float* dx = A.take_n<float>(n_in * op.cin);
-        int32_t* slot = new_slot(P);
-        PLAN_CALL(gcl_row_normalize_bwd(P.t[op.y].ptr, g.ptr, P.saved[i].norm, n_out, op.cout, dx, slot, (void*)st));
-        if ((rc = give(P, op.x, dx, n_in * op.cin, st, slot, 0, op.cin))) return rc;
-        break;
-      }
-      default:
-        return GCL_ERR_ARG;
-    }
+    if ((rc = backward_record(P, i, dense, grads, st))) return rc;
   }
   if (reserve_to && A.off < reserve_to) A.off = reserve_to;
   return join_aux(P, st);      // the caller may hand the gradients of this segment to a collective / the optimizer next
@@ -1470,6 +1428,36 @@ static int check_maps(const Plan& P, const gcl_maps_desc* M) {
 using namespace gcl;
 
 extern "C" {
+
+// Dry run of a pass -- the forward pass, or the forward and the whole backward pass -- with P's maps, parameters and mode as
+// they stand: *need = the arena bytes it takes.  P.A and P.profile come back as they were.  bn_stats NULL: nobody reads them
+static int dry_pass(Plan& P, const float* x, void* const* bn_stats, bool backward, long long* need) {
+  std::vector<void*> nulls(2 * (P.n_bn > 0 ? P.n_bn : 1), nullptr), gn(P.n_params, nullptr);
+  const Arena real = P.A;
+  const bool prof = P.profile;
+  P.A = Arena{DRY_BASE, 0, 0, true};
+  P.profile = false;
+  float* y = nullptr;
+  int rc = plan_forward(P, x, bn_stats ? bn_stats : nulls.data(), &y, nullptr);
+  if (rc == GCL_OK && backward) rc = plan_backward(P, (const float*)DRY_BASE, gn.data(), 0, (int)P.ops.size(), nullptr);
+  *need = P.A.off;
+  P.A = real;
+  P.profile = prof;
+  P.relu_masked.clear();      // (a run that stopped early leaves no ReLU flagged as applied)
+  return rc;
+}
+
+// A forward pass waits for its backward pass in a slot of P.passes, under its arena: park moves the pass being enqueued
+// there, unpark brings it back
+static void park(Plan& P, PassState* slot) {
+  *slot = std::move(static_cast<PassState&>(P));
+  slot->maps = &slot->maps_copy;
+  static_cast<PassState&>(P) = PassState();
+}
+static void unpark(Plan& P, PassState* slot) {
+  static_cast<PassState&>(P) = std::move(*slot);
+  P.maps = &P.maps_copy;
+}
 
 int64_t gcl_maps_arena_bytes(int64_t n, const gcl_map_spec* specs_host, int32_t n_specs, int32_t n_levels) {
   if (n <= 0 || !specs_host || n_specs < 0 || n_specs > GCL_MAX_MAPS || n_levels < 1 || n_levels > GCL_MAX_LEVELS) return -1;
@@ -1681,17 +1669,11 @@ int64_t gcl_plan_arena_bytes(void* plan, const gcl_maps_desc* maps_host) {
   Plan* P = (Plan*)plan;
   if (!P || check_maps(*P, maps_host) != GCL_OK) return -1;
   P->maps = maps_host;
-  P->A = Arena{DRY_BASE, 0, 0, true};
   P->params.assign(P->n_params, nullptr);
-  std::vector<void*> nulls(2 * (P->n_bn > 0 ? P->n_bn : 1), nullptr), gn(P->n_params, nullptr);
-  float* y = nullptr;
-  const bool prof = P->profile;
-  P->profile = false;
-  int rc = plan_forward(*P, nullptr, nulls.data(), &y, nullptr);
-  if (rc == GCL_OK) rc = plan_backward(*P, (const float*)DRY_BASE, gn.data(), 0, (int)P->ops.size(), nullptr);
-  P->profile = prof;
+  long long need = 0;
+  const int rc = dry_pass(*P, nullptr, nullptr, true, &need);
   P->forward_done = false;
-  return rc == GCL_OK ? P->A.off + 4096 : -1;
+  return rc == GCL_OK ? need + 4096 : -1;
 }
 
 int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x, void* const* params_host,
@@ -1708,23 +1690,11 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
   P->A = Arena{(char*)arena, arena_bytes, 0, false};
   P->forward_done = false;
   // size check first (cheap dry run of both passes): never launch into an arena that cannot hold the pass
-  {
-    Arena real = P->A;
-    P->A = Arena{DRY_BASE, 0, 0, true};
-    std::vector<void*> gn(P->n_params, nullptr);
-    float* yy = nullptr;
-    const bool prof = P->profile;
-    P->profile = false;
-    rc = plan_forward(*P, x, bn_stats_host, &yy, nullptr);
-    if (rc == GCL_OK) rc = plan_backward(*P, (const float*)DRY_BASE, gn.data(), 0, (int)P->ops.size(), nullptr);
-    P->profile = prof;
-    const long long need = P->A.off;
-    P->A = real;
-    if (rc) return rc;
-    if (need > arena_bytes) {
-      set_error("gcl_plan_forward: arena too small (%lld bytes needed, %lld given)", need, (long long)arena_bytes);
-      return GCL_ERR_ARENA;
-    }
+  long long need = 0;
+  if ((rc = dry_pass(*P, x, bn_stats_host, true, &need))) return rc;
+  if (need > arena_bytes) {
+    set_error("gcl_plan_forward: arena too small (%lld bytes needed, %lld given)", need, (long long)arena_bytes);
+    return GCL_ERR_ARENA;
   }
   // a list handed over before the pass: the touched-row suffix runs on its rows in this pass too, under the rules of the
   // backward pass -- a suffix, shapes the row-stream weight gradient takes, 2 cap < n_rows, and room in the arena for both
@@ -1733,22 +1703,12 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
   P->suffix_fwd_rows_used = 0;
   if (P->touched && P->touched_cap > 0 && P->suffix_first < n_ops && P->suffix_rows_ok && P->ops.back().cout % 4 == 0 &&
       2 * P->touched_cap < maps_host->n_rows[P->ops[P->suffix_first].level_in]) {
-    Arena real = P->A;
-    P->A = Arena{DRY_BASE, 0, 0, true};
     P->fwd_rows = P->touched;
     P->fwd_cap = P->touched_cap;
-    std::vector<void*> gn(P->n_params, nullptr);
-    float* yy = nullptr;
-    const bool prof = P->profile;
-    P->profile = false;
-    rc = plan_forward(*P, x, bn_stats_host, &yy, nullptr);
-    if (rc == GCL_OK) rc = plan_backward(*P, (const float*)DRY_BASE, gn.data(), 0, n_ops, nullptr);
-    P->profile = prof;
-    if (rc != GCL_OK || P->A.off > arena_bytes) {
+    if (dry_pass(*P, x, bn_stats_host, true, &need) != GCL_OK || need > arena_bytes) {
       P->fwd_rows = nullptr;
       P->fwd_cap = 0;
     }
-    P->A = real;
   }
   rc = plan_forward(*P, x, bn_stats_host, y_out_host, (hipStream_t)stream);
   P->forward_done = rc == GCL_OK;
@@ -1772,9 +1732,7 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
     P->passes.push_back(slot);
   }
   P->key = arena;
-  *slot = std::move(static_cast<PassState&>(*P));
-  slot->maps = &slot->maps_copy;
-  static_cast<PassState&>(*P) = PassState();
+  park(*P, slot);
   return GCL_OK;
 }
 
@@ -1789,20 +1747,15 @@ int64_t gcl_plan_eval_arena_bytes(void* plan, const gcl_maps_desc* maps_host) {
   Plan* P = (Plan*)plan;
   if (!P || check_maps(*P, maps_host) != GCL_OK) return -1;
   P->maps = maps_host;
-  P->A = Arena{DRY_BASE, 0, 0, true};
   P->params.assign(P->n_params, nullptr);
   P->eval = true;
   P->bn_eval = nullptr;
   P->state = DRY_BASE;
-  std::vector<void*> nulls(2 * (P->n_bn > 0 ? P->n_bn : 1), nullptr);
-  float* y = nullptr;
-  const bool prof = P->profile;
-  P->profile = false;
-  int rc = plan_forward(*P, nullptr, nulls.data(), &y, nullptr);
-  P->profile = prof;
+  long long need = 0;
+  const int rc = dry_pass(*P, nullptr, nullptr, false, &need);
   P->eval = false;
   P->forward_done = false;
-  return rc == GCL_OK ? P->A.off + 4096 : -1;
+  return rc == GCL_OK ? need + 4096 : -1;
 }
 
 int gcl_plan_forward_eval(void* plan, const gcl_maps_desc* maps_host, const float* x, void* const* params_host,
@@ -1821,13 +1774,8 @@ int gcl_plan_forward_eval(void* plan, const gcl_maps_desc* maps_host, const floa
   P->bn_eval = bn_eval_host;
   P->eval_repack = repack != 0;
   std::vector<void*> nulls(2 * (P->n_bn > 0 ? P->n_bn : 1), nullptr);
-  P->A = Arena{DRY_BASE, 0, 0, true};      // size check first
-  float* yy = nullptr;
-  const bool prof = P->profile;
-  P->profile = false;
-  rc = plan_forward(*P, x, nulls.data(), &yy, nullptr);
-  P->profile = prof;
-  const long long need = P->A.off;
+  long long need = 0;      // size check first
+  rc = dry_pass(*P, x, nulls.data(), false, &need);
   if (rc == GCL_OK && need > arena_bytes) {
     set_error("gcl_plan_forward_eval: arena too small (%lld bytes needed, %lld given)", need, (long long)arena_bytes);
     rc = GCL_ERR_ARENA;
@@ -1888,8 +1836,7 @@ int gcl_plan_backward(void* plan, void* arena, const float* dy, void* const* gra
                   "ran on the rows of a list: there are no dense operands to fall back to",
                   (int)first_op, (int)last_op, P->suffix_first, (int)P->ops.size());
   }
-  static_cast<PassState&>(*P) = std::move(*slot);
-  P->maps = &P->maps_copy;
+  unpark(*P, slot);
   int rc = plan_backward(*P, dy, grads_host, first_op, last_op, (hipStream_t)stream, rows, cap);
   if (rc == GCL_OK && !P->A.fits()) {
     set_error("gcl_plan_backward: arena overrun");
@@ -1900,9 +1847,7 @@ int gcl_plan_backward(void* plan, void* arena, const float* dy, void* const* gra
     rc = GCL_ERR_ARG;
   }
   if (first_op == 0 || rc != GCL_OK) P->forward_done = false;      // the pass is finished (or broken): its slot is free again
-  *slot = std::move(static_cast<PassState&>(*P));
-  slot->maps = &slot->maps_copy;
-  static_cast<PassState&>(*P) = PassState();
+  park(*P, slot);
   return rc;
 }
 

@@ -132,13 +132,14 @@ def test_gather_and_scatter_rows_are_exact(c, ld, off):
 # ---------------------------------------------------------------------------------------------------------------
 # plan level: ResUNetBN2C on one cloud, dF non-zero on 37 / 0 / 129 rows
 # ---------------------------------------------------------------------------------------------------------------
-_CASE = {}
+_CASE, _CASE_PLANES = {}, {}
 
 
-def _case():
-    """Model, maps, recorded plan and the fp64 oracle's graph: made once, shared by the plan-level tests, never changed."""
-    if _CASE:
-        return _CASE
+def _case(cache=_CASE, oracle=None):
+    """Model, maps, recorded plan and the fp64 oracle's graph: made once, shared by the plan-level tests, never changed.
+    ``oracle``: an earlier case whose model has the same parameters, and whose oracle graph this one shares."""
+    if cache:
+        return cache
     import gcl_amd.MinkowskiEngine as ME
     from gcl_amd import synthetic
     from gcl_amd.MinkowskiEngine import native
@@ -157,8 +158,12 @@ def _case():
                 p.uniform_(-0.1, 0.1)
     st = {k: v.detach().cpu().double().clone() for k, v in m.state_dict().items() if "num_batches" not in k}
     m.train()
-    so = {k: v.clone().requires_grad_("running" not in k) for k, v in st.items()}
-    Fo = O.resunet_forward(so, C.numpy(), feats.double(), 3, True, True, 0.05)
+    if oracle is not None:
+        assert st.keys() == oracle["st"].keys() and all(torch.equal(v, oracle["st"][k]) for k, v in st.items())
+        so, Fo = oracle["so"], oracle["Fo"]
+    else:
+        so = {k: v.clone().requires_grad_("running" not in k) for k, v in st.items()}
+        Fo = O.resunet_forward(so, C.numpy(), feats.double(), 3, True, True, 0.05)
     with torch.cuda.device(DEV):
         Cd, Fd = C.to(DEV), feats.to(DEV)
         mgr = ME.CoordinateManager.build_native(Cd, m.native_map_specs())
@@ -166,8 +171,8 @@ def _case():
         m(ME.SparseTensor(Fd, coordinates=Cd, coordinate_manager=mgr)).F.sum().backward()      # recorded by the Tape
         assert isinstance(m._plan, native.NetworkPlan), getattr(m, "_plan_error", None)
         m.load_state_dict(state0)
-    _CASE.update(m=m, state0=state0, so=so, Fo=Fo, C=Cd, F=Fd, mgr=mgr, n=len(C))
-    return _CASE
+    cache.update(m=m, state0=state0, st=st, so=so, Fo=Fo, C=Cd, F=Fd, mgr=mgr, n=len(C))
+    return cache
 
 
 def _dF(n, k, seed):
@@ -179,8 +184,9 @@ def _dF(n, k, seed):
     return dF, rows
 
 
-def _backward(case, dF, rows=None, cap=None):
-    """One training pass through the plan; ``rows``: announce them first.  Returns ({name: gradient}, rows the head ran on)."""
+def _backward(case, dF, rows=None, cap=None, before_forward=False):
+    """One training pass through the plan; ``rows``: announce them first -- behind the forward pass, or in front of it.
+    Returns ({name: gradient}, rows the head ran on in the backward pass, the plan)."""
     import gcl_amd.MinkowskiEngine as ME
     lib = _lib.load()
     m = case["m"]
@@ -191,10 +197,12 @@ def _backward(case, dF, rows=None, cap=None):
         x = ME.SparseTensor(case["F"], coordinates=case["C"], coordinate_manager=case["mgr"])
         plan = m.plan_for(x)
         assert plan is not None
+        e = torch.zeros(0, dtype=torch.int64, device=DEV)
+        goff = torch.zeros(1, dtype=torch.int64, device=DEV)
+        if rows is not None and before_forward:
+            plan.touch_loss_rows(e, goff, e, rows.to(DEV), e, case["n"], cap)
         out = m(x).F
-        if rows is not None:
-            e = torch.zeros(0, dtype=torch.int64, device=DEV)
-            goff = torch.zeros(1, dtype=torch.int64, device=DEV)
+        if rows is not None and not before_forward:
             plan.touch_loss_rows(e, goff, e, rows.to(DEV), e, case["n"], cap)
         out.backward(dF.to(DEV))
         torch.cuda.synchronize()
@@ -235,6 +243,41 @@ def test_head_backward_on_touched_rows(k):
     assert used == 0
     for name in dense:
         assert torch.equal(dense[name], again[name]), name
+
+
+@gpu
+def test_head_on_touched_rows_reads_plane_images(monkeypatch):
+    """The same cloud and model with plane images from 64 channels on (PRESPLIT_MIN_C = 64 while a fresh model records its
+    plan): conv1_tr (96 -> 64) reads its input and its output gradient as plane images in the head as well."""
+    from gcl_amd.MinkowskiEngine import ops
+    lib = _lib.load()
+    if not _CASE_PLANES:
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, "PRESPLIT_MIN_C", 64)
+            _case(_CASE_PLANES, oracle=_case())
+    case = _CASE_PLANES
+    n, k, cap = case["n"], 37, 128
+    dF, rows = _dF(n, k, 10 + k)
+    dense, used, _ = _backward(case, dF)
+    assert used == 0
+    comp, used, plan = _backward(case, dF, rows, cap)
+    assert used == cap and lib.gcl_plan_suffix_rows_used(plan.handle) == cap, "the pass did not take the touched-row path"
+    for name in dense:
+        if name not in HEAD:
+            assert torch.equal(dense[name], comp[name]), name
+    fwd, used, plan = _backward(case, dF, rows, cap, before_forward=True)
+    assert lib.gcl_plan_suffix_fwd_rows_used(plan.handle) == cap and used == cap, "the forward pass did not run on the list"
+    so, Fo = case["so"], case["Fo"]
+    for v in so.values():
+        v.grad = None
+    Fo.backward(dF.double(), retain_graph=True)
+    for name in HEAD:
+        ref = so[name].grad
+        e_dense, e_comp, e_fwd = _rel_l2(dense[name], ref), _rel_l2(comp[name], ref), _rel_l2(fwd[name], ref)
+        print(f"[planes from 64] {name}: rel-L2 vs fp64 oracle dense {e_dense:.3e}, list before the backward pass {e_comp:.3e}, "
+              f"before the forward pass {e_fwd:.3e}")
+        assert e_comp <= 2 * e_dense, (name, e_dense, e_comp)
+        assert e_fwd <= 2 * e_dense, (name, e_dense, e_fwd)
 
 
 @gpu

@@ -77,6 +77,45 @@ def test_plan_create_accepts_a_resunet_shaped_graph_and_sizes_its_arena():
     lib.gcl_plan_destroy(h)
 
 
+# (gcl_plan_arena_bytes, gcl_plan_eval_arena_bytes) for _maps(10000, 3000) and for _maps(300, 100), as returned by the library
+# of commit 5445072 ("Head forward: run the row-local records on the rows the loss reads") cross-compiled for gfx950.  The dry
+# sizing walks every record's forward and backward body, the touched-row suffix on the largest list included, so a moved,
+# added or lost arena allocation in any of them changes a number here.
+_ARENA_PINS = {
+    "full": ((45784320, 15055936), (4207744, 617136)),
+    "no_rownorm": ((43151616, 13723648), (4116608, 565248)),      # rec[:9]: the suffix is three records
+    "no_suffix": ((27608064, 7274496), (3536000, 324096)),        # rec[:5]
+    "presplit_64": ((53758464, 20175936), (4451200, 770736)),     # the head's widths read plane images
+}
+
+
+@pytest.mark.parametrize("case", sorted(_ARENA_PINS))
+def test_arena_sizes_are_the_ones_the_dense_and_touched_row_bodies_took_before_they_were_shared(case):
+    lib = _lib.load()
+    rec = _mini_records()
+    kw = dict(n_tensors=11, n_params=18, worder=(3, 6, 9, 12, 15, 16))
+    if case == "no_rownorm":
+        rec, kw["n_tensors"] = rec[:9], 10
+    elif case == "no_suffix":
+        rec, kw = rec[:5], dict(n_tensors=6, n_params=15, worder=(3, 6, 9, 12))
+    if case == "presplit_64":      # _create fixes presplit_min_c = 128
+        arr = (_lib.PlanOp * len(rec))()
+        for a, r in zip(arr, rec):
+            for k, v in r.items():
+                setattr(a, k, v)
+        wo = (ctypes.c_int32 * len(kw["worder"]))(*kw["worder"])
+        h = lib.gcl_plan_create(arr, len(rec), kw["n_tensors"], kw["n_params"], wo, len(kw["worder"]), 64)
+    else:
+        h = _create(rec, **kw)
+    assert h, lib.gcl_last_error()
+    h = ctypes.c_void_p(h)
+    for (n, n1), want in zip(((10000, 3000), (300, 100)), _ARENA_PINS[case]):
+        d = _maps(n, n1)
+        got = (lib.gcl_plan_arena_bytes(h, ctypes.byref(d)), lib.gcl_plan_eval_arena_bytes(h, ctypes.byref(d)))
+        assert got == want, (case, n, got, want)
+    lib.gcl_plan_destroy(h)
+
+
 @pytest.mark.parametrize("mutate,why", [
     (lambda r: r[1].update(x=5), "consumes a tensor produced later"),
     (lambda r: r[2].update(w=3), "one parameter in two records (gradients are written, not added)"),
