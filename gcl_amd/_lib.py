@@ -42,6 +42,16 @@ class MapsDesc(ctypes.Structure):     # gcl_maps_desc
                 ("ready_event", _vp), ("late_mask", _i32), ("reserved", _i32), ("maps", MapDesc * MAX_MAPS)]
 
 
+class NnSearch(ctypes.Structure):     # gcl_nn_search
+    _fields_ = [("a", _vp), ("rows_a", _vp), ("b", _vp), ("rows_b", _vp), ("dmin", _vp), ("argmin", _vp), ("pts_a", _vp),
+                ("pts_b", _vp), ("src", _vp), ("tgt", _vp), ("bi_off", _i64), ("part_off", _i64), ("ma", _i32), ("mb", _i32)]
+
+
+class MutualJob(ctypes.Structure):    # gcl_mutual_job
+    _fields_ = [("nn01", _vp), ("nn10", _vp), ("xyz0", _vp), ("xyz1", _vp), ("T", _vp), ("pairs", _vp), ("src", _vp),
+                ("tgt", _vp), ("count", _vp), ("m0", _i32), ("m1", _i32)]
+
+
 class PlanOp(ctypes.Structure):       # gcl_plan_op
     _fields_ = [("kind", _i32), ("x", _i32), ("x2", _i32), ("y", _i32), ("level_in", _i32), ("level_out", _i32),
                 ("cin", _i32), ("cout", _i32), ("map", _i32), ("transpose", _i32), ("K", _i32), ("w", _i32),
@@ -194,6 +204,10 @@ SIGNATURES = {
     "gcl_nn_rowmin_any": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "gcl_nn3_scratch_len": (_i64, [_i32, _i32]),
     "gcl_nn3_rowmin": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gcl_nn_rowmin_batch_scratch_len": (_i64, [_vp, _i32, _i32]),
+    "gcl_nn_rowmin_batch": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gcl_mutual_match_batch": (_i32, [_vp, _vp, _i32, _f32, _vp]),
+    "gcl_mutual_correspondences_batch": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "gcl_mutual_match": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
     "gcl_mutual_correspondences": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "gcl_neg_mask": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),

@@ -10,6 +10,8 @@
 #include <limits.h>
 #include <math.h>
 
+#include <vector>
+
 namespace gcl {
 
 // ---- positive / finest loss: one wave per selected group, lane = channel ------------------------------
@@ -370,15 +372,11 @@ __global__ void __launch_bounds__(256) k_nn_interleave(const float* __restrict__
   *reinterpret_cast<nn_f2*>(bi + 2 * e) = nn_f2{b[r0 * C + c], v1};
 }
 
+// The pieces every search kernel is made of (k_nn_rowmin, k_nn_rowmin_any and their batch forms call the same ones).
+// nn_scan: a thread's running (minimum, lowest index) over the row pairs its wave takes of the B rows [jb, je).
 template <int C>
-__global__ void __launch_bounds__(256) k_nn_rowmin(const float* __restrict__ a, const long long* __restrict__ rows_a,
-                                                   int ma, const float* __restrict__ bi_, int mb, int chunk, int l2,
-                                                   float* __restrict__ out_v, int* __restrict__ out_i) {
-  __shared__ float rv[4][NN_TA];
-  __shared__ int ri[4][NN_TA];
-  const nn_f2* __restrict__ bi = reinterpret_cast<const nn_f2*>(bi_);
-  const int t = threadIdx.x, ar = t & 63, cg = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int arow = blockIdx.x * NN_TA + ar;
+__device__ __forceinline__ void nn_scan(const float* __restrict__ a, const long long* __restrict__ rows_a, int ma, int arow,
+                                        const nn_f2* __restrict__ bi, int jb, int je, int cg, float& best, int& besti) {
   nn_f2 av[C];
   {
     long long src = (arow < ma) ? (rows_a ? rows_a[arow] : (long long)arow) : -1;
@@ -390,10 +388,8 @@ __global__ void __launch_bounds__(256) k_nn_rowmin(const float* __restrict__ a, 
       av[4 * q + 2] = nn_f2{v.z, v.z}; av[4 * q + 3] = nn_f2{v.w, v.w};
     }
   }
-  float best = INFINITY;
-  int besti = 0;
-  const int jb = blockIdx.y * chunk;
-  const int je = (jb + chunk < mb) ? jb + chunk : mb;
+  best = INFINITY;
+  besti = 0;
   for (int p = jb / 2 + cg; 2 * p < je; p += 4) {       // ascending within a thread: strict < keeps the lowest index
     const nn_f2* __restrict__ row = bi + (long long)p * C;
     nn_f2 bv[C];
@@ -413,27 +409,70 @@ __global__ void __launch_bounds__(256) k_nn_rowmin(const float* __restrict__ a, 
       besti = 2 * p + 1;
     }
   }
+}
+
+// The four waves' results of a tile folded through LDS (value, then index).  True for the thread that then holds row
+// `arow`'s (minimum, lowest index) of the chunk: wave 0's lanes with a row inside the matrix.
+__device__ __forceinline__ bool nn_fold_waves(int cg, int ar, bool row_ok, float& best, int& besti) {
+  __shared__ float rv[4][NN_TA];
+  __shared__ int ri[4][NN_TA];
   rv[cg][ar] = best;
   ri[cg][ar] = besti;
   __syncthreads();
-  if (cg == 0 && arow < ma) {
-    float bv = rv[0][ar];
-    int bix = ri[0][ar];
+  if (cg != 0 || !row_ok) return false;
+  float bv = rv[0][ar];
+  int bix = ri[0][ar];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      float v = rv[w][ar];
-      int i2 = ri[w][ar];
-      if (v < bv || (v == bv && i2 < bix)) {
-        bv = v;
-        bix = i2;
-      }
+  for (int w = 1; w < 4; ++w) {
+    float v = rv[w][ar];
+    int i2 = ri[w][ar];
+    if (v < bv || (v == bv && i2 < bix)) {
+      bv = v;
+      bix = i2;
     }
-    if (gridDim.y == 1) {
-      out_v[arow] = l2 ? sqrtf(bv + 1e-7f) : bv;
-      out_i[arow] = bix;
-    } else {
-      out_v[(long long)blockIdx.y * ma + arow] = bv;
-      out_i[(long long)blockIdx.y * ma + arow] = bix;
+  }
+  best = bv;
+  besti = bix;
+  return true;
+}
+
+// the result of a search with ONE chunk goes out as it is returned; a chunk of several leaves its partial result
+__device__ __forceinline__ void nn_store(bool only_chunk, int l2, float bv, int bix, int arow, long long part_row,
+                                         float* __restrict__ out_v, int* __restrict__ out_i) {
+  if (only_chunk) {
+    out_v[arow] = l2 ? sqrtf(bv + 1e-7f) : bv;
+    out_i[arow] = bix;
+  } else {
+    out_v[part_row + arow] = bv;
+    out_i[part_row + arow] = bix;
+  }
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) k_nn_rowmin(const float* __restrict__ a, const long long* __restrict__ rows_a,
+                                                   int ma, const float* __restrict__ bi_, int mb, int chunk, int l2,
+                                                   float* __restrict__ out_v, int* __restrict__ out_i) {
+  const int t = threadIdx.x, ar = t & 63, cg = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int arow = blockIdx.x * NN_TA + ar;
+  const int jb = blockIdx.y * chunk;
+  const int je = (jb + chunk < mb) ? jb + chunk : mb;
+  float best;
+  int besti;
+  nn_scan<C>(a, rows_a, ma, arow, reinterpret_cast<const nn_f2*>(bi_), jb, je, cg, best, besti);
+  if (nn_fold_waves(cg, ar, arow < ma, best, besti))
+    nn_store(gridDim.y == 1, l2, best, besti, arow, (long long)blockIdx.y * ma, out_v, out_i);
+}
+
+// one row's chunks folded in ascending order (strict <: chunks hold ascending index ranges, the lowest index stays)
+__device__ __forceinline__ void nn_merge_row(const float* __restrict__ part_v, const int* __restrict__ part_i, int ma,
+                                             int n_chunks, int r, float& bv, int& bi) {
+  bv = part_v[r];
+  bi = part_i[r];
+  for (int c = 1; c < n_chunks; ++c) {
+    const float v = part_v[(long long)c * ma + r];
+    if (v < bv) {
+      bv = v;
+      bi = part_i[(long long)c * ma + r];
     }
   }
 }
@@ -442,28 +481,23 @@ __global__ void __launch_bounds__(256) k_nn_merge(const float* __restrict__ part
                                                   int n_chunks, int l2, float* __restrict__ dmin, int* __restrict__ argmin) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= ma) return;
-  float bv = part_v[r];
-  int bi = part_i[r];
-  for (int c = 1; c < n_chunks; ++c) {      // chunks hold ascending index ranges: strict < keeps the lowest index
-    const float v = part_v[(long long)c * ma + r];
-    if (v < bv) {
-      bv = v;
-      bi = part_i[(long long)c * ma + r];
-    }
-  }
+  float bv;
+  int bi;
+  nn_merge_row(part_v, part_i, ma, n_chunks, r, bv, bi);
   dmin[r] = l2 ? sqrtf(bv + 1e-7f) : bv;
   argmin[r] = bi;
 }
 
 // B rows per chunk: as many chunks as it takes to put ~1536 workgroups on the chip, each a multiple of NN_GRAN rows
-static int nn_chunk_rows(int ma, int mb) {
-  const long long a_tiles = cdiv(ma, NN_TA);
+// (a batch: a_tiles = the A tiles of all its searches, mb = its largest B)
+static int nn_chunk_rows_tiles(long long a_tiles, int mb) {
   long long want = cdiv(1536, a_tiles);                 // chunks wanted
   const long long grans = cdiv(mb, NN_GRAN);
   if (want > grans) want = grans;
   if (want < 1) want = 1;
   return (int)(cdiv(grans, want) * NN_GRAN);
 }
+static int nn_chunk_rows(int ma, int mb) { return nn_chunk_rows_tiles(cdiv(ma, NN_TA), mb); }
 // scratch (32-bit words): the interleaved copy of B, then the chunks' partial (minimum, index) pairs
 static long long nn_interleaved_words(int mb, int c) { return (long long)cdiv(mb, 2) * 2 * c; }
 
@@ -479,8 +513,8 @@ static long long nn_interleaved_words(int mb, int c) { return (long long)cdiv(mb
 // partial results and the merge are k_nn_rowmin's (k_nn_merge is shared).
 // Measured on an MI355X, 5000 x 5000 (profiles/sc2_bench_probe.txt): 51 us at 32 channels (k_nn_rowmin: 44), 51 at 33, 58 at
 // 40, 92 at 64, 145 at 96, 201 at 128.
-__global__ void __launch_bounds__(256) k_nn_interleave_pad(const float* __restrict__ b, const long long* __restrict__ rows_b,
-                                                           int mb, int c, int cp, float* __restrict__ bi) {
+__device__ __forceinline__ void nn_interleave_pad(const float* __restrict__ b, const long long* __restrict__ rows_b, int mb,
+                                                  int c, int cp, float* __restrict__ bi) {
   const int per = 256 / cp;                                              // row pairs per workgroup (cp <= 128: at least 2)
   const int lp = (int)threadIdx.x / cp, ch = (int)threadIdx.x % cp;      // one (row pair, padded channel) per thread
   const long long p = (long long)blockIdx.x * per + lp;
@@ -491,6 +525,10 @@ __global__ void __launch_bounds__(256) k_nn_interleave_pad(const float* __restri
     if (2 * p + 1 < mb) v1 = b[(rows_b ? rows_b[2 * p + 1] : 2 * p + 1) * c + ch];
   }
   *reinterpret_cast<nn_f2*>(bi + 2 * (p * cp + ch)) = nn_f2{v0, v1};
+}
+__global__ void __launch_bounds__(256) k_nn_interleave_pad(const float* __restrict__ b, const long long* __restrict__ rows_b,
+                                                           int mb, int c, int cp, float* __restrict__ bi) {
+  nn_interleave_pad(b, rows_b, mb, c, cp, bi);
 }
 
 // nn_chain8 with a[k] = the channels (2k, 2k + 1) of the A row: low half broadcast by op_sel:[0,0] op_sel_hi:[0,1], high half
@@ -559,14 +597,9 @@ __device__ __forceinline__ nn_f2 nn_row_dist(const nn_f2* __restrict__ row, cons
 }
 
 template <int CP>
-__global__ void __launch_bounds__(256) k_nn_rowmin_any(const float* __restrict__ a, const long long* __restrict__ rows_a,
-                                                       int ma, int c, const float* __restrict__ bi_, int mb, int chunk,
-                                                       int l2, float* __restrict__ out_v, int* __restrict__ out_i) {
-  __shared__ float rv[4][NN_TA];
-  __shared__ int ri[4][NN_TA];
-  const nn_f2* __restrict__ bi = reinterpret_cast<const nn_f2*>(bi_);
-  const int t = threadIdx.x, ar = t & 63, cg = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int arow = blockIdx.x * NN_TA + ar;
+__device__ __forceinline__ void nn_scan_any(const float* __restrict__ a, const long long* __restrict__ rows_a, int ma, int c,
+                                            int arow, const nn_f2* __restrict__ bi, int jb, int je, int cg, float& best,
+                                            int& besti) {
   nn_f2 av[CP / 2];                                                    // (a_2k, a_2k+1): CP VGPRs
   {
     const long long src = (arow < ma) ? (rows_a ? rows_a[arow] : (long long)arow) : -1;
@@ -574,10 +607,8 @@ __global__ void __launch_bounds__(256) k_nn_rowmin_any(const float* __restrict__
     for (int k = 0; k < CP / 2; ++k)
       av[k] = nn_f2{(src >= 0 && 2 * k < c) ? a[src * c + 2 * k] : 0.f, (src >= 0 && 2 * k + 1 < c) ? a[src * c + 2 * k + 1] : 0.f};
   }
-  float best = INFINITY;
-  int besti = 0;
-  const int jb = blockIdx.y * chunk;
-  const int je = (jb + chunk < mb) ? jb + chunk : mb;
+  best = INFINITY;
+  besti = 0;
   for (int p = jb / 2 + cg; 2 * p < je; p += 4) {       // ascending within a thread: strict < keeps the lowest index
     const nn_f2 acc = nn_row_dist<CP>(bi + (long long)p * CP, av);
     if (acc.x < best) {
@@ -589,29 +620,97 @@ __global__ void __launch_bounds__(256) k_nn_rowmin_any(const float* __restrict__
       besti = 2 * p + 1;
     }
   }
-  rv[cg][ar] = best;
-  ri[cg][ar] = besti;
-  __syncthreads();
-  if (cg == 0 && arow < ma) {                           // k_nn_rowmin's epilogue
-    float bv = rv[0][ar];
-    int bix = ri[0][ar];
+}
+
+template <int CP>
+__global__ void __launch_bounds__(256) k_nn_rowmin_any(const float* __restrict__ a, const long long* __restrict__ rows_a,
+                                                       int ma, int c, const float* __restrict__ bi_, int mb, int chunk,
+                                                       int l2, float* __restrict__ out_v, int* __restrict__ out_i) {
+  const int t = threadIdx.x, ar = t & 63, cg = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int arow = blockIdx.x * NN_TA + ar;
+  const int jb = blockIdx.y * chunk;
+  const int je = (jb + chunk < mb) ? jb + chunk : mb;
+  float best;
+  int besti;
+  nn_scan_any<CP>(a, rows_a, ma, c, arow, reinterpret_cast<const nn_f2*>(bi_), jb, je, cg, best, besti);
+  if (nn_fold_waves(cg, ar, arow < ma, best, besti))
+    nn_store(gridDim.y == 1, l2, best, besti, arow, (long long)blockIdx.y * ma, out_v, out_i);
+}
+
+// ---- a BATCH of searches in the launches of one (gcl_nn_rowmin_batch) ------------------------------------------------------
+// blockIdx.z is the search: its record (gcl_nn_search, a device table the caller filled) is read through wave-uniform
+// loads, so the B rows still arrive as scalars.  The grid's x / y extents are those of the largest search; a workgroup
+// outside its own search's tiles or chunks leaves as a whole before any barrier.  ONE chunk size serves the batch (the
+// minimum is exact and ties go to the lowest index under any chunking, so a search's result does not depend on its
+// neighbours); a search that fits one chunk writes its result from the search kernel, the others from k_nn_merge_batch.
+// Whichever writes argmin[r] also copies the point rows of the correspondence when the record asks for them.
+// The record's output pointers are read AFTER the scan: during it only the interleaved rows' address has to stay in scalar
+// registers (k_nn_rowmin<64> has none to spare).  The search kernel takes scratch as TWO arguments, the interleaved copies
+// it reads and the partial results it writes (disjoint ranges of one block): read and written through one pointer the
+// copies could not be proven unwritten, and the B rows would come through vector loads.
+__device__ __forceinline__ void nn_gather_points(const gcl_nn_search* __restrict__ s, int r, int j) {
+  const float* __restrict__ pa = s->pts_a;
+  if (!pa) return;
+  const float* __restrict__ pb = s->pts_b;
+  const long long* __restrict__ ra = (const long long*)s->rows_a;
+  const long long* __restrict__ rb = (const long long*)s->rows_b;
+  const long long ia = ra ? ra[r] : (long long)r, ib = rb ? rb[j] : (long long)j;
+  float* __restrict__ src = s->src;
+  float* __restrict__ tgt = s->tgt;
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      float v = rv[w][ar];
-      int i2 = ri[w][ar];
-      if (v < bv || (v == bv && i2 < bix)) {
-        bv = v;
-        bix = i2;
-      }
-    }
-    if (gridDim.y == 1) {
-      out_v[arow] = l2 ? sqrtf(bv + 1e-7f) : bv;
-      out_i[arow] = bix;
-    } else {
-      out_v[(long long)blockIdx.y * ma + arow] = bv;
-      out_i[(long long)blockIdx.y * ma + arow] = bix;
-    }
+  for (int k = 0; k < 3; ++k) {
+    src[3 * (long long)r + k] = pa[3 * ia + k];
+    tgt[3 * (long long)r + k] = pb[3 * ib + k];
   }
+}
+
+__global__ void __launch_bounds__(256) k_nn_interleave_batch(const gcl_nn_search* __restrict__ tab, int c, int cp,
+                                                             int32_t* __restrict__ scratch) {
+  const gcl_nn_search* __restrict__ s = tab + blockIdx.z;
+  nn_interleave_pad(s->b, (const long long*)s->rows_b, s->mb, c, cp, (float*)(scratch + s->bi_off));
+}
+
+// W: the channels of k_nn_rowmin<W> (ANY = false; c == W) or the padded channels of k_nn_rowmin_any<W> (ANY = true)
+template <int W, bool ANY>
+__global__ void __launch_bounds__(256) k_nn_rowmin_batch(const gcl_nn_search* __restrict__ tab, int c, int chunk, int l2,
+                                                         const float* __restrict__ copies, int32_t* __restrict__ parts) {
+  const gcl_nn_search* __restrict__ s = tab + blockIdx.z;
+  const int ma = s->ma, mb = s->mb;
+  const int jb = blockIdx.y * chunk;
+  if ((int)blockIdx.x * NN_TA >= ma || jb >= mb) return;               // uniform over the workgroup, before any barrier
+  const int t = threadIdx.x, ar = t & 63, cg = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int arow = blockIdx.x * NN_TA + ar;
+  const int je = (jb + chunk < mb) ? jb + chunk : mb;
+  const nn_f2* __restrict__ bi = reinterpret_cast<const nn_f2*>(copies + s->bi_off);
+  float best;
+  int besti;
+  if constexpr (ANY) nn_scan_any<W>(s->a, (const long long*)s->rows_a, ma, c, arow, bi, jb, je, cg, best, besti);
+  else nn_scan<W>(s->a, (const long long*)s->rows_a, ma, arow, bi, jb, je, cg, best, besti);
+  if (!nn_fold_waves(cg, ar, arow < ma, best, besti)) return;
+  const int n_chunks = (mb + chunk - 1) / chunk;
+  if (n_chunks == 1) {
+    nn_store(true, l2, best, besti, arow, 0, s->dmin, s->argmin);
+    nn_gather_points(s, arow, besti);
+  } else {
+    float* pv = (float*)(parts + s->part_off);
+    nn_store(false, l2, best, besti, arow, (long long)blockIdx.y * ma, pv, (int*)pv + (long long)n_chunks * ma);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_nn_merge_batch(const gcl_nn_search* __restrict__ tab, int chunk, int l2,
+                                                        const int32_t* __restrict__ scratch) {
+  const gcl_nn_search* __restrict__ s = tab + blockIdx.z;
+  const int ma = s->ma, mb = s->mb;
+  const int n_chunks = (mb + chunk - 1) / chunk;
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (n_chunks == 1 || r >= ma) return;                                // one chunk: the search kernel wrote the result
+  const float* pv = (const float*)(scratch + s->part_off);
+  float bv;
+  int bi;
+  nn_merge_row(pv, (const int*)pv + (long long)n_chunks * ma, ma, n_chunks, r, bv, bi);
+  s->dmin[r] = l2 ? sqrtf(bv + 1e-7f) : bv;
+  s->argmin[r] = bi;
+  nn_gather_points(s, r, bi);
 }
 
 // ---- negative-pair mask ---------------------------------------------------------------------------------
@@ -909,6 +1008,118 @@ int gcl_nn_rowmin_any(const float* a, const int64_t* rows_a, int32_t ma, const f
   if (n_chunks > 1)
     hipLaunchKernelGGL(k_nn_merge, dim3((unsigned)cdiv(ma, 256)), dim3(256), 0, st, (const float*)pv, (const int*)pi, ma,
                        n_chunks, l2, dmin, argmin);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+// What the batch entry and its scratch-length function agree on: the batch's chunk size, the grid extents and every
+// search's offsets into scratch.  0 words: nothing to run (bad count, width or an empty search).
+struct NnBatchPlan {
+  int chunk, max_tiles, max_chunks, max_ma, max_pairs;
+  long long words;
+};
+static long long nn_align64(long long words) { return (words + 63) / 64 * 64; }
+static NnBatchPlan nn_batch_plan(const gcl_nn_search* s, int P, int c, long long* bi_off, long long* part_off) {
+  NnBatchPlan pl = {0, 0, 0, 0, 0, 0};
+  if (!s || P < 1 || c < 1 || c > 128) return pl;
+  long long tiles = 0;
+  int max_mb = 0;
+  for (int i = 0; i < P; ++i) {
+    if (s[i].ma <= 0 || s[i].mb <= 0) return pl;
+    tiles += cdiv(s[i].ma, NN_TA);
+    if (s[i].mb > max_mb) max_mb = s[i].mb;
+    if (s[i].ma > pl.max_ma) pl.max_ma = s[i].ma;
+  }
+  pl.chunk = nn_chunk_rows_tiles(tiles, max_mb);
+  pl.max_tiles = (int)cdiv(pl.max_ma, NN_TA);
+  pl.max_pairs = (int)cdiv(max_mb, 2);
+  const int cp = (int)cdiv(c, 8) * 8;
+  const int cw = (c == 16 || c == 32) ? 64 : cp;                        // gcl_nn_rowmin sizes its copy for the widest rows
+  long long off = 0;
+  for (int i = 0; i < P; ++i) {
+    const long long n_chunks = cdiv(s[i].mb, pl.chunk);
+    if (n_chunks > pl.max_chunks) pl.max_chunks = (int)n_chunks;
+    if (bi_off) bi_off[i] = off;
+    off += nn_align64(nn_interleaved_words(s[i].mb, cw));
+    if (part_off) part_off[i] = off;
+    if (n_chunks > 1) off += nn_align64(2 * n_chunks * (long long)s[i].ma);
+  }
+  pl.words = off;
+  return pl;
+}
+
+int64_t gcl_nn_rowmin_batch_scratch_len(gcl_nn_search* searches_host, int32_t n_searches, int32_t c) {
+  if (!searches_host || n_searches < 1 || n_searches > 65535) return 0;
+  std::vector<long long> bi_off(n_searches), part_off(n_searches);
+  const NnBatchPlan pl = nn_batch_plan(searches_host, n_searches, c, bi_off.data(), part_off.data());
+  if (pl.words == 0) return 0;
+  for (int i = 0; i < n_searches; ++i) {
+    searches_host[i].bi_off = bi_off[i];
+    searches_host[i].part_off = part_off[i];
+  }
+  return pl.words;
+}
+
+int gcl_nn_rowmin_batch(const gcl_nn_search* searches_host, const gcl_nn_search* searches, int32_t n_searches, int32_t c,
+                        int32_t l2, int32_t* scratch, void* stream) {
+  GCL_CHECK_ARG(n_searches >= 1 && n_searches <= 65535, "gcl_nn_rowmin_batch: the number of searches must lie in 1 .. 65535 (got %d)",
+                n_searches);
+  GCL_CHECK_ARG(searches_host && searches, "gcl_nn_rowmin_batch: null pointer (the table on the host and its device copy)");
+  GCL_CHECK_ARG(c >= 1 && c <= 128, "gcl_nn_rowmin_batch: feature width must lie in 1 .. 128 (got %d)", c);
+  for (int i = 0; i < n_searches; ++i) {
+    const gcl_nn_search& s = searches_host[i];
+    GCL_CHECK_ARG(s.a && s.b && s.dmin && s.argmin, "gcl_nn_rowmin_batch: search %d: null pointer", i);
+    GCL_CHECK_ARG(s.ma > 0 && s.mb > 0, "gcl_nn_rowmin_batch: search %d: empty input (ma = %d, mb = %d)", i, s.ma, s.mb);
+    GCL_CHECK_ARG((s.pts_a != nullptr) == (s.pts_b != nullptr),
+                  "gcl_nn_rowmin_batch: search %d: pts_a and pts_b go together (the fused gather needs both, or neither)", i);
+    GCL_CHECK_ARG(!s.pts_a || (s.src && s.tgt), "gcl_nn_rowmin_batch: search %d: the gather needs src and tgt (null pointer)", i);
+  }
+  GCL_CHECK_ARG(scratch, "gcl_nn_rowmin_batch: scratch (int32[gcl_nn_rowmin_batch_scratch_len]) is required");
+  std::vector<long long> bi_off(n_searches), part_off(n_searches);
+  const NnBatchPlan pl = nn_batch_plan(searches_host, n_searches, c, bi_off.data(), part_off.data());
+  for (int i = 0; i < n_searches; ++i)
+    GCL_CHECK_ARG(searches_host[i].bi_off == bi_off[i] && searches_host[i].part_off == part_off[i],
+                  "gcl_nn_rowmin_batch: search %d: scratch offsets are not those of gcl_nn_rowmin_batch_scratch_len for this "
+                  "table (call it before copying the table to the device)", i);
+  hipStream_t st = (hipStream_t)stream;
+  const int cp = (int)cdiv(c, 8) * 8;
+  const unsigned P = (unsigned)n_searches;
+  hipLaunchKernelGGL(k_nn_interleave_batch, dim3((unsigned)cdiv(pl.max_pairs, 256 / cp), 1, P), dim3(256), 0, st, searches,
+                     c, cp, scratch);
+  dim3 grid((unsigned)pl.max_tiles, (unsigned)pl.max_chunks, P);
+#define LAUNCH_NN_BATCH(WW, ANY)                                                                                      \
+  hipLaunchKernelGGL((k_nn_rowmin_batch<WW, ANY>), grid, dim3(256), 0, st, searches, c, pl.chunk, l2, (const float*)scratch, scratch)
+#define CASE_NN_BATCH(WW) \
+  case WW:                \
+    LAUNCH_NN_BATCH(WW, true); \
+    break
+  if (c == 16) LAUNCH_NN_BATCH(16, false);
+  else if (c == 32) LAUNCH_NN_BATCH(32, false);
+  else if (c == 64) LAUNCH_NN_BATCH(64, false);
+  else
+    switch (cp) {
+      CASE_NN_BATCH(8);
+      CASE_NN_BATCH(16);
+      CASE_NN_BATCH(24);
+      CASE_NN_BATCH(32);
+      CASE_NN_BATCH(40);
+      CASE_NN_BATCH(48);
+      CASE_NN_BATCH(56);
+      CASE_NN_BATCH(64);
+      CASE_NN_BATCH(72);
+      CASE_NN_BATCH(80);
+      CASE_NN_BATCH(88);
+      CASE_NN_BATCH(96);
+      CASE_NN_BATCH(104);
+      CASE_NN_BATCH(112);
+      CASE_NN_BATCH(120);
+      CASE_NN_BATCH(128);
+    }
+#undef CASE_NN_BATCH
+#undef LAUNCH_NN_BATCH
+  if (pl.max_chunks > 1)
+    hipLaunchKernelGGL(k_nn_merge_batch, dim3((unsigned)cdiv(pl.max_ma, 256), 1, P), dim3(256), 0, st, searches, pl.chunk, l2,
+                       (const int32_t*)scratch);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -183,17 +183,19 @@ static int nn3_chunk_rows(int m, int n) {
 // is two dependent 4-byte reads per source, far too little to spread over the chip, and a scene enqueues one such launch
 // per pair of fragments behind two 1-NN searches that do fill it.  The inlier count (integers: any order gives the same
 // sum) is folded the same way.  Residuals are fp32: |kp0[i] - (R kp1[j] + t)| with the product as an FMA chain per row.
-__global__ void __launch_bounds__(1024) k_mutual_match(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10,
-                                                       int m1, const float* __restrict__ kp0, const float* __restrict__ kp1,
-                                                       const float* __restrict__ T, float tau, int* __restrict__ pairs,
-                                                       int* __restrict__ stats) {
+// (The body is a device function: k_mutual_match runs it in its one workgroup, k_mutual_match_batch in one workgroup per pair.)
+__device__ __forceinline__ void mutual_match_body(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10, int m1,
+                                                  const float* __restrict__ kp0, const float* __restrict__ kp1,
+                                                  const float* __restrict__ T, float tau, int* __restrict__ pairs,
+                                                  int* __restrict__ stats) {
   __shared__ int wcount[16], winl[16];
   __shared__ int base_s, inl_s;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   float Tm[12];
   if (T) {
 #pragma unroll
-    for (int e = 0; e < 12; ++e) Tm[e] = T[e];
+    for (int e = 0; e < 12; ++e)      // the same twelve values in every lane: kept in scalar registers
+      Tm[e] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T[e])));
   }
   if (t == 0) {
     base_s = 0;
@@ -247,6 +249,19 @@ __global__ void __launch_bounds__(1024) k_mutual_match(const int* __restrict__ n
   }
 }
 
+__global__ void __launch_bounds__(1024) k_mutual_match(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10,
+                                                       int m1, const float* __restrict__ kp0, const float* __restrict__ kp1,
+                                                       const float* __restrict__ T, float tau, int* __restrict__ pairs,
+                                                       int* __restrict__ stats) {
+  mutual_match_body(nn01, m0, nn10, m1, kp0, kp1, T, tau, pairs, stats);
+}
+
+// one workgroup per pair of the table: eight pairs fill eight CUs at once instead of one CU eight times in a row
+__global__ void __launch_bounds__(1024) k_mutual_match_batch(const gcl_mutual_job* __restrict__ jobs, float tau) {
+  const gcl_mutual_job* __restrict__ j = jobs + blockIdx.x;
+  mutual_match_body(j->nn01, j->m0, j->nn10, j->m1, j->xyz0, j->xyz1, j->T, tau, j->pairs, j->count);
+}
+
 // ---- k_mutual_corr ------------------------------------------------------------------------------------------------------
 // The correspondences a registration with open3d's mutual filter runs on, as point rows, with their number left on the
 // device.  ONE workgroup, as k_mutual_match and for its reasons, in two walks over the sources: the first counts the mutual
@@ -254,10 +269,10 @@ __global__ void __launch_bounds__(1024) k_mutual_match(const int* __restrict__ n
 // zero rows when there are at least min_count of them, else every source beside its nearest target (open3d: "too few
 // correspondences after mutual filter, fall back to original correspondences").  Which branch runs is uniform over the
 // workgroup.  A target index outside [0, m1) is never dereferenced: such a row of the fall-back has a zero target.
-__global__ void __launch_bounds__(1024) k_mutual_corr(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10, int m1,
-                                                      const float* __restrict__ xyz0, const float* __restrict__ xyz1,
-                                                      int min_count, float* __restrict__ src, float* __restrict__ tgt,
-                                                      int* __restrict__ count) {
+__device__ __forceinline__ void mutual_corr_body(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10, int m1,
+                                                 const float* __restrict__ xyz0, const float* __restrict__ xyz1,
+                                                 int min_count, float* __restrict__ src, float* __restrict__ tgt,
+                                                 int* __restrict__ count) {
   __shared__ int wcount[16];
   __shared__ int base_s;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -331,6 +346,18 @@ __global__ void __launch_bounds__(1024) k_mutual_corr(const int* __restrict__ nn
   }
 }
 
+__global__ void __launch_bounds__(1024) k_mutual_corr(const int* __restrict__ nn01, int m0, const int* __restrict__ nn10, int m1,
+                                                      const float* __restrict__ xyz0, const float* __restrict__ xyz1,
+                                                      int min_count, float* __restrict__ src, float* __restrict__ tgt,
+                                                      int* __restrict__ count) {
+  mutual_corr_body(nn01, m0, nn10, m1, xyz0, xyz1, min_count, src, tgt, count);
+}
+
+__global__ void __launch_bounds__(1024) k_mutual_corr_batch(const gcl_mutual_job* __restrict__ jobs, int min_count) {
+  const gcl_mutual_job* __restrict__ j = jobs + blockIdx.x;
+  mutual_corr_body(j->nn01, j->m0, j->nn10, j->m1, j->xyz0, j->xyz1, min_count, j->src, j->tgt, j->count);
+}
+
 }  // namespace gcl
 
 using namespace gcl;
@@ -390,6 +417,40 @@ int gcl_mutual_correspondences(const int32_t* nn01, int32_t m0, const int32_t* n
   GCL_CHECK_ARG(nn01 && nn10 && xyz0 && xyz1 && src && tgt && count, "gcl_mutual_correspondences: null pointer");
   hipLaunchKernelGGL(k_mutual_corr, dim3(1), dim3(1024), 0, (hipStream_t)stream, nn01, m0, nn10, m1, xyz0, xyz1, min_count,
                      src, tgt, count);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_mutual_match_batch(const gcl_mutual_job* jobs_host, const gcl_mutual_job* jobs, int32_t n_pairs, float tau,
+                           void* stream) {
+  GCL_CHECK_ARG(n_pairs >= 1, "gcl_mutual_match_batch: the number of pairs must be >= 1 (got %d)", n_pairs);
+  GCL_CHECK_ARG(jobs_host && jobs, "gcl_mutual_match_batch: null pointer (the table on the host and its device copy)");
+  for (int i = 0; i < n_pairs; ++i) {
+    const gcl_mutual_job& j = jobs_host[i];
+    GCL_CHECK_ARG(j.m0 >= 0 && j.m1 >= 0, "gcl_mutual_match_batch: pair %d: negative size (m0 = %d, m1 = %d)", i, j.m0, j.m1);
+    GCL_CHECK_ARG(j.count, "gcl_mutual_match_batch: pair %d: null pointer (count)", i);
+    GCL_CHECK_ARG(j.m0 == 0 || (j.nn01 && j.pairs), "gcl_mutual_match_batch: pair %d: null pointer (nn01, pairs)", i);
+    GCL_CHECK_ARG(j.m0 == 0 || j.m1 == 0 || j.nn10, "gcl_mutual_match_batch: pair %d: null pointer (nn10)", i);
+    GCL_CHECK_ARG(!j.T || (j.xyz0 && j.xyz1),
+                  "gcl_mutual_match_batch: pair %d: a transformation needs both keypoint arrays (null xyz0 / xyz1)", i);
+  }
+  hipLaunchKernelGGL(k_mutual_match_batch, dim3((unsigned)n_pairs), dim3(1024), 0, (hipStream_t)stream, jobs, tau);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_mutual_correspondences_batch(const gcl_mutual_job* jobs_host, const gcl_mutual_job* jobs, int32_t n_pairs,
+                                     int32_t min_count, void* stream) {
+  GCL_CHECK_ARG(n_pairs >= 1, "gcl_mutual_correspondences_batch: the number of pairs must be >= 1 (got %d)", n_pairs);
+  GCL_CHECK_ARG(jobs_host && jobs, "gcl_mutual_correspondences_batch: null pointer (the table on the host and its device copy)");
+  for (int i = 0; i < n_pairs; ++i) {
+    const gcl_mutual_job& j = jobs_host[i];
+    GCL_CHECK_ARG(j.m0 >= 1 && j.m1 >= 1, "gcl_mutual_correspondences_batch: pair %d: sizes must be >= 1 (m0 = %d, m1 = %d)", i,
+                  j.m0, j.m1);
+    GCL_CHECK_ARG(j.nn01 && j.nn10 && j.xyz0 && j.xyz1 && j.src && j.tgt && j.count,
+                  "gcl_mutual_correspondences_batch: pair %d: null pointer", i);
+  }
+  hipLaunchKernelGGL(k_mutual_corr_batch, dim3((unsigned)n_pairs), dim3(1024), 0, (hipStream_t)stream, jobs, min_count);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -12,6 +12,7 @@ No file formats are read here (PLY fragments, keypoint index files: dataset I/O,
 arrays.  Points and keypoints are searched in fp32 (the reference hands pytorch3d the float64 arrays of open3d); the
 distance is evaluated in the difference form, good to a few 2^-24 relative at any offset from the origin.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -20,7 +21,7 @@ import torch
 import gcl_amd.MinkowskiEngine as ME
 from gcl_amd import _lib
 from gcl_amd.lib.eval import host_to_device
-from gcl_amd.lib.metrics import nn3_min, pdist_min
+from gcl_amd.lib.metrics import mutual_jobs, nn3_min, pdist_min, pdist_min_batch
 
 DESC_WIDTHS = (16, 32, 64)      # what gcl_nn_rowmin searches
 
@@ -177,6 +178,47 @@ def match_fragments(kp_s, kp_t, desc_s, desc_t, gtTrans, tau1=0.1, out=None):
     return _mutual(nn01, nn10, kp_s, kp_t, _transform12(gtTrans, dev), tau1, out)
 
 
+def match_fragments_batch(jobs, tau1=0.1, outs=None):
+    """``match_fragments`` for a list of pairs ``(kp_s, kp_t, desc_s, desc_t, gtTrans)`` in a fixed number of launches: both
+    directions of every pair are the searches of ONE ``pdist_min_batch``, the mutual filters ONE ``gcl_mutual_match_batch``
+    (one workgroup per pair).  ``outs``: per pair the int32 [2] tensor that receives (mutual pairs, inliers) -- rows of a
+    scene's table.  Same refusals, and per pair the same ``FragmentMatch``, bit for bit."""
+    lib = _lib.require_gpu()
+    P = len(jobs)
+    if P < 1:
+        raise ValueError("match_fragments_batch needs at least one pair")
+    if outs is not None and len(outs) != P:
+        raise ValueError(f"{P} pairs but {len(outs)} outputs")
+    dev = jobs[0][2].device
+    checked = []
+    for kp_s, kp_t, desc_s, desc_t, gtTrans in jobs:
+        _check_width(desc_s.shape[1])
+        if desc_t.shape[1] != desc_s.shape[1]:
+            raise ValueError(f"descriptor widths differ: {desc_s.shape[1]} and {desc_t.shape[1]}")
+        kp_s, kp_t = _points(kp_s, dev), _points(kp_t, dev)
+        if kp_s.shape[0] != desc_s.shape[0] or kp_t.shape[0] != desc_t.shape[0]:
+            raise ValueError("match_fragments: one descriptor row per keypoint is required")
+        if desc_s.shape[0] == 0 or desc_t.shape[0] == 0:
+            raise ValueError("match_fragments: a fragment without keypoints")
+        checked.append((kp_s, kp_t, desc_s, desc_t, _transform12(gtTrans, dev)))
+    nn = pdist_min_batch([(j[2], j[3]) for j in checked] + [(j[3], j[2]) for j in checked], "SquareL2")
+    pairs = torch.empty((sum(j[2].shape[0] for j in checked), 2), dtype=torch.int32, device=dev)
+    stats = outs if outs is not None else list(torch.empty((P, 2), dtype=torch.int32, device=dev))
+    table, result, at = [], [], 0
+    for k, (kp_s, kp_t, desc_s, desc_t, T) in enumerate(checked):
+        if stats[k].dtype != torch.int32 or stats[k].numel() != 2:
+            raise ValueError("match_fragments: out must be an int32 tensor of two elements")
+        m0, m1 = desc_s.shape[0], desc_t.shape[0]
+        table.append(dict(nn01=nn[k][1], nn10=nn[P + k][1], xyz0=kp_s, xyz1=kp_t, T=T, pairs=pairs[at:at + m0], count=stats[k],
+                          m0=m0, m1=m1))
+        result.append(FragmentMatch(pairs[at:at + m0], stats[k], nn[k][1], nn[P + k][1]))
+        at += m0
+    recs, jobs_dev = mutual_jobs(table, dev)
+    _lib.check(lib.gcl_mutual_match_batch(ctypes.addressof(recs), _lib.ptr(jobs_dev), P, float(tau1), _lib.stream()),
+               "gcl_mutual_match_batch")
+    return result
+
+
 def scene_summary(table, tau2=0.05):
     """The reference's aggregation (:270-282) of a per-pair table [P, 3] = (num_inliers, inlier_ratio, gt_flag)."""
     result = np.asarray(table, dtype=np.float64).reshape(-1, 3)
@@ -189,14 +231,15 @@ def scene_summary(table, tau2=0.05):
 
 
 def evaluate_scene(fragments, keypoints, gt_log, model=None, descriptors=None, voxel_size=0.05, tau1=0.1, tau2=0.05,
-                   matcher=None):
+                   matcher=None, max_batch_bytes=1 << 30):
     """Feature-match recall of one scene (the loop of :258-284).
 
     ``fragments``: the clouds [N_i, 3] (unused when ``descriptors`` is given), ``keypoints``: [K_i, 3] per fragment,
     ``gt_log``: ``loadlog``'s dict.  Descriptors are computed ONCE per fragment (``fragment_descriptors``; the reference
     runs the network twice per pair) or taken from ``descriptors`` ([K_i, C] per fragment).  Every pair id1 < id2 named
-    by ``gt_log`` is enqueued with ``match_fragments`` into one int32 [P, 2] table, which is read ONCE; a pair the log does
-    not name counts (0, 0, gt_flag 0), as in the reference.
+    by ``gt_log`` is matched into one int32 [P, 2] table, which is read ONCE -- the pairs go in chunks whose search scratch
+    stays within ``max_batch_bytes``, each chunk ONE ``match_fragments_batch`` (a chunk of one pair: ``match_fragments``); a
+    pair the log does not name counts (0, 0, gt_flag 0), as in the reference.
 
     Returns ``recall`` (percent), ``correct_match``, ``gt_match``, ``ave_num_inliers`` and ``table`` float64 [P, 3] =
     (num_inliers, inlier_ratio, gt_flag) per pair in the loop's order, with the reference's arithmetic: the ratio goes
@@ -232,12 +275,27 @@ def evaluate_scene(fragments, keypoints, gt_log, model=None, descriptors=None, v
             T_host = np.stack([np.asarray(gt_log["%d_%d" % ids[p]], dtype=np.float64).reshape(-1)[:12] for p in gt_rows])
             T_all = host_to_device(np.ascontiguousarray(T_host, dtype=np.float32), dev)
         estimates = []
-        for g, p in enumerate(gt_rows):
-            a, b = ids[p]
-            match_fragments(kps[a], kps[b], descriptors[a], descriptors[b], T_all[g], tau1, out=counts[p])
+        lib, g0 = _lib.require_gpu(), 0
+        while g0 < len(gt_rows):                               # chunks of pairs under the scratch limit, at least one pair each
+            g1, need = g0, 0
+            while g1 < len(gt_rows):
+                m0, m1 = (int(descriptors[i].shape[0]) for i in ids[gt_rows[g1]])
+                need += 4 * (lib.gcl_nn_rowmin_scratch_len(m0, m1) + lib.gcl_nn_rowmin_scratch_len(m1, m0))
+                if g1 > g0 and need > int(max_batch_bytes):
+                    break
+                g1 += 1
+            chunk = [(g, gt_rows[g]) + ids[gt_rows[g]] for g in range(g0, g1)]
+            if len(chunk) == 1:
+                g, p, a, b = chunk[0]
+                match_fragments(kps[a], kps[b], descriptors[a], descriptors[b], T_all[g], tau1, out=counts[p])
+            else:
+                match_fragments_batch([(kps[a], kps[b], descriptors[a], descriptors[b], T_all[g]) for g, p, a, b in chunk], tau1,
+                                      outs=[counts[p] for g, p, a, b in chunk])
             if matcher is not None:
-                T_est = matcher.estimator(kps[a][None], kps[b][None], descriptors[a][None], descriptors[b][None])[0]
-                estimates.append(T_est[0])
+                for g, p, a, b in chunk:
+                    T_est = matcher.estimator(kps[a][None], kps[b][None], descriptors[a][None], descriptors[b][None])[0]
+                    estimates.append(T_est[0])
+            g0 = g1
         counts_host = counts.cpu().numpy()                     # the scene's ONE read of the match counts
         T_est_host = torch.stack(estimates).cpu().numpy().astype(np.float64) if estimates else None
     table = np.zeros((len(ids), 3), dtype=np.float64)

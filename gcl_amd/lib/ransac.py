@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from gcl_amd import _lib
-from gcl_amd.lib.metrics import pdist_min
+from gcl_amd.lib.metrics import mutual_jobs, pdist_min, pdist_min_batch
 
 
 class RegistrationResult:
@@ -167,6 +167,27 @@ def mutual_correspondences(xyz0, xyz1, F0, F1, min_count, src_out=None, tgt_out=
     return src, tgt, count
 
 
+def mutual_correspondences_batch(xyz0, xyz1, F0, F1, min_count, src_out=None, tgt_out=None, count_out=None):
+    """``mutual_correspondences`` for B pairs ([B, N0, ...] / [B, N1, ...] tensors) in a fixed number of launches: both
+    directions of every pair are the 2 B searches of ONE ``pdist_min_batch``, the filter is ONE
+    ``gcl_mutual_correspondences_batch`` (one workgroup per pair).  Returns ``(src [B, N0, 3], tgt [B, N0, 3], count int32
+    [B, 2])``, every pair's rows bitwise those of ``mutual_correspondences``."""
+    lib = _lib.require_gpu()
+    xyz0, xyz1 = xyz0.detach().to(torch.float32).contiguous(), xyz1.detach().to(torch.float32).contiguous()
+    B, m0, m1, dev = xyz0.shape[0], xyz0.shape[1], xyz1.shape[1], xyz0.device
+    src = torch.empty((B, m0, 3), dtype=torch.float32, device=dev) if src_out is None else src_out
+    tgt = torch.empty((B, m0, 3), dtype=torch.float32, device=dev) if tgt_out is None else tgt_out
+    count = torch.empty((B, 2), dtype=torch.int32, device=dev) if count_out is None else count_out
+    if tuple(src.shape) != (B, m0, 3) or tuple(tgt.shape) != (B, m0, 3) or tuple(count.shape) != (B, 2):
+        raise ValueError("mutual_correspondences_batch: outputs must be [B, N0, 3], [B, N0, 3] and [B, 2]")
+    nn = pdist_min_batch([(F0[b], F1[b]) for b in range(B)] + [(F1[b], F0[b]) for b in range(B)], "SquareL2")
+    recs, table = mutual_jobs([dict(nn01=nn[b][1], nn10=nn[B + b][1], xyz0=xyz0[b], xyz1=xyz1[b], src=src[b], tgt=tgt[b],
+                                    count=count[b], m0=m0, m1=m1) for b in range(B)], dev)
+    _lib.check(lib.gcl_mutual_correspondences_batch(ctypes.addressof(recs), _lib.ptr(table), B, int(min_count),
+                                                    _lib.stream()), "gcl_mutual_correspondences_batch")
+    return src, tgt, count
+
+
 def registration_ransac_based_on_mutual_feature_matching(xyz0, xyz1, F0, F1, max_correspondence_distance=0.3, ransac_n=4,
                                                          edge_length_similarity=0.9, checker_distance=None,
                                                          max_iteration=4000000, confidence=0.999, seed=None):
@@ -207,7 +228,8 @@ def registration_ransac_based_on_feature_matching(xyz0, xyz1, F0, F1, mutual_fil
 class FeatureRansac:
     """The RANSAC branch as a ``Matcher``: ``estimator`` has ``Matcher.estimator``'s contract for any batch size.  One pair
     without the mutual filter is one ``gcl_ransac_register`` call; a batch, or ``mutual_filter=True`` (open3d's default since
-    0.13; the reference passes False), is ONE ``gcl_ransac_register_batch`` call behind the pairs' 1-NN searches, and the
+    0.13; the reference passes False), is ONE ``gcl_ransac_register_batch`` call behind the pairs' 1-NN searches (a batch: one ``pdist_min_batch`` call that
+    writes the correspondences, with the filter one ``gcl_mutual_correspondences_batch``), and the
     returned tensors are [B, ...] with zero rows beyond a pair's correspondence count.
 
     NOTE on ``confidence``: the default everywhere here, ``kitti()`` and ``eth()`` included, is open3d's own default 0.999,
@@ -264,14 +286,15 @@ class FeatureRansac:
         src = torch.empty((B, src_keypts.shape[1], 3), dtype=torch.float32, device=dev)
         tgt = torch.empty_like(src)
         cnt = torch.empty((B, 2), dtype=torch.int32, device=dev) if self.mutual_filter else None
-        for b in range(B):
-            if self.mutual_filter:
-                mutual_correspondences(src_keypts[b], tgt_keypts[b], src_features[b], tgt_features[b], self.ransac_n, src[b],
-                                       tgt[b], cnt[b])
-            else:
-                _, arg = pdist_min(src_features[b], tgt_features[b], "SquareL2")
-                src[b] = src_keypts[b]
-                tgt[b] = tgt_keypts[b].to(torch.float32)[arg.long()]
+        if B == 1:                                                           # one pair keeps the single entries
+            mutual_correspondences(src_keypts[0], tgt_keypts[0], src_features[0], tgt_features[0], self.ransac_n, src[0], tgt[0],
+                                   cnt[0])
+        elif self.mutual_filter:
+            mutual_correspondences_batch(src_keypts, tgt_keypts, src_features, tgt_features, self.ransac_n, src, tgt, cnt)
+        else:                                                                # the B searches and their gathers in one call
+            kp0, kp1 = src_keypts.to(torch.float32).contiguous(), tgt_keypts.to(torch.float32).contiguous()
+            pdist_min_batch([(src_features[b], tgt_features[b], None, None, kp0[b], kp1[b], src[b], tgt[b]) for b in range(B)],
+                            "SquareL2")
         if seeds is None:
             seeds = [self.draw_seed() for _ in range(B)]
         res = ransac_correspondences_batch(src, tgt, self.max_correspondence_distance, self.ransac_n,

@@ -8,7 +8,7 @@ import torch
 
 from gcl_amd import _lib
 from gcl_amd.lib.eval import host_to_device
-from gcl_amd.lib.metrics import pdist_min
+from gcl_amd.lib.metrics import pdist_min, pdist_min_batch
 
 STAT_COLUMNS = ("loss", "rte", "rre", "hit_ratio", "n_corr", "status")
 
@@ -85,8 +85,9 @@ def _f32(x):
 def validate_pairs(model, val_batches, val_max_iter=-1, batch_pairs=8, subsample_size=5000, hit_ratio_thresh=0.3,
                    nn_max_n=500):
     """The validation loop over ``val_batches`` (pair dicts of ``collate_debug_pair_fn``: sinput{0,1}_C / _F, pcd0 / pcd1,
-    T_gt), ``batch_pairs`` pairs at a time: one forward pass for the chunk's clouds, per pair the two draws and the feature
-    1-NN (enqueued; the indices stay on the device), then ONE pose call and ONE statistics call for the chunk and one
+    T_gt), ``batch_pairs`` pairs at a time: one forward pass for the chunk's clouds, per pair the two draws (in the
+    reference's order), the chunk's feature 1-NN searches as ONE call that writes the correspondences at their offsets (a
+    chunk of one pair: ``pdist_min`` and the gathers), then ONE pose call and ONE statistics call for the chunk and one
     pinned [B, 6] copy, which is read while the next chunk runs.  ``nn_max_n`` is the reference's chunk size against a
     temporary that does not exist here.
 
@@ -113,24 +114,36 @@ def validate_pairs(model, val_batches, val_max_iter=-1, batch_pairs=8, subsample
                                            for d in chunk for k in (0, 1)])
             src, tgt, first, off, off0 = [], [], [], [0], [0]
             gts = np.empty((B, 16), dtype=np.float64)
+            searches = []                                                          # B > 1: the chunk's searches, one call below
             for j, d in enumerate(chunk):
                 F0, F1 = feats[2 * j], feats[2 * j + 1]
                 xyz0, xyz1 = host_to_device(_f32(d["pcd0"][0]), dev), host_to_device(_f32(d["pcd1"][0]), dev)
                 gts[j] = _f32(d["T_gt"]).reshape(16).double().cpu().numpy()          # the reference's T_gt is float32
                 inds0, inds1 = draw_subsample(len(F0), len(F1), subsample_size)
-                if inds0 is None:
-                    _, arg = pdist_min(F0, F1, "SquareL2")
-                    a, b = xyz0, xyz1[arg.long()]
+                i0, i1 = (None, None) if inds0 is None else (host_to_device(inds0, dev), host_to_device(inds1, dev))
+                if B > 1:
+                    searches.append((F0, F1, i0, i1, xyz0, xyz1))
+                    n = len(F0) if i0 is None else len(i0)
                 else:
-                    i0, i1 = host_to_device(inds0, dev), host_to_device(inds1, dev)
-                    _, arg = pdist_min(F0[i0], F1[i1], "SquareL2")
-                    a, b = xyz0[i0], xyz1[i1[arg.long()]]
-                src.append(a)
-                tgt.append(b)
+                    if i0 is None:
+                        _, arg = pdist_min(F0, F1, "SquareL2")
+                        a, b = xyz0, xyz1[arg.long()]
+                    else:
+                        _, arg = pdist_min(F0[i0], F1[i1], "SquareL2")
+                        a, b = xyz0[i0], xyz1[i1[arg.long()]]
+                    src.append(a)
+                    tgt.append(b)
+                    n = len(a)
                 first.append(xyz0)
-                off.append(off[-1] + len(a))
+                off.append(off[-1] + n)
                 off0.append(off0[-1] + len(xyz0))
-            src, tgt, first = (torch.cat(x) if B > 1 else x[0] for x in (src, tgt, first))
+            if B > 1:                         # the searches write their correspondences at the offsets `off` themselves
+                src = torch.empty((off[-1], 3), dtype=torch.float32, device=dev)
+                tgt = torch.empty_like(src)
+                pdist_min_batch([s + (src[off[j]:off[j + 1]], tgt[off[j]:off[j + 1]]) for j, s in enumerate(searches)], "SquareL2")
+                first = torch.cat(first)
+            else:
+                src, tgt, first = src[0], tgt[0], first[0]
             off_d = host_to_device(np.asarray(off, dtype=np.int64), dev)
             off0_d = host_to_device(np.asarray(off0, dtype=np.int64), dev)
             T_est, status = est_quad_linear_robust_batch(src, tgt, off_d)

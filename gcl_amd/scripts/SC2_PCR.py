@@ -16,7 +16,7 @@ import torch
 
 from gcl_amd import _lib
 from gcl_amd.lib.eval import host_to_device
-from gcl_amd.lib.metrics import pdist_min
+from gcl_amd.lib.metrics import pdist_min, pdist_min_batch
 
 import os
 
@@ -293,8 +293,58 @@ class BatchMatcher(Matcher):
         self._labels = labels
         return out.view(B, 4, 4)
 
+    def _match_into(self, pairs, seeds, src_corr, tgt_corr):
+        """``Matcher.match_pair`` for every ``(src_keypts, tgt_keypts, src_features, tgt_features)`` of ``pairs`` ([n, ...]
+        tensors, ragged) under the draws ``seeds`` in ONE ``pdist_min_batch`` call: pair b's correspondences go to the first
+        rows of ``src_corr[b]`` / ``tgt_corr[b]`` ([B, n_cap, 3]; rows beyond its count are left alone), written by the search
+        itself when the points are float32, else by indexing with its arg-minima.  One copy brings all the draws over."""
+        dev = src_corr.device
+        drawn = [np.asarray(r, dtype=np.int64) for sel in seeds if sel is not None for r in sel]
+        rows, at = (host_to_device(np.concatenate(drawn), dev), 0) if drawn else (None, 0)
+        fused = all(p[0].dtype == torch.float32 and p[1].dtype == torch.float32 for p in pairs) and \
+            src_corr.dtype == torch.float32 and tgt_corr.dtype == torch.float32
+        problems, sels = [], []
+        for b, ((sk, tk, sf, tf), sel) in enumerate(zip(pairs, seeds)):
+            src_sel = tgt_sel = None
+            if sel is not None:
+                src_sel, tgt_sel = rows[at:at + len(sel[0])], rows[at + len(sel[0]):at + len(sel[0]) + len(sel[1])]
+                at += len(sel[0]) + len(sel[1])
+            n = sf.shape[0] if src_sel is None else src_sel.shape[0]
+            sels.append((src_sel, tgt_sel, n))
+            problems.append((sf, tf, src_sel, tgt_sel, sk, tk, src_corr[b, :n], tgt_corr[b, :n]) if fused
+                            else (sf, tf, src_sel, tgt_sel))
+        out = pdist_min_batch(problems, "SquareL2")
+        if not fused:
+            for b, ((sk, tk, _, _), (src_sel, tgt_sel, n)) in enumerate(zip(pairs, sels)):
+                arg = out[b][1].long()
+                src_corr[b, :n] = sk if src_sel is None else sk[src_sel]
+                tgt_corr[b, :n] = tk[tgt_sel[arg] if tgt_sel is not None else arg]
+        return [n for _, _, n in sels]
+
+    def match_pairs(self, pairs, seeds=None):
+        """``Matcher.match_pair`` for a list of RAGGED pairs ``(src_keypts, tgt_keypts, src_features, tgt_features)`` ([n, ...]
+        or [1, n, ...] tensors) in one native call.  Returns ``(src [B, n_cap, 3], tgt [B, n_cap, 3], counts)`` (float32; a
+        pair's rows beyond its count are never written): what ``SC2_PCR(src, tgt, counts=counts)`` takes.  The draws of an
+        integer ``num_node`` are made first, in pair order -- the stream of B ``match_pair`` calls in a row -- unless ``seeds``
+        (per pair what ``draw_seed`` returned) gives them."""
+        pairs = [tuple(x[0] if x.dim() == 3 else x for x in p) for p in pairs]
+        if len(pairs) < 1:
+            raise ValueError("match_pairs needs at least one pair")
+        if seeds is None:
+            seeds = [self.draw_seed(sf.shape[0], tf.shape[0]) for _, _, sf, tf in pairs]
+        if len(seeds) != len(pairs):
+            raise ValueError(f"{len(pairs)} pairs but {len(seeds)} seeds")
+        counts = [sf.shape[0] if sel is None else len(sel[0]) for (_, _, sf, _), sel in zip(pairs, seeds)]
+        dev = pairs[0][2].device
+        pairs = [(sk.to(torch.float32), tk.to(torch.float32), sf, tf) for sk, tk, sf, tf in pairs]
+        src = torch.empty((len(pairs), max(counts), 3), dtype=torch.float32, device=dev)
+        tgt = torch.empty_like(src)
+        self._match_into(pairs, seeds, src, tgt)
+        return src, tgt, counts
+
     def estimator(self, src_keypts, tgt_keypts, src_features, tgt_features, seeds=None):
-        """``Matcher.estimator`` on [B, N, ...] tensors: one feature 1-NN per pair, ONE registration call.  ``seeds``: per
+        """``Matcher.estimator`` on [B, N, ...] tensors: the pairs' feature 1-NN searches as ONE call that writes the
+        correspondences (one pair: ``Matcher.match_pair``'s calls), ONE registration call.  ``seeds``: per
         pair what ``draw_seed`` returned, for a caller that made the draws already (in its own order of host draws); None:
         drawn here, in pair order -- the draws of B ``Matcher.estimator`` calls in a row."""
         B = src_keypts.shape[0]
@@ -308,13 +358,16 @@ class BatchMatcher(Matcher):
         dev = src_features.device
         src_corr = torch.empty((B, n, 3), dtype=src_keypts.dtype, device=dev)
         tgt_corr = torch.empty((B, n, 3), dtype=tgt_keypts.dtype, device=dev)
-        for b in range(B):                                                       # Matcher.match_pair with the given draws
-            sel = seeds[b]
+        if B == 1:                                                               # Matcher.match_pair with the given draws
+            sel = seeds[0]
             src_sel, tgt_sel = (None, None) if sel is None else (host_to_device(sel[0], dev), host_to_device(sel[1], dev))
-            _, arg = pdist_min(src_features[b], tgt_features[b], "SquareL2", rows_a=src_sel, rows_b=tgt_sel)
+            _, arg = pdist_min(src_features[0], tgt_features[0], "SquareL2", rows_a=src_sel, rows_b=tgt_sel)
             arg = arg.long()
-            src_corr[b] = src_keypts[b] if src_sel is None else src_keypts[b, src_sel]
-            tgt_corr[b] = tgt_keypts[b, tgt_sel[arg] if tgt_sel is not None else arg]
+            src_corr[0] = src_keypts[0] if src_sel is None else src_keypts[0, src_sel]
+            tgt_corr[0] = tgt_keypts[0, tgt_sel[arg] if tgt_sel is not None else arg]
+        else:                                                                    # the B searches and their gathers: one call
+            self._match_into([(src_keypts[b], tgt_keypts[b], src_features[b], tgt_features[b]) for b in range(B)], seeds,
+                             src_corr, tgt_corr)
         pred_trans = self.SC2_PCR(src_corr, tgt_corr)
         if n <= self.max_points:                                                 # made by the registration call itself
             return pred_trans, self._labels, src_corr, tgt_corr

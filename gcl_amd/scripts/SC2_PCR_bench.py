@@ -129,31 +129,33 @@ def eval_per_pair(records, matcher, config, batch_pairs=8, scene_ind=-1, device=
         for kind, idx in chunks:
             B = len(idx)
             t_data, t_model, held, gts = [], [], [], np.empty((B, 4, 4), dtype=np.float32)
+            one_call = kind is not None and kind != "fail" and B > 1                # the chunk's matching as one native call
             for j, i in enumerate(idx):
                 t0 = time.perf_counter()
                 sk, tk, sf, tf, gt = records[i]
                 sk, tk, sf, tf = (_dev(x, dev)[None] for x in (sk, tk, sf, tf))
                 gts[j] = gt.detach().cpu().numpy().reshape(4, 4) if torch.is_tensor(gt) else np.asarray(gt).reshape(4, 4)
                 t1 = time.perf_counter()
-                held.append(matcher.match_pair(sk, tk, sf, tf))                    # [1, n, 3] each; draws in pair order
+                held.append((sk, tk, sf, tf) if one_call else matcher.match_pair(sk, tk, sf, tf))      # draws in pair order
                 t_data.append(t1 - t0)
                 t_model.append(time.perf_counter() - t1)
             t0 = time.perf_counter()
-            n = [h[0].shape[1] for h in held]
-            if kind is None or kind == "fail":                                      # one pair, its own extent
+            if one_call:
+                src, tgt, n = matcher.match_pairs(held)                             # rows from a count on are never read
+                pred = matcher.SC2_PCR(src, tgt, counts=n)
+                cnt = None if min(n) == max(n) else n
+            elif kind is None or kind == "fail":                                    # one pair, its own extent
+                n = [held[0][0].shape[1]]
                 src, tgt, cnt = held[0][0].to(torch.float32), held[0][1].to(torch.float32), None
                 if kind is None and int(min(n[0], matcher.max_points) * matcher.ratio) >= 1:
                     pred = matcher.SC2_PCR(src, tgt).reshape(1, 4, 4)
                 else:
                     pred = host_to_device(eye[None].copy(), dev)                    # no seed: identity (module docstring)
-            else:
-                n_cap = max(n)
-                src = torch.empty((B, n_cap, 3), dtype=torch.float32, device=dev)  # rows from a count on are never read
-                tgt = torch.empty((B, n_cap, 3), dtype=torch.float32, device=dev)
-                for j, (s, t) in enumerate(held):
-                    src[j, :n[j]], tgt[j, :n[j]] = s[0], t[0]
+            else:                                                                   # a chunk of one pair
+                n = [held[0][0].shape[1]]
+                src, tgt = held[0][0].to(torch.float32).contiguous(), held[0][1].to(torch.float32).contiguous()
                 pred = matcher.SC2_PCR(src, tgt, counts=n)
-                cnt = None if min(n) == n_cap else n
+                cnt = None
             dt = (time.perf_counter() - t0) / B
             st = registration_stats(src, tgt, cnt, pred, host_to_device(gts, dev), thr, re_thre, te_thre)
             host = torch.empty((B, 10), dtype=torch.float64, pin_memory=True)

@@ -26,10 +26,13 @@
  *                                                    generalization_ETH/evaluate.py:171-186
  *        -> gcl_nn_rowmin, gcl_ransac_register, gcl_ransac_register_batch, gcl_mutual_correspondences
  *   find_nearest_voxel_feature, calculate_M, inlier ratio   generalization_ETH/evaluate.py:63-77, :110-122, :160-169
- *        -> gcl_nn3_rowmin, gcl_nn_rowmin, gcl_mutual_match
+ *        -> gcl_nn3_rowmin, gcl_nn_rowmin, gcl_mutual_match; a scene's logged pairs in chunks: gcl_nn_rowmin_batch,
+ *           gcl_mutual_match_batch
  *   eval_KITTI_per_pair, eval_3DMatch_scene (SC2-PCR benchmark)   scripts/SC2_PCR/test_KITTI.py:18-85,
  *                                                    test_3DMatch.py:18-76, evaluate_metric.py
- *        -> gcl_nn_rowmin / gcl_nn_rowmin_any (any descriptor width), gcl_sc2_register_batch, gcl_registration_stats
+ *        -> gcl_nn_rowmin / gcl_nn_rowmin_any (any descriptor width), gcl_sc2_register_batch, gcl_registration_stats;
+ *           a chunk's searches and correspondence gathers in one call: gcl_nn_rowmin_batch (with the mutual filter:
+ *           gcl_mutual_correspondences_batch)
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless its name ends in _host;
@@ -613,6 +616,39 @@ int gcl_nn_rowmin(const float* a, const int64_t* rows_a, int32_t ma, const float
 int64_t gcl_nn_rowmin_any_scratch_len(int32_t ma, int32_t mb, int32_t c);
 int gcl_nn_rowmin_any(const float* a, const int64_t* rows_a, int32_t ma, const float* b, const int64_t* rows_b,
                       int32_t mb, int32_t c, int32_t l2, int32_t* scratch, float* dmin, int32_t* argmin, void* stream);
+/* A BATCH of such searches in the launches of one: one interleave launch, one search launch with the search as the grid's
+ * z dimension, and one merge launch when some search runs in more than one chunk -- whatever n_searches is.  Widths 16 /
+ * 32 / 64 run the chain of gcl_nn_rowmin, every other width in 1 .. 128 that of gcl_nn_rowmin_any (the same device
+ * functions), and the minimum is exact with ties to the lowest index under any chunking: dmin / argmin of a search are bit
+ * for bit those of the single entry, alone, at any position of any batch, on every run.  Ragged: every search has its own
+ * ma / mb / row lists; searches may share a, b or both (the two directions of a pair).  c and l2 are per call.
+ * Optional fused gather, per search: with pts_a and pts_b (float [*, 3]; both or neither) the kernel that writes argmin[r]
+ * also writes  src[r] = pts_a[rows_a ? rows_a[r] : r]  and  tgt[r] = pts_b[rows_b ? rows_b[argmin[r]] : argmin[r]]
+ * (float [ma, 3] each; they may be slices of a batch's padded correspondence buffers).
+ * The table is passed TWICE: searches_host, from which the entry validates and sizes grids and chunks, and searches (a
+ * device copy of the same bytes) for the kernels; the entry allocates, copies and synchronises nothing.
+ * gcl_nn_rowmin_batch_scratch_len FILLS bi_off / part_off of every record (offsets into scratch, in 32-bit words) and
+ * returns the scratch length in words: call it on the host table before copying the table to the device.  It returns 0
+ * for n_searches < 1, c outside 1 .. 128 or an empty search.  Per search: the interleaved copy of B (cdiv(mb, 2) * 2 * cp
+ * words, cp = c rounded up to 8; 64 for c = 16 / 32 as the single entry sizes it) plus, when it runs in several chunks,
+ * 2 * n_chunks * ma words; the chunk size aims at ~1536 workgroups for the whole batch. */
+typedef struct gcl_nn_search {
+  const float* a;             /* float [*, c] */
+  const int64_t* rows_a;      /* int64 [ma] or NULL = rows 0 .. ma - 1 */
+  const float* b;
+  const int64_t* rows_b;      /* int64 [mb] or NULL */
+  float* dmin;                /* float [ma] */
+  int32_t* argmin;            /* int32 [ma] */
+  const float* pts_a;         /* optional gather (both or neither) */
+  const float* pts_b;
+  float* src;                 /* float [ma, 3], required with pts_a / pts_b */
+  float* tgt;
+  int64_t bi_off, part_off;   /* filled by gcl_nn_rowmin_batch_scratch_len */
+  int32_t ma, mb;
+} gcl_nn_search;
+int64_t gcl_nn_rowmin_batch_scratch_len(gcl_nn_search* searches_host, int32_t n_searches, int32_t c);
+int gcl_nn_rowmin_batch(const gcl_nn_search* searches_host, const gcl_nn_search* searches, int32_t n_searches, int32_t c,
+                        int32_t l2, int32_t* scratch, void* stream);
 
 /* 3-D nearest point (generalization_ETH/evaluate.py:110-122, find_nearest_voxel_feature): for every query q[i]
  * (float [m, 3]) the row j of p (float [n, 3]) that minimises (qx - px)^2 + (qy - py)^2 + (qz - pz)^2, evaluated in that
@@ -646,6 +682,28 @@ int gcl_mutual_match(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32
  * slices of a batch's buffers: nothing is read back.  Ordered compaction by one workgroup: the same list on every run. */
 int gcl_mutual_correspondences(const int32_t* nn01, int32_t m0, const int32_t* nn10, int32_t m1, const float* xyz0,
                                const float* xyz1, int32_t min_count, float* src, float* tgt, int32_t* count, void* stream);
+/* Both filters for a BATCH of pairs in one launch, one workgroup per pair (the single entries run one workgroup and leave
+ * the other CUs idle: eight pairs are eight such launches in a row).  The kernel bodies are those of the single entries, so
+ * a pair's outputs are bit for bit theirs.  jobs_host / jobs: the table on the host (validated) and its device copy (read
+ * by the kernel).  gcl_mutual_match_batch reads nn01, m0, nn10, m1, xyz0 (= kp0), xyz1 (= kp1), T and writes pairs and
+ * count (= stats); gcl_mutual_correspondences_batch reads nn01, m0, nn10, m1, xyz0, xyz1 and writes src, tgt, count.  tau
+ * and min_count are per call. */
+typedef struct gcl_mutual_job {
+  const int32_t* nn01;
+  const int32_t* nn10;
+  const float* xyz0;
+  const float* xyz1;
+  const float* T;             /* float [12] or NULL (gcl_mutual_match_batch) */
+  int32_t* pairs;             /* int32 [m0, 2] (gcl_mutual_match_batch) */
+  float* src;                 /* float [m0, 3] (gcl_mutual_correspondences_batch) */
+  float* tgt;
+  int32_t* count;             /* int32 [2]: stats / count of the single entries */
+  int32_t m0, m1;
+} gcl_mutual_job;
+int gcl_mutual_match_batch(const gcl_mutual_job* jobs_host, const gcl_mutual_job* jobs, int32_t n_pairs, float tau,
+                           void* stream);
+int gcl_mutual_correspondences_batch(const gcl_mutual_job* jobs_host, const gcl_mutual_job* jobs, int32_t n_pairs,
+                                     int32_t min_count, void* stream);
 
 /* keep[r] = (sel1[r] != sel2[arg[r]]) && the pair {sel1[r], sel2[arg[r]]} shares no positive group
  * (equivalent to the reference's `~np.isin(_neg_hash(...), index_hash)` :521-529: the symmetric key is
