@@ -132,6 +132,8 @@ SIGNATURES = {
     "gcl_bn_apply_planes": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "gcl_bn_bwd_reduce_range": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gcl_bn_bwd_apply_planes": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gcl_bn_bwd_reduce_rows": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gcl_bn_bwd_apply_rows": (_i32, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcl_bn_stats_from_tiles": (_i32, [_vp, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gcl_bn_apply": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "gcl_bn_apply_ld": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
@@ -164,6 +166,8 @@ SIGNATURES = {
     "gcl_plan_suffix_fwd_rows_used": (_i64, [_vp]),
     "gcl_gather_rows": (_i32, [_vp, _i32, _i64, _vp, _i64, _i32, _f32, _vp, _vp]),
     "gcl_scatter_rows": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp]),
+    "gcl_scatter_add_rows": (_i32, [_vp, _i32, _vp, _i64, _i32, _i64, _vp, _i32, _vp]),
+    "gcl_row_slots": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "gcl_touched_rows_scratch_len": (_i64, [_i64]),
     "gcl_touched_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
     "gcl_stream_create_cu_share": (_i32, [_i32, _i32, ctypes.POINTER(ctypes.c_void_p)]),

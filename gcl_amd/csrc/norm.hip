@@ -27,6 +27,54 @@ __device__ __forceinline__ float4 mask_as_y(const unsigned long long* __restrict
                      (float)((m[3] >> b) & 1));
 }
 
+__device__ __forceinline__ void relu_gate(float4& g, const float4& yv) {
+  g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
+  g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
+}
+
+// end of a statistics kernel: the thread sums s0 / s1 (and, gmax, the thread maxima gm) of a workgroup -> its entry of the
+// channel-major partials [2 or 3][c][gridDim.x] (a channel's run is contiguous for reduce_runs), the row lanes of a
+// channel quad added in order.  gmax is uniform over the workgroup.
+__device__ __forceinline__ void bn_reduce_partials(double (&red)[2][256][4], const double (&s0)[4], const double (&s1)[4],
+                                                   const float (&gm)[4], int c, bool gmax, double* partial) {
+  const int cq_n = c >> 2;
+  const int cq = threadIdx.x % cq_n, rl = threadIdx.x / cq_n, rstep = 256 / cq_n;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    red[0][threadIdx.x][j] = s0[j];
+    red[1][threadIdx.x][j] = s1[j];
+  }
+  __syncthreads();
+  if (rl == 0) {
+    const long long nwg = gridDim.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double a = 0, b = 0;
+      for (int q = 0; q < rstep; ++q) {
+        a += red[0][q * cq_n + cq][j];
+        b += red[1][q * cq_n + cq][j];
+      }
+      partial[(long long)(cq * 4 + j) * nwg + blockIdx.x] = a;
+      partial[(long long)(c + cq * 4 + j) * nwg + blockIdx.x] = b;
+    }
+  }
+  if (gmax) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[0][threadIdx.x][j] = (double)gm[j];
+    __syncthreads();
+    if (rl == 0) {
+      const long long nwg = gridDim.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        double a = 0;
+        for (int q = 0; q < rstep; ++q) a = fmax(a, red[0][q * cq_n + cq][j]);
+        partial[(long long)(2 * c + cq * 4 + j) * nwg + blockIdx.x] = a;
+      }
+    }
+  }
+}
+
 // thread t -> channel quad cq = t % (c/4), row lane rl = t / (c/4)
 template <bool BWD>
 __global__ void __launch_bounds__(256) k_bn_reduce(const float* __restrict__ x, const float* __restrict__ dy,
@@ -99,40 +147,52 @@ __global__ void __launch_bounds__(256) k_bn_reduce(const float* __restrict__ x, 
     BN_ACC(xa, ga, ya)
   }
 #undef BN_ACC
+  bn_reduce_partials(red, s0, s1, gm, c, BWD && want_gmax, partial);
+}
+
+// k_bn_reduce<true> with the gradient supplied sparsely: g is the compact [cap, c] gradient (row pitch g_ld floats, 0 = c) of
+// the rows of a list, slots[n] a row's position in it (-1 off the list: that row of the dense gradient is zero and would add
+// nothing).  The grid, the rows of a workgroup and the rows of a thread are the dense kernel's, walked in the same ascending
+// order, so the partials -- and everything k_bn_bwd_final makes of them -- are the dense pass's without its exact-zero
+// terms: bit for bit.  A thread reads the slots of its rows four at a time (independent loads), and x, g and the ReLU's sign
+// bits (mask) at the listed rows only.
+__global__ void __launch_bounds__(256) k_bn_reduce_rows(const float* __restrict__ x, const float* __restrict__ g,
+                                                        const int* __restrict__ slots, long long n, int c,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const unsigned long long* __restrict__ mask, int rows_per_wg,
+                                                        double* partial, int g_ld, int want_gmax) {
+  const long long gld = g_ld ? g_ld : c;
+  __shared__ double red[2][256][4];
+  const int cq_n = c >> 2;
+  const int cq = threadIdx.x % cq_n, rl = threadIdx.x / cq_n, rstep = 256 / cq_n;
+  const long long r_begin = (long long)blockIdx.x * rows_per_wg;
+  long long r_end = r_begin + rows_per_wg;
+  if (r_end > n) r_end = n;
+  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+  float gm[4] = {0.f, 0.f, 0.f, 0.f};
+  const float4 mu = reinterpret_cast<const float4*>(mean)[cq], rs = reinterpret_cast<const float4*>(rstd)[cq];
+  for (long long r0 = r_begin + rl; r0 < r_end; r0 += 4 * rstep) {
+    int slot[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    red[0][threadIdx.x][j] = s0[j];
-    red[1][threadIdx.x][j] = s1[j];
-  }
-  __syncthreads();
-  if (rl == 0) {      // channel-major partials [2][c][gridDim.x]: a channel's run is contiguous for reduce_runs
-    const long long nwg = gridDim.x;
+    for (int u = 0; u < 4; ++u) {
+      const long long r = r0 + (long long)u * rstep;
+      slot[u] = r < r_end ? slots[r] : -1;
+    }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double a = 0, b = 0;
-      for (int q = 0; q < rstep; ++q) {
-        a += red[0][q * cq_n + cq][j];
-        b += red[1][q * cq_n + cq][j];
-      }
-      partial[(long long)(cq * 4 + j) * nwg + blockIdx.x] = a;
-      partial[(long long)(c + cq * 4 + j) * nwg + blockIdx.x] = b;
+    for (int u = 0; u < 4; ++u) {
+      if (slot[u] < 0) continue;
+      const long long r = r0 + (long long)u * rstep;
+      const float4 xv = reinterpret_cast<const float4*>(x + r * c)[cq];
+      float4 gv = reinterpret_cast<const float4*>(g + (long long)slot[u] * gld)[cq];
+      if (mask) relu_gate(gv, mask_as_y(mask, r * cq_n + cq));
+      s0[0] += gv.x; s0[1] += gv.y; s0[2] += gv.z; s0[3] += gv.w;
+      gm[0] = fmaxf(gm[0], fabsf(gv.x)); gm[1] = fmaxf(gm[1], fabsf(gv.y));
+      gm[2] = fmaxf(gm[2], fabsf(gv.z)); gm[3] = fmaxf(gm[3], fabsf(gv.w));
+      s1[0] += (double)gv.x * ((xv.x - mu.x) * rs.x); s1[1] += (double)gv.y * ((xv.y - mu.y) * rs.y);
+      s1[2] += (double)gv.z * ((xv.z - mu.z) * rs.z); s1[3] += (double)gv.w * ((xv.w - mu.w) * rs.w);
     }
   }
-  if (BWD && want_gmax) {      // uniform over the workgroup
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[0][threadIdx.x][j] = (double)gm[j];
-    __syncthreads();
-    if (rl == 0) {
-      const long long nwg = gridDim.x;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        double a = 0;
-        for (int q = 0; q < rstep; ++q) a = fmax(a, red[0][q * cq_n + cq][j]);
-        partial[(long long)(2 * c + cq * 4 + j) * nwg + blockIdx.x] = a;
-      }
-    }
-  }
+  bn_reduce_partials(red, s0, s1, gm, c, want_gmax != 0, partial);
 }
 
 // ordered (deterministic) sum of ONE channel's two runs of per-workgroup partials (channel-major layout) by a 256-thread
@@ -452,12 +512,12 @@ __device__ __forceinline__ float4 bn_bwd_one(const float4& xv, const float4& g, 
   o.w = k.wv.w * k.rs.w * (g.w - k.sg.w * inv_n - (xv.w - k.mu.w) * k.rs.w * k.sx.w * inv_n);
   return o;
 }
-__device__ __forceinline__ void relu_gate(float4& g, const float4& yv) {
-  g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
-  g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
-}
 
-template <bool HOIST>
+// ROWS: dy is supplied sparsely -- the compact [cap, c] gradient (row pitch dy_ld floats, 0 = c) of the rows of a list, every
+// other row of the dense gradient being zero.  slots[n]: a row's position in the list, -1 for a row that is not on it.  The
+// kernel still walks all n rows (dx is non-zero everywhere); a wave none of whose rows is listed issues no load of dy.
+// dres is then compact too, [cap, c]: the gated gradient of the listed rows (it is zero in every other row).
+template <bool HOIST, bool ROWS>
 __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ x, const float* __restrict__ dy,
                                                       const float* __restrict__ y, long long total4, int c,
                                                       float inv_n, const float* __restrict__ mean,
@@ -469,7 +529,8 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
                                                       float* __restrict__ dx, float* __restrict__ dres,
                                                       int* amax_bits, int dy_ld = 0,
                                                       unsigned short* __restrict__ planes = nullptr,
-                                                      const int* __restrict__ planes_amax = nullptr) {
+                                                      const int* __restrict__ planes_amax = nullptr,
+                                                      const int* __restrict__ slots = nullptr) {
   // planes: the fp16 plane image of dx in the same pass, scaled by k_bn_bwd_final's bound (slot `planes_amax`)
   const float pscale = planes ? amax_scale(planes_amax) : 1.f;
   const int cq_n = c >> 2;
@@ -484,6 +545,15 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
 #define BN_DY(E, ROW) (dy_ld ? (HOIST ? reinterpret_cast<const float4*>(dy)[(ROW)*gld4 + q0]                       \
                                       : reinterpret_cast<const float4*>(dy)[((E) / cq_n) * gld4 + ((E) % cq_n)])  \
                              : reinterpret_cast<const float4*>(dy)[E])
+  // ROWS: the list position of quad E's row, its quad of the compact dy (zero off the list) and its place in the compact dres
+#define BN_SLOT(E, ROW) slots[HOIST ? (ROW) : (E) / cq_n]
+#define BN_DY_ROWS(G, E, SLOT) \
+  if ((SLOT) >= 0) G = reinterpret_cast<const float4*>(dy)[(SLOT)*gld4 + (HOIST ? q0 : (int)((E) % cq_n))];
+#define BN_DRES(E, SLOT, G)                                                                                       \
+  if (dres) {                                                                                                     \
+    if (!ROWS) reinterpret_cast<float4*>(dres)[E] = G;                                                            \
+    else if ((SLOT) >= 0) reinterpret_cast<float4*>(dres)[(SLOT)*cq_n + (HOIST ? q0 : (int)((E) % cq_n))] = G;    \
+  }
   const float4 z4 = make_float4(0, 0, 0, 0);
   float am = 0.f;
   BnBwdC ka, kb;
@@ -495,11 +565,17 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
       ka = bn_bwd_c(mean, rstd, weight, sum_g, sum_gx, (int)(e % cq_n));
       kb = bn_bwd_c(mean, rstd, weight, sum_g, sum_gx, (int)((okb ? f : 0) % cq_n));
     }
-    float4 xa = reinterpret_cast<const float4*>(x)[e], ga = BN_DY(e, row_e);
+    long long sa = -1, sb = -1;
+    if (ROWS) {
+      sa = BN_SLOT(e, row_e);
+      if (okb) sb = BN_SLOT(f, row_e + rstep);
+    }
+    float4 xa = reinterpret_cast<const float4*>(x)[e], ga = z4;
+    if (ROWS) { BN_DY_ROWS(ga, e, sa) } else ga = BN_DY(e, row_e);
     float4 xb = z4, gb = z4, ya = z4, yb = z4;
     if (okb) {
       xb = reinterpret_cast<const float4*>(x)[f];
-      gb = BN_DY(f, row_e + rstep);
+      if (ROWS) { BN_DY_ROWS(gb, f, sb) } else gb = BN_DY(f, row_e + rstep);
     }
     row_e += 2 * rstep;
     if (relu) {
@@ -512,16 +588,19 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
     reinterpret_cast<float4*>(dx)[e] = oa;
     am = amax4(am, oa);
     if (planes) store_planes4(planes, e / cq_n, c, (int)(e % cq_n) * 4, oa, pscale);
-    if (dres) reinterpret_cast<float4*>(dres)[e] = ga;
+    BN_DRES(e, sa, ga)
     if (okb) {
       const float4 ob = bn_bwd_one(xb, gb, inv_n, kb);
       reinterpret_cast<float4*>(dx)[f] = ob;
       am = amax4(am, ob);
       if (planes) store_planes4(planes, f / cq_n, c, (int)(f % cq_n) * 4, ob, pscale);
-      if (dres) reinterpret_cast<float4*>(dres)[f] = gb;
+      BN_DRES(f, sb, gb)
     }
   }
 #undef BN_DY
+#undef BN_SLOT
+#undef BN_DY_ROWS
+#undef BN_DRES
   if (amax_bits && !planes) publish_amax(am, amax_bits);
 }
 
@@ -758,13 +837,60 @@ int gcl_bn_bwd_apply_planes(const float* x, const float* dy, int32_t dy_ld, cons
   long long g = cdiv(total4, 256);
   if (g > 4096) g = 4096;
   if ((g * 256) % (c / 4) == 0)
-    hipLaunchKernelGGL(k_bn_bwd_apply<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, dy, y, total4, c,
+    hipLaunchKernelGGL((k_bn_bwd_apply<true, false>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, dy, y, total4, c,
                        1.0f / (float)n, mean, rstd, weight, sum_g, sum_gx, relu, (const unsigned long long*)relu_mask, dx,
                        dres, dx_amax, dy_ld, (unsigned short*)planes, (const int*)dx_amax);
   else
-    hipLaunchKernelGGL(k_bn_bwd_apply<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, dy, y, total4, c,
+    hipLaunchKernelGGL((k_bn_bwd_apply<false, false>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, dy, y, total4, c,
                        1.0f / (float)n, mean, rstd, weight, sum_g, sum_gx, relu, (const unsigned long long*)relu_mask, dx,
                        dres, dx_amax, dy_ld, (unsigned short*)planes, (const int*)dx_amax);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_bn_bwd_reduce_rows(const float* x, const float* g, int32_t g_ld, const int32_t* slots, const uint64_t* relu_mask,
+                           int64_t n, int32_t c, const float* mean, const float* rstd, int32_t relu, double* scratch,
+                           float* sum_g, float* sum_gx, const float* xrange, const float* weight, int32_t* dx_amax,
+                           void* stream) {
+  GCL_CHECK_ARG(g_ld == 0 || (g_ld >= c && g_ld % 4 == 0), "gcl_bn_bwd_reduce_rows: g_ld must be 0 or a multiple of 4 >= c");
+  GCL_CHECK_ARG(x && g && slots && mean && rstd && scratch && sum_g && sum_gx, "gcl_bn_bwd_reduce_rows: null pointer");
+  GCL_CHECK_ARG(!relu || relu_mask, "gcl_bn_bwd_reduce_rows: relu_mask is required when relu is set");
+  GCL_CHECK_ARG(n > 0 && bn_c_ok(c), "gcl_bn_bwd_reduce_rows: unsupported shape n=%lld c=%d", (long long)n, c);
+  GCL_CHECK_ARG(!dx_amax || (xrange && weight), "gcl_bn_bwd_reduce_rows: the bound of max|dx| needs xrange (forward pass) and the weight");
+  hipStream_t st = (hipStream_t)stream;
+  const int per_wg = bn_rows_per_wg(n, c);      // the dense pass's grid
+  const int nwg = (int)cdiv(n, per_wg);
+  hipLaunchKernelGGL(k_bn_reduce_rows, dim3(nwg), dim3(256), 0, st, x, g, (const int*)slots, (long long)n, c, mean, rstd,
+                     (const unsigned long long*)(relu ? relu_mask : nullptr), per_wg, scratch, g_ld, dx_amax ? 1 : 0);
+  const BnBwdRange rg{xrange, mean, rstd, weight, (long long)n, (int*)dx_amax};
+  hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)c), dim3(256), 0, st, (const double*)scratch, nwg, c, sum_g, sum_gx, rg);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_bn_bwd_apply_rows(const float* x, const float* g, int32_t g_ld, const int32_t* slots, const uint64_t* relu_mask,
+                          int64_t n, int32_t c, const float* mean, const float* rstd, const float* weight, const float* sum_g,
+                          const float* sum_gx, int32_t relu, float* dx, float* dres, int32_t* dx_amax, void* planes,
+                          void* stream) {
+  GCL_CHECK_ARG(g_ld == 0 || (g_ld >= c && g_ld % 4 == 0), "gcl_bn_bwd_apply_rows: g_ld must be 0 or a multiple of 4 >= c");
+  GCL_CHECK_ARG(x && g && slots && mean && rstd && weight && sum_g && sum_gx && dx, "gcl_bn_bwd_apply_rows: null pointer");
+  GCL_CHECK_ARG(!relu || relu_mask, "gcl_bn_bwd_apply_rows: relu_mask is required when relu is set");
+  GCL_CHECK_ARG(n > 0 && c >= 4 && c % 4 == 0, "gcl_bn_bwd_apply_rows: unsupported shape");
+  GCL_CHECK_ARG(!planes || (dx_amax && c % 32 == 0),
+                "gcl_bn_bwd_apply_rows: a plane image needs the slot that holds the bound of max|dx| and c a multiple of 32");
+  long long total4 = n * (c / 4);
+  long long grid = cdiv(total4, 256);
+  if (grid > 4096) grid = 4096;
+  if ((grid * 256) % (c / 4) == 0)
+    hipLaunchKernelGGL((k_bn_bwd_apply<true, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, g,
+                       (const float*)nullptr, total4, c, 1.0f / (float)n, mean, rstd, weight, sum_g, sum_gx, relu,
+                       (const unsigned long long*)relu_mask, dx, dres, dx_amax, g_ld, (unsigned short*)planes,
+                       (const int*)dx_amax, (const int*)slots);
+  else
+    hipLaunchKernelGGL((k_bn_bwd_apply<false, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, g,
+                       (const float*)nullptr, total4, c, 1.0f / (float)n, mean, rstd, weight, sum_g, sum_gx, relu,
+                       (const unsigned long long*)relu_mask, dx, dres, dx_amax, g_ld, (unsigned short*)planes,
+                       (const int*)dx_amax, (const int*)slots);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -166,6 +166,32 @@ __global__ void __launch_bounds__(256) k_scatter_rows(const float4* __restrict__
     if (r >= 0 && r < n_dst) reinterpret_cast<float4*>(dst + r * ld)[q] = src[i];
   }
 }
+// dst[rows[j]] += src[j] (src: [cap, c4 float4], row pitch src_ld floats): the list holds a row at most once, so one
+// thread owns an element of dst
+__global__ void __launch_bounds__(256) k_scatter_add_rows(const float* __restrict__ src, int src_ld,
+                                                          const int* __restrict__ rows, long long cap, int c4,
+                                                          long long n_dst, float* __restrict__ dst, int ld) {
+  const long long total = cap * c4;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long j = i / c4;
+    const int q = (int)(i - j * c4);
+    const long long r = rows[j];
+    if (r < 0 || r >= n_dst) continue;
+    const float4 a = reinterpret_cast<const float4*>(src + j * src_ld)[q];
+    float4* d = reinterpret_cast<float4*>(dst + r * ld) + q;
+    float4 v = *d;
+    v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+    *d = v;
+  }
+}
+// slots[rows[j]] = j for the rows of the list inside [0, n); the caller has filled slots with -1
+__global__ void __launch_bounds__(256) k_row_slots(const int* __restrict__ rows, long long cap, long long n,
+                                                   int* __restrict__ slots) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= cap) return;
+  const long long r = rows[j];
+  if (r >= 0 && r < n) slots[r] = (int)j;
+}
 // k_scatter_rows for the output of a forward pass that ran the row normalisation on the rows of a list: the same move, and
 // the rows of the compact tensors that belong to no row of dst (-1 padding, ids outside dst) are made inert in place --
 // y[j] = 0, norm[j] = 1 -- whatever the normalisation left there (0 / 0 when the row in front of it is zero)
@@ -506,8 +532,11 @@ static int maps_build(const int32_t* coords, long long n, const gcl_map_spec* sp
 // ---------------------------------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------------------------------
+struct RowView;
 struct TState {            // a tensor of the pass (forward value or gradient)
   float* ptr = nullptr;
+  RowView* rv = nullptr;     // a gradient kept compact: ptr is [rv->cap, c] (row pitch ld), the rows rv->rows of a tensor that
+                             // is exactly zero in every other row (the backward pass of a plan_backward call with a list)
   int32_t* amax = nullptr;   // amax slot that holds max|tensor|, or NULL = not measured yet
   void* planes = nullptr;    // gcl_split_planes image, or NULL = not made yet
   int ld = 0;                // row pitch in floats when the tensor is a column slice of a wider one (gradients of ME.cat
@@ -1044,10 +1073,34 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
   return GCL_OK;
 }
 
+struct RowView {
+  const int32_t* rows = nullptr;
+  long long cap = 0, n = 0;
+  bool parked = false;
+  std::vector<std::pair<const float*, float*>> gathered;
+  int32_t* slots = nullptr;      // [n]: a row's position in the list, -1 off it (row_slots: made when a kernel first needs it)
+  long long n_rows(const gcl_maps_desc& M, int level) const { return cap > 0 ? cap : M.n_rows[level]; }
+};
+
+static int contiguous(Plan& P, TState& g, long long rows, int c, hipStream_t st);
+
+// a compact gradient (g.rv) as the dense [n, c] tensor it stands for: for readers that take no list
+static int densify(Plan& P, TState& g, int c, hipStream_t st) {
+  if (!g.rv || !g.ptr) return GCL_OK;
+  const RowView& V = *g.rv;
+  int rc;
+  if ((rc = contiguous(P, g, V.cap, c, st))) return rc;
+  float* dense;
+  if ((rc = spread_rows(P, g.ptr, nullptr, V.rows, V.cap, c, V.n, &dense, st))) return rc;
+  g = TState();
+  g.ptr = dense;
+  return GCL_OK;
+}
+
 // Tape.backward's give(): the first gradient of a tensor is kept, later ones are added in arrival order
-// gptr: [rows, c] with row pitch ld floats (0 = c: contiguous; numel = rows * c)
+// gptr: [rows, c] with row pitch ld floats (0 = c: contiguous; numel = rows * c); rv: gptr is compact (TState::rv)
 static int give(Plan& P, int tensor, float* gptr, long long numel, hipStream_t st, int32_t* amax = nullptr, int ld = 0,
-                int c = 0) {
+                int c = 0, RowView* rv = nullptr) {
   Arena& A = P.A;
   if (tensor < 0 || !P.made[tensor] || !gptr) return GCL_OK;
   TState& g = P.g[tensor];
@@ -1055,8 +1108,21 @@ static int give(Plan& P, int tensor, float* gptr, long long numel, hipStream_t s
     g = TState();
     g.ptr = gptr;
     g.ld = ld;
+    g.rv = rv;
     g.amax = amax;        // published by the producing kernel (valid while the gradient stays this one tensor)
     return GCL_OK;
+  }
+  if (g.rv || rv) {      // two gradients of which one is compact meet outside a convolution epilogue: added as dense tensors
+    GCL_CHECK_ARG(c > 0 && c % 4 == 0, "gcl_plan_backward: a compact gradient needs its channel count");
+    TState in;
+    in.ptr = gptr;
+    in.ld = ld;
+    in.rv = rv;
+    numel = (g.rv ? g.rv : rv)->n * c;
+    int rc;
+    if ((rc = densify(P, g, c, st)) || (rc = densify(P, in, c, st))) return rc;
+    gptr = in.ptr;
+    ld = in.ld;
   }
   float* sum = A.take_n<float>(numel);
   if (!A.dry) {
@@ -1099,14 +1165,6 @@ static int contiguous(Plan& P, TState& g, long long rows, int c, hipStream_t st)
 // gradients are its sums over fewer rows in other groups.  The -1 padding rows are zero rows throughout (their norm reads 1:
 // no 0 / 0).  The saved operands are gathered onto the list, each once (`gathered`); after a forward pass that ran the
 // suffix on this list (`parked`, P.fwd_cap > 0) they ARE the compact tensors, with inert padding rows.
-struct RowView {
-  const int32_t* rows = nullptr;
-  long long cap = 0, n = 0;
-  bool parked = false;
-  std::vector<std::pair<const float*, float*>> gathered;
-  long long n_rows(const gcl_maps_desc& M, int level) const { return cap > 0 ? cap : M.n_rows[level]; }
-};
-
 // *out = the saved operand src ([n, c], row pitch ld) on the rows of V; pad: the value of its padding rows
 static int saved_rows(Plan& P, RowView& V, const float* src, int ld, int c, float pad, hipStream_t st, const float** out) {
   Arena& A = P.A;
@@ -1125,6 +1183,15 @@ static int saved_rows(Plan& P, RowView& V, const float* src, int ld, int c, floa
 }
 static int saved_rows(Plan& P, RowView& V, const TState& t, int c, hipStream_t st, const float** out) {
   return saved_rows(P, V, t.ptr, t.ld ? t.ld : c, c, 0.f, st, out);
+}
+
+// V.slots, made once per list
+static int row_slots(Plan& P, RowView& V, hipStream_t st) {
+  Arena& A = P.A;
+  if (V.slots) return GCL_OK;
+  V.slots = A.take_n<int32_t>(V.n);
+  PLAN_CALL(gcl_row_slots(V.rows, V.cap, V.n, V.slots, (void*)st));
+  return GCL_OK;
 }
 
 // ops._SparseConvFn.backward for record i with output gradient dy (dy.amax set when a producer published it)
@@ -1172,15 +1239,20 @@ static int conv_backward(Plan& P, int i, TState dy, RowView& V, void* const* gra
     const bool pl = pl_x;
     float* acc = P.g[op.x].ptr;       // a gradient that already reached x through another path: added in the epilogue
     const int acc_ld = P.g[op.x].ld;  // ... possibly a column slice of a cat's gradient
+    // ... or compact, the listed rows of a gradient that is zero elsewhere: the launch runs plain, and one launch on those
+    // rows adds them to its output (the same single fp32 addition per element as the epilogue's)
+    const RowView* acc_rows = P.g[op.x].rv;
+    GCL_CHECK_ARG(!acc_rows || (V.cap <= 0 && acc_rows->n == n_in && op.cin % 4 == 0),
+                  "gcl_plan_backward: record %d: a compact gradient waits at an input of another shape", i);
     float* dx = A.take_n<float>(n_in * op.cin);
     int32_t* dx_amax = nullptr;
     {
-      ProfScope ps(P, st, acc ? 1 : 0, pairs, op.cout, op.cin, n_out, n_in, op.K);
-      if (acc)
+      ProfScope ps(P, st, acc && !acc_rows ? 1 : 0, pairs, op.cout, op.cin, n_out, n_in, op.K);
+      if (acc && !acc_rows)
         PLAN_CALL(gcl_conv_fwd_fused_ld(pl ? (const float*)dy.planes : dy.ptr, n_out, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4,
                                         dy.amax, w_amax, tbl, order, mask, n_in, op.K, op.cout, op.cin, nullptr, nullptr, acc,
                                         acc_ld, 0, nullptr, dx, nullptr, 0, (void*)st));
-      else if (P.mask_from[i] >= 0) {
+      else if (!acc && P.mask_from[i] >= 0) {
         // x came out of a ReLU that nothing else reads: its backward (g where y > 0) in this epilogue, max|g| published
         dx_amax = new_slot(P);
         PLAN_CALL(gcl_conv_fwd_fused(pl ? (const float*)dy.planes : dy.ptr, n_out, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4,
@@ -1192,6 +1264,9 @@ static int conv_backward(Plan& P, int i, TState dy, RowView& V, void* const* gra
         PLAN_CALL(gcl_conv_fwd(pl ? (const float*)dy.planes : dy.ptr, n_out, pl ? 1 : 0, P.pack_bwd + P.off_bwd[wi], 4, dy.amax,
                                w_amax, tbl, order, mask, n_in, op.K, op.cout, op.cin, nullptr, dx, nullptr, 0, (void*)st));
     }
+    if (acc_rows)
+      PLAN_CALL(gcl_scatter_add_rows(acc, acc_ld ? acc_ld : op.cin, acc_rows->rows, acc_rows->cap, op.cin, n_in, dx, op.cin,
+                                     (void*)st));
     P.g[op.x] = TState();
     P.g[op.x].ptr = dx;
     P.g[op.x].amax = dx_amax;
@@ -1235,6 +1310,13 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
   P.g[op.y] = TState();
   if (!g.ptr) return GCL_OK;
   int rc;
+  // a compact gradient stays compact through an ME.cat and into the first BatchNorm backward, which mixes the rows: its
+  // statistics pass reads the listed rows only, its apply pass takes g through the list's slots and leaves dres compact
+  // -- every other record reads it as the dense tensor it stands for
+  const bool rows_ok = g.rv && V.cap <= 0 && g.rv->n == n_out &&
+                       (op.kind == GCL_OP_CAT || (op.kind == GCL_OP_CONVBN && (!op.relu || P.saved[i].mask)));
+  if (g.rv && !rows_ok && (rc = densify(P, g, op.cout, st))) return rc;
+  RowView* const rv = g.rv;      // the list of a gradient that stays compact in this record
   switch (op.kind) {
     case GCL_OP_CONVBN: {
       const OpSaved& sv = P.saved[i];
@@ -1247,16 +1329,29 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
       TState d;
       d.ptr = A.take_n<float>(n_out * c);
       d.amax = new_slot(P);
-      PLAN_CALL(gcl_bn_bwd_reduce_range(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean, sv.rstd,
-                                        op.relu, scratch, sum_g, sum_gx, sv.xrange, (const float*)P.params[op.bn_w],
-                                        bound ? d.amax : nullptr, (void*)st));
+      if (rv) {
+        if ((rc = row_slots(P, *rv, st))) return rc;
+        PLAN_CALL(gcl_bn_bwd_reduce_rows(sv.conv_out, g.ptr, g.ld, rv->slots, (const uint64_t*)sv.mask, n_out, c, sv.mean, sv.rstd,
+                                         op.relu, scratch, sum_g, sum_gx, sv.xrange, (const float*)P.params[op.bn_w],
+                                         bound ? d.amax : nullptr, (void*)st));
+      } else {
+        PLAN_CALL(gcl_bn_bwd_reduce_range(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean, sv.rstd,
+                                          op.relu, scratch, sum_g, sum_gx, sv.xrange, (const float*)P.params[op.bn_w],
+                                          bound ? d.amax : nullptr, (void*)st));
+      }
       if (bound) d.planes = A.take(n_out * c * 4);
-      float* dres = op.x2 >= 0 ? A.take_n<float>(n_out * c) : nullptr;
-      PLAN_CALL(gcl_bn_bwd_apply_planes(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean,
-                                        sv.rstd, (const float*)P.params[op.bn_w], sum_g, sum_gx, op.relu, d.ptr, dres,
-                                        d.amax, d.planes, (void*)st));
+      const long long res_rows = rv ? rv->cap : n_out;
+      float* dres = op.x2 >= 0 ? A.take_n<float>(res_rows * c) : nullptr;
+      if (rv)
+        PLAN_CALL(gcl_bn_bwd_apply_rows(sv.conv_out, g.ptr, g.ld, rv->slots, (const uint64_t*)sv.mask, n_out, c, sv.mean, sv.rstd,
+                                        (const float*)P.params[op.bn_w], sum_g, sum_gx, op.relu, d.ptr, dres, d.amax, d.planes,
+                                        (void*)st));
+      else
+        PLAN_CALL(gcl_bn_bwd_apply_planes(sv.conv_out, g.ptr, g.ld, nullptr, (const uint64_t*)sv.mask, n_out, c, sv.mean,
+                                          sv.rstd, (const float*)P.params[op.bn_w], sum_g, sum_gx, op.relu, d.ptr, dres,
+                                          d.amax, d.planes, (void*)st));
       if ((rc = conv_backward(P, i, d, V, grads, st))) return rc;
-      return give(P, op.x2, dres, n_out * c, st, nullptr, 0, c);
+      return give(P, op.x2, dres, res_rows * c, st, nullptr, 0, c, rv);
     }
     case GCL_OP_CONV:
       if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
@@ -1282,10 +1377,12 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
     case GCL_OP_CAT: {
       // the gradients of the two inputs ARE the column slices of g: handed on as views (row pitch = the cat's width); their
       // readers -- the BatchNorm backward kernels, a convolution epilogue that adds a waiting gradient -- take the pitch
+      // (a compact gradient is split the same way: the slices of its cap rows)
       const int ca = op.cin, cb = op.cout - op.cin;
-      if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
-      if ((rc = give(P, op.x, g.ptr, n_out * ca, st, nullptr, op.cout, ca))) return rc;
-      return give(P, op.x2, g.ptr + ca, n_out * cb, st, nullptr, op.cout, cb);
+      const long long rows = rv ? rv->cap : n_out;
+      if ((rc = contiguous(P, g, rows, op.cout, st))) return rc;
+      if ((rc = give(P, op.x, g.ptr, rows * ca, st, nullptr, op.cout, ca, rv))) return rc;
+      return give(P, op.x2, g.ptr + ca, rows * cb, st, nullptr, op.cout, cb, rv);
     }
     case GCL_OP_ROWNORM: {
       if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
@@ -1303,18 +1400,16 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
   }
 }
 
-// The touched-row suffix on the rows of a list: dy gathered onto it, the records on cap rows (RowView), and the compact
-// gradient of the suffix's input scattered into a zero-filled dense one that is handed on as the records hand theirs on
-static int suffix_backward(Plan& P, const float* dy, void* const* grads, const int32_t* rows, long long cap, hipStream_t st) {
+// The touched-row suffix on the rows of V's list: dy gathered onto it, the records on cap rows, and the compact gradient of the
+// suffix's input handed on compact (TState::rv = &V, which has to outlive the records that read it): no zero-filled dense
+// tensor -- the records behind it keep it compact up to the first BatchNorm backward (backward_record)
+static int suffix_backward(Plan& P, const float* dy, void* const* grads, RowView& V, hipStream_t st) {
   Arena& A = P.A;
   const gcl_plan_op &head = P.ops[P.suffix_first], &tail = P.ops.back();
-  RowView V;
-  V.rows = rows;
-  V.cap = cap;
   V.n = P.maps->n_rows[head.level_in];
   V.parked = P.fwd_cap > 0;
-  float* dyc = A.take_n<float>(cap * tail.cout);
-  PLAN_CALL(gcl_gather_rows(dy, tail.cout, V.n, rows, cap, tail.cout, 0.f, dyc, (void*)st));
+  float* dyc = A.take_n<float>(V.cap * tail.cout);
+  PLAN_CALL(gcl_gather_rows(dy, tail.cout, V.n, V.rows, V.cap, tail.cout, 0.f, dyc, (void*)st));
   P.g[tail.y] = TState();
   P.g[tail.y].ptr = dyc;
   int rc;
@@ -1322,13 +1417,17 @@ static int suffix_backward(Plan& P, const float* dy, void* const* grads, const i
     if ((rc = backward_record(P, i, V, grads, st))) return rc;
   const TState g = P.g[head.x];      // nothing but the suffix reads this tensor: the compact gradient is all of it
   P.g[head.x] = TState();
-  if (!g.ptr) {      // the suffix's input wants no gradient (the sizing reserves the room all the same)
-    A.take_n<float>(V.n * head.cin);
-    return GCL_OK;
-  }
-  float* dx;
-  if ((rc = spread_rows(P, g.ptr, nullptr, rows, cap, head.cin, V.n, &dx, st))) return rc;
-  return give(P, head.x, dx, V.n * head.cin, st, g.amax, 0, head.cin);
+  // the room of the dense [n, cin] gradient stays reserved: a densify() behind the suffix -- a segment that ends in front of
+  // the first BatchNorm backward, a compact gradient that meets a dense one -- takes as much, and the sizing has to cover it
+  A.take_n<float>(V.n * head.cin);
+  if (!g.ptr) return GCL_OK;      // the suffix's input wants no gradient
+  return give(P, head.x, g.ptr, V.cap * head.cin, st, nullptr, 0, head.cin, &V);
+}
+
+static int tensor_width(const Plan& P, int tensor) {      // channels of a tensor a record of the plan produces
+  for (const gcl_plan_op& op : P.ops)
+    if (op.y == tensor) return op.cout;
+  return 0;
 }
 
 static int plan_backward(Plan& P, const float* dy, void* const* grads, int first, int last, hipStream_t st,
@@ -1357,11 +1456,16 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
   // touched-row suffix: on the rows of a list when there is one and it is short, else dense like every other record
   int top = last - 1, rc;
   long long reserve_to = 0;
+  RowView list;      // the list of this call: the compact gradients behind the suffix point at it
   if (last == n_ops && !A.dry) P.suffix_rows_used = 0;
   if (last == n_ops && P.suffix_first < n_ops && P.suffix_rows_ok && first <= P.suffix_first) {
     const long long n = M.n_rows[P.ops[P.suffix_first].level_in];
     // counted: the same calls without a launch, which leave nothing behind but *end, the arena offset they reached
     auto run = [&](const int32_t* r, long long c, bool counted, long long* end) {
+      RowView scratch_view;      // a counted run leaves no gradient behind that could name its list
+      RowView& V = counted ? scratch_view : list;
+      V.rows = r;
+      V.cap = c;
       const Arena a0 = A;
       const long long slot0 = P.next_slot;
       std::vector<TState> g0;
@@ -1371,7 +1475,7 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
         masked0 = P.relu_masked;
         A.dry = true;
       }
-      const int rcs = suffix_backward(P, dy, grads, r, c, st);
+      const int rcs = suffix_backward(P, dy, grads, V, st);
       *end = A.off;
       if (counted) {
         A = a0;
@@ -1403,6 +1507,9 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
     if ((rc = backward_record(P, i, dense, grads, st))) return rc;
   }
   if (reserve_to && A.off < reserve_to) A.off = reserve_to;
+  // a segment that ends in front of the first BatchNorm backward: the gradients that wait for the next call wait dense
+  for (size_t t = 0; t < P.g.size(); ++t)
+    if (P.g[t].rv && (rc = densify(P, P.g[t], tensor_width(P, (int)t), st))) return rc;
   return join_aux(P, st);      // the caller may hand the gradients of this segment to a collective / the optimizer next
 }
 
@@ -1884,6 +1991,27 @@ int gcl_scatter_rows(const float* src, const int32_t* rows, int64_t cap, int32_t
                 "gcl_scatter_rows: channel count and row pitch must be multiples of 4, the tensors 16-byte aligned");
   hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(cap * c / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)src,
                      (const int*)rows, (long long)cap, c / 4, (long long)n_dst, dst, ld);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_scatter_add_rows(const float* src, int32_t src_ld, const int32_t* rows, int64_t cap, int32_t c, int64_t n_dst,
+                         float* dst, int32_t ld, void* stream) {
+  GCL_CHECK_ARG(src && rows && dst && n_dst > 0 && cap > 0, "gcl_scatter_add_rows: bad argument");
+  GCL_CHECK_ARG(c > 0 && c % 4 == 0 && ld >= c && ld % 4 == 0 && src_ld >= c && src_ld % 4 == 0 &&
+                    (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
+                "gcl_scatter_add_rows: channel count and row pitches must be multiples of 4, the tensors 16-byte aligned");
+  hipLaunchKernelGGL(k_scatter_add_rows, dim3(grid_for(cap * c / 4)), dim3(256), 0, (hipStream_t)stream, src, src_ld,
+                     (const int*)rows, (long long)cap, c / 4, (long long)n_dst, dst, ld);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_row_slots(const int32_t* rows, int64_t cap, int64_t n, int32_t* slots, void* stream) {
+  GCL_CHECK_ARG(rows && slots && n > 0 && cap > 0 && cap < (1ll << 31), "gcl_row_slots: bad argument");
+  GCL_CHECK_HIP(hipMemsetAsync(slots, 0xff, (size_t)n * sizeof(int32_t), (hipStream_t)stream));
+  hipLaunchKernelGGL(k_row_slots, dim3((unsigned)cdiv(cap, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)rows,
+                     (long long)cap, (long long)n, slots);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -538,6 +538,24 @@ int gcl_bn_bwd_apply_planes(const float* x, const float* dy, int32_t dy_ld, cons
                             int32_t c, const float* mean, const float* rstd, const float* weight, const float* sum_g,
                             const float* sum_gx, int32_t relu, float* dx, float* dres, int32_t* dx_amax, void* planes,
                             void* stream);
+/* The backward pair with the gradient supplied sparsely: g is the compact [cap, c] tensor (row pitch g_ld floats, 0 = c) of
+ * the rows of a list (distinct rows of [0, n)); every other row of the dense dy is exactly zero.  Both entries find a row's
+ * g through slots[n] (gcl_row_slots: the row's position in the list, -1 off it).
+ * gcl_bn_bwd_reduce_rows reads x, g and the ReLU bits at the listed rows only and leaves what gcl_bn_bwd_reduce_range leaves,
+ * bit for bit: it runs the dense pass's grid, every thread on the rows it takes there in the same order, so the fp64
+ * additions are the dense pass's without its exact-zero terms -- the grid and the order depend on (n, c) only.  A padding
+ * entry of the list has no slot and adds nothing.  scratch: double[gcl_bn_scratch_len(n, c)].
+ * gcl_bn_bwd_apply_rows walks all n rows as gcl_bn_bwd_apply_planes does (dx is dense; a wave without a listed row loads no
+ * g).  dres (optional) is COMPACT, [cap, c]: the gated gradient of the listed rows -- its padding rows are not written.
+ * The ReLU gate takes the sign bits (relu_mask) only. */
+int gcl_bn_bwd_reduce_rows(const float* x, const float* g, int32_t g_ld, const int32_t* slots, const uint64_t* relu_mask,
+                           int64_t n, int32_t c, const float* mean, const float* rstd, int32_t relu, double* scratch,
+                           float* sum_g, float* sum_gx, const float* xrange, const float* weight, int32_t* dx_amax,
+                           void* stream);
+int gcl_bn_bwd_apply_rows(const float* x, const float* g, int32_t g_ld, const int32_t* slots, const uint64_t* relu_mask,
+                          int64_t n, int32_t c, const float* mean, const float* rstd, const float* weight, const float* sum_g,
+                          const float* sum_gx, int32_t relu, float* dx, float* dres, int32_t* dx_amax, void* planes,
+                          void* stream);
 
 /* Row-wise L2 normalisation of the output features, y = x / ||x||_2 (model/resunet.py:226-230; no epsilon, as there).
  * norm[n] keeps the row norms for the backward pass: dx = (dy - y (y . dy)) / norm.  c: power of two in [4, 256].
@@ -1072,6 +1090,18 @@ int gcl_gather_rows(const float* src, int32_t ld, int64_t n_src, const int32_t* 
                     float* out, void* stream);
 int gcl_scatter_rows(const float* src, const int32_t* rows, int64_t cap, int32_t c, int64_t n_dst, float* dst, int32_t ld,
                      void* stream);
+/* With a list, the backward pass does not zero-fill and scatter the gradient of the suffix's input (earlier versions did):
+ * it stays compact, [cap, c], through the ME.cat in front of the suffix (split by columns) and into the first BatchNorm
+ * backward, which mixes the rows (gcl_bn_bwd_reduce_rows / gcl_bn_bwd_apply_rows: sums and dx bitwise the dense pass's).  A
+ * compact gradient that waits at a tensor -- that BatchNorm's residual branch, the cat's other input -- is not handed to the
+ * next input-gradient launch as an epilogue operand: the launch runs plain and one launch on cap rows adds it to the output,
+ * the same single fp32 addition per element.  Everything upstream stays bitwise the dense pass's.  Any other reader of a
+ * compact gradient, and the end of a segmented call, gets it as the dense tensor it stands for (zero fill + scatter).  gcl_scatter_add_rows: dst[rows[j], :] += src[j, :] (src: [cap, c], row pitch src_ld;
+ * dst: row pitch ld; the rows of the list are distinct, so one thread owns an element: no atomics).  gcl_row_slots:
+ * slots[n] = the position j of row rows[j], -1 for a row that is not on the list. */
+int gcl_scatter_add_rows(const float* src, int32_t src_ld, const int32_t* rows, int64_t cap, int32_t c, int64_t n_dst,
+                         float* dst, int32_t ld, void* stream);
+int gcl_row_slots(const int32_t* rows, int64_t cap, int64_t n, int32_t* slots, void* stream);
 /* a stream whose kernels run on the lowest `percent` % of the device's CUs (hipExtStreamCreateWithCUMask) -- measurement hook
  * for the weight-gradient stream (GCL_AUX_CU_PCT); gcl_stream_destroy frees it */
 int gcl_stream_create_cu_share(int32_t percent, int32_t low_priority, void** stream_out);
