@@ -2,7 +2,7 @@
 
 Exports exactly the symbols the reference's hot path uses:
 ``SparseTensor, MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,
-MinkowskiInstanceNorm (declared, out of scope), MinkowskiFunctional.relu, cat, MinkowskiNetwork,
+MinkowskiInstanceNorm, MinkowskiFunctional.relu, cat, MinkowskiNetwork,
 utils.sparse_quantize / batched_coordinates / sparse_collate``
 with the call signatures found at model/resunet.py:38-171, model/residual_block.py:23-53, model/common.py:4-10,
 lib/colocation_trainer.py:843-845, scripts/test_kitti.py:143-147, util/misc.py:118-128.
@@ -246,7 +246,8 @@ class MinkowskiInstanceNorm(nn.Module):
     batch is normalised on its own -- per channel (x - mean) / sqrt(var + 1e-8) with the biased variance over the
     cloud's voxels, no running statistics (train == eval) -- followed by a shared affine map with parameters
     ``weight`` / ``bias`` of shape [1, C] (ME 0.5).  ``forward(x, residual=None, relu=False)`` exposes the same fused
-    residual-add / ReLU as MinkowskiBatchNorm."""
+    residual-add / ReLU as MinkowskiBatchNorm.  All clouds of the tensor run in one gcl_in_fwd / gcl_in_bwd call, whatever
+    the order of its rows (csrc/instnorm.hip; the clouds' row lists come from CoordinateManager.cloud_rows)."""
 
     EPS = 1e-8
 
@@ -259,8 +260,8 @@ class MinkowskiInstanceNorm(nn.Module):
     def forward(self, x, residual=None, relu=False):
         if residual is not None and residual.coordinate_map_key != x.coordinate_map_key:
             raise ValueError("residual lives on a different coordinate map")
-        seg = x.coordinate_manager.batch_segments(x.coordinate_map_key.tensor_stride)
-        F = ops.instance_norm(x.F, self.weight, self.bias, seg, self.EPS,
+        clouds = x.coordinate_manager.cloud_rows(x.coordinate_map_key.tensor_stride)
+        F = ops.instance_norm(x.F, self.weight, self.bias, clouds, self.EPS,
                               residual.F if residual is not None else None, relu)
         out = SparseTensor(F, coordinate_map_key=x.coordinate_map_key, coordinate_manager=x.coordinate_manager)
         out._nonneg = bool(relu)

@@ -130,7 +130,8 @@ class CoordinateManager:
         nm = NativeMaps(coordinates, specs, n_levels, arena, side_stream=side_stream)
         self = cls.__new__(cls)
         self.native, self.device = nm, nm.device
-        self._segments, self._maps, self._status = {}, {}, {}
+        self._maps, self._status = {}, {}
+        self._cloud_rows, self._n_clouds = {}, None
         self._checked = set(1 << l for l in range(nm.n_levels))       # gcl_maps_build has validated the coordinates
         self._kmaps, self._identity, self._bitmap = {}, {}, None
         return self
@@ -179,7 +180,6 @@ class CoordinateManager:
         return km
 
     def __init__(self, coordinates):
-        self._segments = {}
         lib = _lib.require_gpu()
         if coordinates.dim() != 2 or coordinates.shape[1] != 4:
             raise ValueError("coordinates must be [N, 4] = (batch, x, y, z)")
@@ -197,6 +197,7 @@ class CoordinateManager:
         self._kmaps = {}
         self._identity = {}
         self._bitmap = None
+        self._cloud_rows, self._n_clouds = {}, None      # cloud_rows(): tables per stride, the number of clouds
 
     # -- coordinate maps -----------------------------------------------------------------------------------
     def _input_table(self):
@@ -238,22 +239,23 @@ class CoordinateManager:
     def num_rows(self, t):
         return self.get_coords(t).shape[0]
 
-    def batch_segments(self, t):
-        """[(first row, rows)] of every cloud at tensor stride ``t`` (InstanceNorm normalises per cloud).  Rows of one
-        cloud must be contiguous, which holds for collated input and for every strided map derived from it (first-
-        occurrence order); anything else is rejected.  One host read per level, cached."""
-        if t not in self._segments:
-            b = self.get_coords(t)[:, 0]
-            vals, counts = torch.unique_consecutive(b, return_counts=True)
-            vals, counts = vals.tolist(), counts.tolist()
-            if len(set(vals)) != len(vals):
-                raise NotImplementedError("MinkowskiInstanceNorm needs the rows of each cloud to be contiguous")
-            seg, start = [], 0
-            for c in counts:
-                seg.append((start, c))
-                start += c
-            self._segments[t] = seg
-        return self._segments[t]
+    def cloud_rows(self, t):
+        """``(seg_off, rows, row_cloud, n_clouds)`` of tensor stride ``t``: what gcl_in_fwd / gcl_in_bwd take to normalise every
+        cloud on its own (MinkowskiInstanceNorm).  ``row_cloud`` int32 [n] is the batch column, ``rows`` int32 [n] the rows
+        grouped by cloud with each cloud's rows in their own order (a stable sort), ``seg_off`` int64 [n_clouds + 1] the
+        prefix of the clouds' row counts -- device tensors made by device ops, for rows in ANY order; a batch index without
+        rows is an empty cloud.  ``n_clouds`` (largest batch index + 1) is the one host read of the manager, shared by its
+        strides; the tables are cached per stride."""
+        tables = self._cloud_rows
+        if t not in tables:
+            b = self.get_coords(t)[:, 0].contiguous()
+            if self._n_clouds is None:
+                self._n_clouds = int(self.get_coords(1)[:, 0].max()) + 1
+            n_clouds = self._n_clouds
+            sorted_b, order = torch.sort(b, stable=True)
+            seg_off = torch.searchsorted(sorted_b, torch.arange(n_clouds + 1, dtype=torch.int32, device=b.device))
+            tables[t] = (seg_off, order.to(torch.int32), b, n_clouds)
+        return tables[t]
 
     def _build_stride_maps(self, t):
         """Builds every missing power-of-two level up to max(t, 8) in ONE chain of launches: level 2s is built from

@@ -15,6 +15,8 @@
  *           gcl_stem_fwd / gcl_stem_bwd_weight       (Cin <= 4 first layer, model/resunet.py:38-45)
  *   ME.MinkowskiBatchNorm + MEF.relu + `out += residual`   model/common.py:4-6, model/residual_block.py:37-53
  *        -> gcl_bn_stats, gcl_bn_apply, gcl_bn_bwd_reduce, gcl_bn_bwd_apply
+ *   ME.MinkowskiInstanceNorm (every cloud on its own)   model/common.py:7-8, model/resunet.py:269-291
+ *        -> gcl_in_fwd, gcl_in_bwd
  *   out.F / torch.norm(out.F, p=2, dim=1, keepdim=True)   model/resunet.py:226-230  -> gcl_row_normalize_fwd/bwd
  *   finest_contrastive_loss                          lib/colocation_trainer.py:430-535
  *        -> gcl_group_loss_fwd/bwd, gcl_nn_rowmin (pdist + min, lib/metrics.py:22-25),
@@ -556,6 +558,41 @@ int gcl_bn_bwd_apply_rows(const float* x, const float* g, int32_t g_ld, const in
                           int64_t n, int32_t c, const float* mean, const float* rstd, const float* weight, const float* sum_g,
                           const float* sum_gx, int32_t relu, float* dx, float* dres, int32_t* dx_amax, void* planes,
                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * InstanceNorm over the rows of [n, c] (ME.MinkowskiInstanceNorm, model/common.py:7-8): every cloud of a batch is
+ * normalised on its own -- per channel (x - mean) / sqrt(var + eps), biased variance over the cloud's rows -- then the
+ * shared affine map, fused with the residual add and ReLU like BatchNorm.  All clouds in a fixed number of launches (four
+ * per entry), rows in any order, nothing read back by the host.  Device inputs that describe the clouds:
+ *   seg_off   int64 [n_clouds + 1]  prefix of the clouds' row counts (seg_off[n_clouds] = n)
+ *   rows      int32 [n] or NULL     the i-th row of cloud b is rows[seg_off[b] + i]: the rows grouped by cloud, every cloud's
+ *                                   rows in their order in x (a stable sort by cloud); NULL = identity (contiguous clouds)
+ *   row_cloud int32 [n]             the cloud of each row
+ * n_clouds (1 .. 65535) is a host integer; a cloud without rows is skipped: nothing is read or written for it, its rows of
+ * the [n_clouds, c] tables keep what they held.
+ * On each cloud the statistics are those of gcl_bn_stats / gcl_bn_bwd_reduce run on the cloud's rows alone, bit for bit (the
+ * same chunks, threads, order of additions and conversions), and y / dx / dres those of gcl_bn_apply / gcl_bn_bwd_apply
+ * with 1 / rows_b formed on the device; deterministic, no floating-point atomics.
+ *   gcl_in_scratch_len(n, n_clouds, c), in doubles:
+ *        (cdiv(n, 64) + n_clouds) * 2 * c      chunk sums (a chunk has at least 64 rows of one cloud)
+ *      + (n_clouds + 1)                        int64 prefix of the clouds' chunk counts
+ *      + (n_clouds + 1) / 2                    float 1 / rows_b per cloud
+ *        0 for n <= 0, n_clouds < 1 or c < 1.
+ *   gcl_in_fwd:  mean / rstd [n_clouds, c], y [n, c]; with relu the sign bits of y into relu_mask
+ *                (uint64 [gcl_bn_mask_len(n, c)], ONE mask for the tensor, indexed by the tensor's own quads; required with
+ *                relu); y_amax (optional, ZERO-INITIALISED amax slot) receives gcl_amax of y.
+ *   gcl_in_bwd:  g = dy * (relu ? y > 0 : 1);  sum_g / sum_gx [n_clouds, c] (per cloud; the affine map's gradients are
+ *                their column sums), dx [n, c], optionally dres = g and gcl_amax of dx in dx_amax.
+ * c as for gcl_bn_stats (a multiple of 4 with c / 4 dividing 256); n < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t gcl_in_scratch_len(int64_t n, int32_t n_clouds, int32_t c);
+int gcl_in_fwd(const float* x, int64_t n, int32_t c, const int64_t* seg_off, const int32_t* rows, const int32_t* row_cloud,
+               int32_t n_clouds, float eps, const float* weight, const float* bias, const float* residual, int32_t relu,
+               double* scratch, float* mean, float* rstd, float* y, uint64_t* relu_mask, int32_t* y_amax, void* stream);
+int gcl_in_bwd(const float* x, const float* dy, int64_t n, int32_t c, const int64_t* seg_off, const int32_t* rows,
+               const int32_t* row_cloud, int32_t n_clouds, const float* mean, const float* rstd, const float* weight,
+               int32_t relu, const uint64_t* relu_mask, double* scratch, float* sum_g, float* sum_gx, float* dx, float* dres,
+               int32_t* dx_amax, void* stream);
 
 /* Row-wise L2 normalisation of the output features, y = x / ||x||_2 (model/resunet.py:226-230; no epsilon, as there).
  * norm[n] keeps the row norms for the backward pass: dx = (dy - y (y . dy)) / norm.  c: power of two in [4, 256].
