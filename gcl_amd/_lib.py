@@ -90,6 +90,7 @@ SIGNATURES = {
     "gcl_kernel_map_scratch_len": (_i64, [_i32, _i64]),
     "gcl_kernel_map": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "gcl_kernel_map_pairs": (_i32, [_vp, _i32, _i64, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp]),
+    "gcl_map_launch_shape": (_i32, [_i64, _i32, _i32, ctypes.POINTER(_i32)]),
     "gcl_pack_weights_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "gcl_amax": (_i32, [_vp, _i64, _vp, _i32, _vp]),
     "gcl_amax_multi": (_i32, [_vp, _vp, _i32, _vp, _vp]),

@@ -76,6 +76,19 @@ __device__ __forceinline__ long long table_find(const Slot* t, long long cap, un
   }
 }
 
+// ---- the map builders' host decisions (coords.hip: map_launch_shape; exported as gcl_map_launch_shape) ----------------
+struct MapShape {
+  int stride_long;   // strided level: 0 = short form (flags + block totals, final scan + emit), 1 = long form
+  int scan_blocks;   // strided level: scan blocks of SCAN_B rows
+  int acc;           // kernel map: per-offset counts by integer atomics (flag bit 2 and few blocks)
+  int grid_x, grid_y;      // kernel map: blocks of 256 rows, blocks of MAP_KPT offsets
+  int reduce;        // kernel map: k_count_reduce is launched (over grid_x per-block counts)
+  int pair_blocks;   // pair lists: compaction blocks of PAIR_B rows
+  int prefill;       // gcl_maps_build: one -1 fill for every neighbour table of the build (gcl_kernel_map flag bit 3)
+  int use_bitmap;    // gcl_maps_build: a presence bitmap per coordinate table
+};
+MapShape map_launch_shape(long long n, int ks, int flags);
+
 // ---- wave helpers ---------------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

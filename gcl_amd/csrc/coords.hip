@@ -923,6 +923,36 @@ __global__ void __launch_bounds__(SCAN_T) k_stride_final_emit(const int4* __rest
 
 static bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// ---- every size-dependent decision of the map builders (host arithmetic; gcl_map_launch_shape exports it, so that a test
+// can place a case on either side of each limit without a GPU).  `n` is the row count the caller dispatches on: n_in of a
+// strided level, n_out of a kernel map and of its pair lists, the input rows of a gcl_maps_build call.
+constexpr int MAP_KPT = 4;      // offsets per thread of the lookup kernels (1 and 2 measured slower, round 5)
+// (64 blocks = 16 384 rows.  The K counters share two cache lines: at 256 / 1024 blocks the atomics cost more than the
+// launch they save -- eight pairs per pass 97.4 -> 89 - 96 / 87 - 94 M voxels/s, the training step 11.94 -> 12.0 / 12.35 ms)
+constexpr long long MAP_ACC_MAX_BLOCKS = 64;
+constexpr long long MAPS_PREFILL_MAX_ROWS = 65536;
+MapShape map_launch_shape(long long n, int ks, int flags) {
+  MapShape s;
+  const int K = ks * ks * ks;
+  // strided level: up to SCAN_T scan blocks the final pass adds up the raw block totals itself (short form, three launches);
+  // beyond that the flags, a three-launch scan and the emit pass run one by one (long form)
+  s.scan_blocks = (int)cdiv(n, SCAN_B);
+  s.stride_long = s.scan_blocks > SCAN_T ? 1 : 0;
+  // kernel map: 256 rows per block, MAP_KPT offsets per thread; a same-map looks up the offsets k <= K / 2 only
+  s.grid_x = (int)cdiv(n, 256);
+  s.grid_y = (int)cdiv((flags & 1) ? K / 2 + 1 : K, MAP_KPT);
+  s.acc = ((flags & 4) != 0 && s.grid_x <= MAP_ACC_MAX_BLOCKS) ? 1 : 0;
+  s.reduce = s.acc ? 0 : 1;
+  s.pair_blocks = (int)cdiv(n, PAIR_B);
+  // gcl_maps_build: one -1 fill for all neighbour tables of a small build; the presence bitmap (2 MB) pays when the table
+  // (16 bytes per slot, a power of two >= 2 n slots, at least 64) is more than four times its size
+  s.prefill = n <= MAPS_PREFILL_MAX_ROWS ? 1 : 0;
+  long long cap = 64;
+  while (cap < 2 * n) cap *= 2;
+  s.use_bitmap = cap * (long long)sizeof(Slot) > 4 * BITMAP_WORDS * (long long)sizeof(int32_t) ? 1 : 0;
+  return s;
+}
+
 // EMPTY-fills `slots` consecutive table slots (several levels' tables at once) and zeroes the four status words
 void tables_fill(int64_t* tables, long long slots, int32_t* zero4, hipStream_t st) {
   hipLaunchKernelGGL(k_table_fill, dim3((unsigned)cdiv(slots, 256)), dim3(256), 0, st, (Slot*)tables, slots, zero4);
@@ -959,8 +989,9 @@ int stride_map_impl(const int32_t* coords_in, int64_t n_in, const int32_t* n_in_
                        (long long)cap_out, status);
   hipLaunchKernelGGL(k_stride_insert, dim3(g), dim3(256), 0, st, (const int4*)coords_in, (long long)n_in,
                      (const int*)n_in_dev, t_out, (Slot*)table_out, (long long)cap_out, status);
-  const long long nb = cdiv(n_in, SCAN_B);
-  if (nb <= SCAN_T) {      // short form: three launches per level instead of six
+  const MapShape ms = map_launch_shape(n_in, 1, 0);
+  const long long nb = ms.scan_blocks;
+  if (!ms.stride_long) {      // short form: three launches per level instead of six
     hipLaunchKernelGGL(k_stride_flag_reduce, dim3((unsigned)nb), dim3(SCAN_T), 0, st, (const int4*)coords_in, (long long)n_in,
                        (const int*)n_in_dev, t_out, (const Slot*)table_out, (long long)cap_out, flag, bs);
     hipLaunchKernelGGL(k_stride_final_emit, dim3((unsigned)nb), dim3(SCAN_T), 0, st, (const int4*)coords_in, (long long)n_in,
@@ -1031,19 +1062,17 @@ int gcl_kernel_map(const int32_t* coords_out, int64_t n_out, const int64_t* tabl
   GCL_CHECK_ARG(ks >= 1 && (ks & 1) && ks <= 5, "gcl_kernel_map: kernel size must be 1, 3 or 5");
   GCL_CHECK_ARG(n_out > 0 && step >= 1 && is_pow2(cap_in), "gcl_kernel_map: bad sizes");
   const bool bitmap_valid = (same_map & 2) != 0;      // bit 1: `bitmap` already describes table_in (built by an earlier call)
-  // bit 2: `counts` is zero on entry and the build is short (<= 1024 blocks): per-offset counts by integer atomics, no
-  // k_count_reduce launch, `scratch` unused
-  // (64 blocks = 16 384 rows.  The K counters share two cache lines: at 256 / 1024 blocks the atomics cost more than the
-  // launch they save -- eight pairs per pass 97.4 -> 89 - 96 / 87 - 94 M voxels/s, the training step 11.94 -> 12.0 / 12.35 ms)
-  constexpr long long MAP_ACC_MAX_BLOCKS = 64;
-  const int acc = ((same_map & 4) != 0 && cdiv(n_out, 256) <= MAP_ACC_MAX_BLOCKS) ? 1 : 0;
+  // bit 2: `counts` is zero on entry and the build is short (<= MAP_ACC_MAX_BLOCKS = 64 blocks): per-offset counts by integer
+  // atomics, no k_count_reduce launch, `scratch` unused
+  const MapShape ms = map_launch_shape(n_out, ks, same_map);
+  const int acc = ms.acc;
   const bool prefilled = (same_map & 8) != 0;      // bit 3: nbr / nbr_t hold -1 everywhere on entry (one fill for all maps)
   same_map &= 1;
   GCL_CHECK_ARG(!same_map || (nbr_t == nullptr && n_in == n_out), "gcl_kernel_map: same_map excludes nbr_t");
   hipStream_t st = (hipStream_t)stream;
   int K = ks * ks * ks;
-  int nblk = (int)cdiv(n_out, 256);
-  constexpr int KPT = 4;      // offsets per thread of the lookup kernels (1 and 2 measured slower, round 5)
+  const int nblk = ms.grid_x;
+  constexpr int KPT = MAP_KPT;
   if (bitmap && !bitmap_valid) {
     fill32(bitmap, BITMAP_WORDS, 0u, st);
     hipLaunchKernelGGL(k_bitmap_fill, dim3((unsigned)cdiv(cap_in, 256)), dim3(256), 0, st, (const Slot*)table_in,
@@ -1052,16 +1081,16 @@ int gcl_kernel_map(const int32_t* coords_out, int64_t n_out, const int64_t* tabl
   if (same_map) {
     if (K > 1 && !prefilled)
       fill32(nbr + (size_t)(K / 2 + 1) * n_out, (long long)(K / 2) * n_out, 0xFFFFFFFFu, st);
-    hipLaunchKernelGGL(k_kernel_map_sym<KPT>, dim3(nblk, (unsigned)cdiv(K / 2 + 1, KPT)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_kernel_map_sym<KPT>, dim3(nblk, ms.grid_y), dim3(256), 0, st,
                        (const int4*)coords_out, (long long)n_out, (const Slot*)table_in, (long long)cap_in,
                        (const unsigned*)bitmap, ks, step, nbr, acc ? counts : scratch, acc);
-    if (!acc) hipLaunchKernelGGL(k_count_reduce, dim3(K / 2 + 1), dim3(256), 0, st, (const int*)scratch, nblk, K, 1, counts);
+    if (ms.reduce) hipLaunchKernelGGL(k_count_reduce, dim3(K / 2 + 1), dim3(256), 0, st, (const int*)scratch, nblk, K, 1, counts);
   } else {
     if (nbr_t && !prefilled) fill32(nbr_t, (long long)K * n_in, 0xFFFFFFFFu, st);
-    hipLaunchKernelGGL(k_kernel_map<KPT>, dim3(nblk, (unsigned)cdiv(K, KPT)), dim3(256), 0, st, (const int4*)coords_out,
+    hipLaunchKernelGGL(k_kernel_map<KPT>, dim3(nblk, ms.grid_y), dim3(256), 0, st, (const int4*)coords_out,
                        (long long)n_out, (const Slot*)table_in, (long long)cap_in, (const unsigned*)bitmap, ks, step, nbr,
                        nbr_t, (long long)n_in, acc ? counts : scratch, acc);
-    if (!acc) hipLaunchKernelGGL(k_count_reduce, dim3(K), dim3(256), 0, st, (const int*)scratch, nblk, K, 0, counts);
+    if (ms.reduce) hipLaunchKernelGGL(k_count_reduce, dim3(K), dim3(256), 0, st, (const int*)scratch, nblk, K, 0, counts);
   }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
@@ -1078,12 +1107,22 @@ int gcl_kernel_map_pairs(const int32_t* nbr, int32_t K, int64_t n_out, const int
     GCL_CHECK_ARG(seg.off[k] % GCL_PAIR_CHUNK == 0, "gcl_kernel_map_pairs: segment offsets must be multiples of %d",
                   GCL_PAIR_CHUNK);
   }
-  int nb = (int)cdiv(n_out, PAIR_B);
+  const int nb = map_launch_shape(n_out, 1, 0).pair_blocks;
   hipLaunchKernelGGL(k_pairs_count, dim3(nb, K), dim3(256), 0, st, nbr, (long long)n_out, nb, scratch);
   hipLaunchKernelGGL(k_pairs_scan, dim3(K), dim3(256), 0, st, scratch, nb);
   hipLaunchKernelGGL(k_pairs_emit, dim3(nb, K), dim3(256), 0, st, nbr, (long long)n_out, nb, (const int*)scratch, seg,
                      pair_in, pair_out);
   GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int gcl_map_launch_shape(int64_t n, int32_t ks, int32_t same_map, int32_t out[12]) {
+  GCL_CHECK_ARG(out && n > 0 && n <= INT_MAX && ks >= 1 && (ks & 1) && ks <= 5 && same_map >= 0 && same_map < 16,
+                "gcl_map_launch_shape: bad argument");
+  const MapShape s = map_launch_shape(n, ks, same_map);
+  const int v[12] = {s.stride_long, s.scan_blocks, s.acc, s.grid_x, s.grid_y, s.reduce, s.pair_blocks, s.prefill, s.use_bitmap,
+                     MAP_KPT, 0, 0};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
   return GCL_OK;
 }
 

@@ -378,7 +378,8 @@ static int maps_build(const int32_t* coords, long long n, const gcl_map_spec* sp
   struct MapLaunch { int s, src5, flags; int32_t *bitmap, *scratch; void* stream; };
   MapLaunch launches[GCL_MAX_MAPS];
   int n_launches = 0;
-  const bool prefill = !A.dry && !side && n <= 65536;
+  const MapShape mshape = map_launch_shape(n, 1, 0);
+  const bool prefill = !A.dry && !side && mshape.prefill;
   char* fill_lo = nullptr;
   for (int s = 0; s < n_specs; ++s) {
     const gcl_map_spec& sp = specs[s];
@@ -416,7 +417,7 @@ static int maps_build(const int32_t* coords, long long n, const gcl_map_spec* sp
     }
     // the presence bitmap (2 MB) pays when the table is much larger than it; a table of <= 8 MB (<= 256 k slots: a pass over
     // a few clouds) sits in the caches itself and the bitmap's fill + build are two launches per level for nothing
-    const bool use_bitmap = A.dry || out->cap[d.level_in] * 16 > 4 * gcl_kernel_map_bitmap_len() * (long long)sizeof(int32_t);
+    const bool use_bitmap = A.dry || mshape.use_bitmap;      // (every level's table has the input level's capacity)
     const bool bitmap_valid = use_bitmap && bitmap[sd][d.level_in] != nullptr;     // shared by the maps of ONE stream only
     if (use_bitmap && !bitmap_valid) bitmap[sd][d.level_in] = A.take_n<int32_t>(gcl_kernel_map_bitmap_len());
     int32_t* scratch = A.take_n<int32_t>(gcl_kernel_map_scratch_len(sp.kernel_size, d.n_out));

@@ -232,6 +232,16 @@ int gcl_kernel_map(const int32_t* coords_out, int64_t n_out, const int64_t* tabl
 int gcl_kernel_map_pairs(const int32_t* nbr, int32_t K, int64_t n_out, const int64_t* seg_off_host,
                          int32_t* scratch, int32_t* pair_in, int32_t* pair_out, void* stream);
 
+/* What the map builders launch for a row count: host arithmetic, no GPU (gcl_stride_map / gcl_unique_coords,
+ * gcl_kernel_map, gcl_kernel_map_pairs and gcl_maps_build call the same function; tests place their cases on both sides
+ * of every limit with it).  n = the row count the entry dispatches on (n_in of a strided level, n_out of a kernel map and
+ * of its pair lists, the input rows of gcl_maps_build); ks, same_map as for gcl_kernel_map.
+ * out = {strided level: 1 = long form (flags, three-launch scan, emit), 0 = short form; its scan blocks;
+ *        kernel map: counts by integer atomics; grid x; grid y; the count reduction is launched (over grid x blocks);
+ *        pair lists: compaction blocks; gcl_maps_build: one -1 fill for all tables; a presence bitmap per table;
+ *        offsets per thread of the lookup kernels; 0; 0}. */
+int gcl_map_launch_shape(int64_t n, int32_t ks, int32_t same_map, int32_t out[12]);
+
 /* Row ordering for the output-stationary convolution: sorts the rows of a [K][n] neighbour table (K <= 27) by
  * their K-bit presence mask (stable radix sort), so that the rows of a 32-row wave tile need nearly the same offsets.
  * The sort key is the mask with its bits re-ordered by how often each offset occurs in THIS table -- the
