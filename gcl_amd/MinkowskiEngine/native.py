@@ -502,6 +502,21 @@ class NetworkPlan:
         n, s = len(self.records), _lib.load().gcl_plan_touched_suffix(self.handle)
         return all(last <= s or (first <= s and last == n) for first, last, _ in self._segments())
 
+    def set_keep_fp32(self, keep):
+        """``keep`` true: the passes from the next ``run`` on write (and size) the fp32 twin of every tensor, also of those
+        the plan keeps as a plane image only by default (gcl_plan_set_keep_fp32) -- for tests and comparisons; the results
+        are bitwise the same either way."""
+        _lib.check(_lib.load().gcl_plan_set_keep_fp32(self.handle, int(bool(keep))), "gcl_plan_set_keep_fp32")
+
+    def plane_only(self):
+        """(forward, backward): the record indices whose output / whose BatchNorm input gradient exists as a plane image
+        only (gcl_plan_plane_only); both empty while ``set_keep_fp32(True)`` holds."""
+        n = len(self.records)
+        flags = (ctypes.c_int32 * n)()
+        if _lib.load().gcl_plan_plane_only(self.handle, flags, n) < 0:
+            raise RuntimeError("gcl_plan_plane_only: " + _lib.load().gcl_last_error().decode())
+        return [i for i in range(n) if flags[i] & 1], [i for i in range(n) if flags[i] & 2]
+
     def output_rows(self, maps):
         """Rows of the output of a pass on ``maps``."""
         return int(maps.desc.n_rows[self.records[-1]["level_out"]])

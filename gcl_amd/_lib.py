@@ -165,6 +165,8 @@ SIGNATURES = {
     "gcl_plan_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gcl_plan_release": (_i32, [_vp, _vp]),
     "gcl_plan_set_aux_stream": (_i32, [_vp, _vp]),
+    "gcl_plan_set_keep_fp32": (_i32, [_vp, _i32]),
+    "gcl_plan_plane_only": (_i32, [_vp, _vp, _i32]),
     "gcl_plan_touched_suffix": (_i32, [_vp]),
     "gcl_plan_set_touched_rows": (_i32, [_vp, _vp, _i64]),
     "gcl_plan_suffix_rows_used": (_i64, [_vp]),

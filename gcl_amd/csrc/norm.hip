@@ -443,7 +443,8 @@ __global__ void __launch_bounds__(256) k_bn_apply(const float* __restrict__ x, l
                                                   int* amax_bits, int y_ld = 0, unsigned short* __restrict__ planes = nullptr,
                                                   const int* __restrict__ planes_amax = nullptr) {
   // planes (round 5): the fp16 plane image of y is written in the same pass (row pitch = y's, y_ld or c channels), scaled
-  // by the slot `planes_amax` -- k_bn_stats_direct's bound of max|y|, final before this launch starts; no publication then
+  // by the slot `planes_amax` -- k_bn_stats_direct's bound of max|y|, final before this launch starts; no publication then.
+  // y == NULL (with planes only; the entry checks): every reader takes the image, the fp32 store alone is skipped
   const float pscale = planes ? amax_scale(planes_amax) : 1.f;
   const int cq_n = c >> 2;
   const long long S = (long long)gridDim.x * blockDim.x;
@@ -478,8 +479,8 @@ __global__ void __launch_bounds__(256) k_bn_apply(const float* __restrict__ x, l
     }
     const float4 oa = bn_fwd_one(xa, ra, residual != nullptr, relu, ka);
     const float4 ob = bn_fwd_one(xb, rb, residual != nullptr, relu, kb);
-    if (oka) { BN_Y(e, row_e) = oa; am = amax4(am, oa); }
-    if (okb) { BN_Y(f, row_e + rstep) = ob; am = amax4(am, ob); }
+    if (oka) { if (y) BN_Y(e, row_e) = oa; am = amax4(am, oa); }
+    if (okb) { if (y) BN_Y(f, row_e + rstep) = ob; am = amax4(am, ob); }
     if (planes) {
       const long long pld = yld4 * 4;
       if (oka) store_planes4(planes, HOIST ? row_e : e / cq_n, pld, HOIST ? q0 * 4 : (int)(e % cq_n) * 4, oa, pscale);
@@ -532,6 +533,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
                                                       const int* __restrict__ planes_amax = nullptr,
                                                       const int* __restrict__ slots = nullptr) {
   // planes: the fp16 plane image of dx in the same pass, scaled by k_bn_bwd_final's bound (slot `planes_amax`)
+  // dx == NULL (with planes only; the entries check): every reader takes the image, the fp32 store alone is skipped
   const float pscale = planes ? amax_scale(planes_amax) : 1.f;
   const int cq_n = c >> 2;
   const long long S = (long long)gridDim.x * blockDim.x;
@@ -585,13 +587,13 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const float* __restrict__ 
       relu_gate(gb, yb);
     }
     const float4 oa = bn_bwd_one(xa, ga, inv_n, ka);
-    reinterpret_cast<float4*>(dx)[e] = oa;
+    if (dx) reinterpret_cast<float4*>(dx)[e] = oa;
     am = amax4(am, oa);
     if (planes) store_planes4(planes, e / cq_n, c, (int)(e % cq_n) * 4, oa, pscale);
     BN_DRES(e, sa, ga)
     if (okb) {
       const float4 ob = bn_bwd_one(xb, gb, inv_n, kb);
-      reinterpret_cast<float4*>(dx)[f] = ob;
+      if (dx) reinterpret_cast<float4*>(dx)[f] = ob;
       am = amax4(am, ob);
       if (planes) store_planes4(planes, f / cq_n, c, (int)(f % cq_n) * 4, ob, pscale);
       BN_DRES(f, sb, gb)
@@ -754,7 +756,8 @@ int gcl_bn_apply_ld(const float* x, int64_t n, int32_t c, const float* mean, con
 int gcl_bn_apply_planes(const float* x, int64_t n, int32_t c, const float* mean, const float* rstd, const float* weight,
                         const float* bias, const float* residual, int32_t relu, float* y, int32_t y_ld, uint64_t* relu_mask,
                         int32_t* y_amax, void* planes, void* stream) {
-  GCL_CHECK_ARG(x && mean && rstd && weight && bias && y, "gcl_bn_apply: null pointer");
+  GCL_CHECK_ARG(x && mean && rstd && weight && bias, "gcl_bn_apply: null pointer");
+  GCL_CHECK_ARG(y || planes, "gcl_bn_apply_planes: y may be NULL only when a plane image is written in its place");
   GCL_CHECK_ARG(n > 0 && c >= 4 && c % 4 == 0, "gcl_bn_apply: unsupported shape");
   GCL_CHECK_ARG(y_ld == 0 || (y_ld >= c && y_ld % 4 == 0), "gcl_bn_apply_ld: y_ld must be 0 or a multiple of 4 >= c");
   GCL_CHECK_ARG(!planes || (y_amax && c % 32 == 0 && (y_ld % 32) == 0),
@@ -828,7 +831,8 @@ int gcl_bn_bwd_apply_planes(const float* x, const float* dy, int32_t dy_ld, cons
                             const float* sum_gx, int32_t relu, float* dx, float* dres, int32_t* dx_amax, void* planes,
                             void* stream) {
   GCL_CHECK_ARG(dy_ld == 0 || (dy_ld >= c && dy_ld % 4 == 0), "gcl_bn_bwd_apply: dy_ld must be 0 or a multiple of 4 >= c");
-  GCL_CHECK_ARG(x && dy && mean && rstd && weight && sum_g && sum_gx && dx, "gcl_bn_bwd_apply: null pointer");
+  GCL_CHECK_ARG(x && dy && mean && rstd && weight && sum_g && sum_gx, "gcl_bn_bwd_apply: null pointer");
+  GCL_CHECK_ARG(dx || planes, "gcl_bn_bwd_apply_planes: dx may be NULL only when a plane image is written in its place");
   GCL_CHECK_ARG(!relu || y || relu_mask, "gcl_bn_bwd_apply: y or relu_mask is required when relu is set");
   GCL_CHECK_ARG(n > 0 && c >= 4 && c % 4 == 0, "gcl_bn_bwd_apply: unsupported shape");
   GCL_CHECK_ARG(!planes || (dx_amax && c % 32 == 0),

@@ -542,7 +542,13 @@ struct TState {            // a tensor of the pass (forward value or gradient)
   void* planes = nullptr;    // gcl_split_planes image, or NULL = not made yet
   int ld = 0;                // row pitch in floats when the tensor is a column slice of a wider one (gradients of ME.cat
                              // inputs: slices of the gradient of the cat's output), 0 = its own channel count
+  bool plane_only = false;   // ptr is NULL on purpose: every reader takes `planes` (plane_only_analysis), no fp32 form exists
 };
+
+// in front of every launch that reads the fp32 form of a tensor: a reader the analysis overlooked ends here, on the host
+#define NEED_F32(ts, rec, what)                                                                                          \
+  GCL_CHECK_ARG(!(ts).plane_only, "gcl_plan: record %d reads %s in fp32, but the plan keeps that tensor as a plane image " \
+                                  "only (reader analysis of gcl_plan_create)", (int)(rec), what)
 
 struct OpSaved {           // what the backward pass of a record needs from its forward pass
   float* conv_out = nullptr;            // CONVBN: the convolution output (the BatchNorm input)
@@ -581,6 +587,7 @@ struct PassState {        // everything one forward pass leaves behind for its b
   // tensors of the suffix -- its input included -- and its saved operands are then compact [fwd_cap, c] tensors
   const int32_t* fwd_rows = nullptr;
   long long fwd_cap = 0;
+  bool keep_twins = false;          // Plan::keep_fp32 as it stood when the pass was sized: both passes of one arena agree
 };
 
 struct Plan : PassState {   // the base part is the pass being enqueued right now
@@ -599,6 +606,11 @@ struct Plan : PassState {   // the base part is the pass being enqueued right no
                                     // BatchNorm apply pass writes into the cat's output (row pitch = the cat's width)
   std::vector<int> mask_from;       // record i is a convolution whose input is the output of RELU record mask_from[i] and that
                                     // ReLU's only consumer: its input-gradient epilogue applies the ReLU's backward (-1: no)
+  // plane-only tensors (plane_only_analysis): record i is a CONVBN in bound mode whose output y (po_fwd) / whose BatchNorm
+  // input gradient dx (po_bwd) every reader takes as a plane image -- the apply pass writes no fp32 twin and the arena holds
+  // none.  keep_fp32 (gcl_plan_set_keep_fp32, tests): every twin is written, as if both vectors were all zero
+  std::vector<char> po_fwd, po_bwd;
+  bool keep_fp32 = false;
   // device tables (inside the caller's `state` buffer), re-uploaded when a parameter pointer changes
   std::vector<long long> host_tables, uploaded;
   // inference passes (gcl_plan_forward_eval): BatchNorm in eval mode folded into the convolution epilogue
@@ -636,17 +648,20 @@ static int32_t* new_slot(Plan& P) {      // slots are used once per pass (they s
   return P.slot_pool + (P.next_slot++) * GCL_AMAX_WORDS;
 }
 
-static int ensure_amax(Plan& P, TState& ts, long long numel, hipStream_t st) {
+// rec: the record on whose behalf the tensor is measured / split (error texts)
+static int ensure_amax(Plan& P, TState& ts, long long numel, hipStream_t st, int rec) {
   Arena& A = P.A;
   if (ts.amax) return GCL_OK;
+  NEED_F32(ts, rec, "a tensor whose max-abs slot is missing");
   ts.amax = new_slot(P);
   PLAN_CALL(gcl_amax(ts.ptr, numel, ts.amax, 1, (void*)st));
   return GCL_OK;
 }
 
-static int ensure_planes(Plan& P, TState& ts, long long n, int c, hipStream_t st) {
+static int ensure_planes(Plan& P, TState& ts, long long n, int c, hipStream_t st, int rec) {
   Arena& A = P.A;
   if (ts.planes) return GCL_OK;
+  NEED_F32(ts, rec, "a tensor whose plane image is missing");
   ts.planes = A.take(n * c * 4);
   PLAN_CALL(gcl_split_planes(ts.ptr, n, c, ts.amax, ts.planes, (void*)st));
   return GCL_OK;
@@ -743,6 +758,7 @@ static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStr
   *relu_amax_out = nullptr;
   const float* W = (const float*)P.params[op.w];
   if (is_stem(op, m)) {
+    NEED_F32(x, i, "its input (first layer)");
     int rcs = stem_flag(P, op, m, x, n_in, st);
     if (rcs) return rcs;
     PLAN_CALL(gcl_stem_fwd(x.ptr, W, m.nbr, n_out, op.K, op.cin, op.cout, y, m.presence, m.presence ? P.not_ones : nullptr,
@@ -754,11 +770,12 @@ static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStr
     GCL_CHECK_HIP(hipStreamWaitEvent(st, P.fwd_packs, 0));
     P.fwd_packs_pending = false;
   }
-  int rc = ensure_amax(P, x, n_in * op.cin, st);
+  int rc = ensure_amax(P, x, n_in * op.cin, st, i);
   if (rc) return rc;
   P.saved[i].x_amax = x.amax;
   const bool pl = op.cin >= P.presplit;
-  if (pl && (rc = ensure_planes(P, x, n_in, op.cin, st))) return rc;
+  if (pl && (rc = ensure_planes(P, x, n_in, op.cin, st, i))) return rc;
+  if (!pl) NEED_F32(x, i, "its input");
   float* stats = nullptr;
   if (op.kind == GCL_OP_CONVBN) stats = A.take_n<float>(cdiv(n_out, 128) * 4 * op.cout);      // sum, squares, min, max per column and 128-row tile
   *stats_out = stats;
@@ -895,6 +912,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
     const long long n_out = compact ? P.fwd_cap : M.n_rows[op.level_out];
     if (compact && (int)i == P.suffix_first) {
       TState& xs = P.t[op.x];
+      NEED_F32(xs, i, "the input of the touched-row suffix");
       float* cx = A.take_n<float>(P.fwd_cap * op.cin);
       PLAN_CALL(gcl_gather_rows(xs.ptr, xs.ld ? xs.ld : op.cin, M.n_rows[op.level_in], P.fwd_rows, P.fwd_cap, op.cin, 0.f, cx,
                                 (void*)st));
@@ -917,6 +935,8 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
           TState& x = P.t[op.x];
           const int c = op.cout;
           const float* res = op.x2 >= 0 ? P.t[op.x2].ptr : nullptr;
+          NEED_F32(x, i, "its input (inference)");      // (an inference pass keeps every tensor in fp32: never taken)
+          if (op.x2 >= 0) NEED_F32(P.t[op.x2], i, "its residual operand");
           y.ptr = A.take_n<float>(n_out * c);
           y.amax = new_slot(P);
           void* const* be = P.bn_eval ? P.bn_eval + 4 * op.bn : nullptr;
@@ -931,7 +951,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
             break;
           }
           const int wi = P.widx[op.w];
-          if ((rc = ensure_amax(P, x, n_in * op.cin, st))) return rc;
+          if ((rc = ensure_amax(P, x, n_in * op.cin, st, (int)i))) return rc;
           const SortedTable T = sorted_table(m, op.transpose);
           GCL_CHECK_ARG(A.dry || m.kernel_size == 1 || T.tbl,
                         "gcl_plan_forward_eval: record %d needs a sorted table the maps do not carry", (int)i);
@@ -990,12 +1010,15 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
           y.amax = cty.amax;
           y.planes = nullptr;      // the image belongs to the cat (this tensor's only consumer)
         } else {
-          y.ptr = A.take_n<float>(n_out * c);
+          // plane-only: every reader of y takes the image (plane_only_analysis) -- no fp32 block in the arena, no fp32 store
+          y.plane_only = bound && !P.keep_twins && P.po_fwd[i];
+          y.ptr = y.plane_only ? nullptr : A.take_n<float>(n_out * c);
           y.ld = 0;
           y.amax = bound ? bound_slot : new_slot(P);
           if (bound) y.planes = A.take(n_out * c * 4);
         }
         if (op.relu) sv.mask = A.take_n<unsigned long long>(gcl_bn_mask_len(n_out, c));
+        if (op.x2 >= 0) NEED_F32(P.t[op.x2], i, "its residual operand");
         const float* res = op.x2 >= 0 ? P.t[op.x2].ptr : nullptr;
         void* img = !bound ? nullptr : (P.cat_left[i] >= 0 ? P.t[P.ops[P.cat_left[i]].y].planes : y.planes);
         PLAN_CALL(gcl_bn_apply_planes(cy, n_out, c, sv.mean, sv.rstd, (const float*)P.params[op.bn_w],
@@ -1020,6 +1043,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
           break;
         }
         const long long n4 = n_out * op.cout / 4;
+        NEED_F32(P.t[op.x], i, "its input");
         y.ptr = A.take_n<float>(n_out * op.cout);
         y.amax = new_slot(P);        // published by the kernel itself: the consumer needs no gcl_amax pass
         if (!A.dry) {
@@ -1031,6 +1055,8 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
       }
       case GCL_OP_CAT: {
         const int ca = op.cin, cb = op.cout - op.cin;
+        NEED_F32(P.t[op.x], i, "its left input");
+        NEED_F32(P.t[op.x2], i, "its right input");
         if (P.t[op.x].ld == op.cout && P.t[op.x].ptr == y.ptr && y.ptr) {      // left input already in place (cat_left)
           if (!A.dry) {
             hipLaunchKernelGGL(k_cat_right, dim3(grid_for(n_out * cb / 4)), dim3(256), 0, st, (const float4*)P.t[op.x2].ptr,
@@ -1054,6 +1080,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
         break;
       }
       case GCL_OP_ROWNORM: {
+        NEED_F32(P.t[op.x], i, "its input");
         y.ptr = A.take_n<float>(n_out * op.cout);
         P.saved[i].norm = A.take_n<float>(n_out);
         PLAN_CALL(gcl_row_normalize_fwd(P.t[op.x].ptr, n_out, op.cout, y.ptr, P.saved[i].norm, (void*)st));
@@ -1065,6 +1092,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
     }
   }
   if (late_pending) GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));      // (the arena outlives the side stream's work)
+  NEED_F32(P.t[P.ops.back().y], P.ops.size() - 1, "its output (the caller's)");
   *y_out = P.t[P.ops.back().y].ptr;
   if (P.fwd_cap > 0) {      // the pass's output stays dense: the rows of the list hold the features, every other row is zero
     const gcl_plan_op& last = P.ops.back();      // ... and the padding rows of a saved y and norm become (0, 1)
@@ -1182,7 +1210,8 @@ static int saved_rows(Plan& P, RowView& V, const float* src, int ld, int c, floa
   *out = rows;
   return GCL_OK;
 }
-static int saved_rows(Plan& P, RowView& V, const TState& t, int c, hipStream_t st, const float** out) {
+static int saved_rows(Plan& P, RowView& V, const TState& t, int c, hipStream_t st, const float** out, int rec) {
+  if (V.cap > 0 && !V.parked) NEED_F32(t, rec, "a saved operand it gathers onto a row list");
   return saved_rows(P, V, t.ptr, t.ld ? t.ld : c, c, 0.f, st, out);
 }
 
@@ -1206,6 +1235,8 @@ static int conv_backward(Plan& P, int i, TState dy, RowView& V, void* const* gra
   float* dW = (float*)grads[op.w];
   int rc;
   if (is_stem(op, m)) {
+    NEED_F32(x, i, "its input (first layer)");
+    NEED_F32(dy, i, "its output gradient (first layer)");
     float* scratch = A.take_n<float>(gcl_stem_bwd_weight_scratch_len(op.K, op.cin, op.cout, n_out));
     hipStream_t ws = fork_aux(P, st);
     ProfScope ps(P, ws, 2, (double)m.n_pairs, op.cin, op.cout, n_in, n_out, op.K);
@@ -1214,20 +1245,26 @@ static int conv_backward(Plan& P, int i, TState dy, RowView& V, void* const* gra
     return GCL_OK;
   }
   const int wi = P.widx[op.w];
-  if ((rc = ensure_amax(P, dy, n_out * op.cout, st))) return rc;
+  if ((rc = ensure_amax(P, dy, n_out * op.cout, st, i))) return rc;
   const int32_t* w_amax = P.w_amax + (long long)wi * GCL_AMAX_WORDS;
   const double pairs = (double)(m.kernel_size > 1 ? m.n_pairs : n_out);
   // kernel_size 1: both operands of the weight gradient streamed once in fp32, no pair list (as ops._ConvFn.backward decides)
   const long long rows_len = m.kernel_size == 1 ? gcl_conv_bwd_weight_rows_scratch_len(op.cin, op.cout, 4, n_in) : 0;
   const bool pl_w = rows_len <= 0 && op.cin >= P.presplit && op.cout >= P.presplit;      // weight gradient on plane images
   const bool pl_x = op.cout >= P.presplit;                              // input gradient reads dy's plane image
-  if ((pl_w || (pl_x && P.made[op.x])) && (rc = ensure_planes(P, dy, n_out, op.cout, st))) return rc;
+  if ((pl_w || (pl_x && P.made[op.x])) && (rc = ensure_planes(P, dy, n_out, op.cout, st, i))) return rc;
   if (pl_w) {
     x.amax = P.saved[i].x_amax;
-    if ((rc = ensure_planes(P, x, n_in, op.cin, st))) return rc;
+    if ((rc = ensure_planes(P, x, n_in, op.cin, st, i))) return rc;
   }
+  // every launch below that takes the fp32 form of x or dy: a plane-only tensor has none
+  if (!pl_w) NEED_F32(x, i, "its input (weight gradient)");
+  if (!pl_w) NEED_F32(dy, i, "its output gradient (weight gradient)");
+  if (!pl_x && P.made[op.x]) NEED_F32(dy, i, "its output gradient (input gradient)");
+  if (P.made[op.x] && !P.g[op.x].ptr && P.mask_from[i] >= 0) NEED_F32(x, i, "its input (ReLU mask of the input-gradient epilogue)");
+  if (op.bias >= 0) NEED_F32(dy, i, "its output gradient (bias gradient)");
   const float* xr;      // the fp32 rows of x: what the row-stream weight gradient and a ReLU mask in the epilogue read
-  if ((rc = saved_rows(P, V, x, op.cin, st, &xr))) return rc;
+  if ((rc = saved_rows(P, V, x, op.cin, st, &xr, i))) return rc;
   // every operand of the weight gradient is enqueued: fork here, so that it runs beside the input gradient below
   hipStream_t ws = fork_aux(P, st);
   if (P.made[op.x]) {      // input gradient: the same output-stationary kernel over the opposite table
@@ -1327,8 +1364,14 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
       double* scratch = A.take_n<double>(gcl_bn_scratch_len(n_out, c));
       // bound mode: dx is read as a plane image by the input gradient (and by the weight gradient when both widths allow)
       const bool bound = sv.xrange && c >= P.presplit && !is_stem(op, M.maps[op.map]);
+      // plane-only: the input gradient and the weight gradient of this record both read dx as a plane image
+      // (plane_only_analysis) -- no fp32 block, no fp32 store.  The row-list apply pass keeps its fp32 dx: the analysis
+      // leaves out every record a compact gradient can reach
       TState d;
-      d.ptr = A.take_n<float>(n_out * c);
+      d.plane_only = bound && !P.keep_twins && P.po_bwd[i];
+      GCL_CHECK_ARG(!(d.plane_only && rv), "gcl_plan_backward: record %d: a compact gradient reached a BatchNorm whose input "
+                                           "gradient the plan keeps as a plane image only", i);
+      d.ptr = d.plane_only ? nullptr : A.take_n<float>(n_out * c);
       d.amax = new_slot(P);
       if (rv) {
         if ((rc = row_slots(P, *rv, st))) return rc;
@@ -1364,7 +1407,8 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
       }
       if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
       const float* y;
-      if ((rc = saved_rows(P, V, P.t[op.y], op.cout, st, &y))) return rc;
+      NEED_F32(P.t[op.y], i, "its saved output");
+      if ((rc = saved_rows(P, V, P.t[op.y], op.cout, st, &y, i))) return rc;
       const long long numel = n_out * op.cout;
       float* gx = A.take_n<float>(numel);
       int32_t* slot = new_slot(P);
@@ -1388,7 +1432,8 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
     case GCL_OP_ROWNORM: {
       if ((rc = contiguous(P, g, n_out, op.cout, st))) return rc;
       const float *y, *norm;
-      if ((rc = saved_rows(P, V, P.t[op.y], op.cout, st, &y))) return rc;
+      NEED_F32(P.t[op.y], i, "its saved output");
+      if ((rc = saved_rows(P, V, P.t[op.y], op.cout, st, &y, i))) return rc;
       if ((rc = saved_rows(P, V, P.saved[i].norm, 1, 1, 1.f, st, &norm))) return rc;
       float* dx = A.take_n<float>(n_in * op.cin);
       int32_t* slot = new_slot(P);
@@ -1512,6 +1557,64 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
   for (size_t t = 0; t < P.g.size(); ++t)
     if (P.g[t].rv && (rc = densify(P, P.g[t], tensor_width(P, (int)t), st))) return rc;
   return join_aux(P, st);      // the caller may hand the gradients of this segment to a collective / the optimizer next
+}
+
+// Reader analysis (gcl_plan_create): which tensors exist as a plane image only.  A CONVBN record in bound mode writes the
+// fp16 hi/lo image of its output y (forward apply pass) and of its BatchNorm input gradient dx (backward apply pass) beside
+// the fp32 tensor, the same number of bytes again.  The default is to keep the fp32 twin; it is dropped only when the record
+// can run in bound mode and EVERY reader provably takes the image:
+//   y  (po_fwd): each reader is a convolution record in front of the touched-row suffix with kernel size > 1 and both
+//                widths >= presplit -- its forward launch (cin >= presplit) and its pair-list weight gradient (pl_w) read
+//                x.planes.  Anything else keeps fp32: a residual operand or an ME.cat input (x2, the in-place cat_left
+//                case), a ReLU / row normalisation, a kernel_size-1 record (row-stream weight gradient), a narrow record
+//                (fp32 weight gradient), the ReLU-mask epilogue (mask_from), the first layer, the suffix (gathers fp32 rows),
+//                the plan's output (the caller's), a tensor nobody reads.
+//   dx (po_bwd): the tensor never leaves backward_record -- its readers are the record's own input gradient (cout >= presplit:
+//                the image) and weight gradient (the image iff pl_w: kernel size > 1, cin >= presplit), so it crosses no
+//                segment cut and reaches no give().  A bias gradient (gcl_col_sum) or the first layer would read fp32, and
+//                a record a compact gradient (TState::rv) can reach runs the row-list apply pass, which keeps its fp32 dx.
+// The passes re-check the run-time half (`bound`) and every fp32 read (NEED_F32): a reader this analysis overlooked is an
+// error return, not a null pointer in a kernel.
+static void plane_only_analysis(Plan& P) {
+  const int n_ops = (int)P.ops.size();
+  P.po_fwd.assign(n_ops, 0);
+  P.po_bwd.assign(n_ops, 0);
+  auto stem_shape = [](const gcl_plan_op& o) { return o.cin <= 4 && (o.cout % 32) == 0 && !o.transpose && o.K > 1 && o.bias < 0; };
+  auto conv = [](const gcl_plan_op& o) { return o.kind == GCL_OP_CONVBN || o.kind == GCL_OP_CONV; };
+  std::vector<int> maker(P.n_tensors, -1);
+  for (int i = 0; i < n_ops; ++i) maker[P.ops[i].y] = i;
+  // tensors whose gradient can arrive compact: the suffix's input, and from there the inputs of an ME.cat and the residual
+  // operand of a CONVBN that takes a compact gradient (its dres stays compact) -- backward_record's rows_ok
+  std::vector<char> may_rv(P.n_tensors, 0);
+  if (P.suffix_first < n_ops) may_rv[P.ops[P.suffix_first].x] = 1;
+  for (int i = n_ops - 1; i >= 0; --i) {
+    const gcl_plan_op& o = P.ops[i];
+    if (!may_rv[o.y]) continue;
+    if (o.kind == GCL_OP_CAT) may_rv[o.x] = may_rv[o.x2] = 1;
+    if (o.kind == GCL_OP_CONVBN && o.x2 >= 0) may_rv[o.x2] = 1;
+  }
+  for (int i = 0; i < n_ops && i < P.suffix_first; ++i) {
+    const gcl_plan_op& o = P.ops[i];
+    // bound mode as plan_forward decides it: column ranges from the MFMA epilogue, a wide output, the residual's slot known
+    bool bound = o.kind == GCL_OP_CONVBN && !stem_shape(o) && o.cout >= P.presplit && (o.cout % 32) == 0;
+    if (bound && o.x2 >= 0) {
+      const int k = maker[o.x2] >= 0 ? P.ops[maker[o.x2]].kind : 0;
+      bound = k == GCL_OP_CONVBN || k == GCL_OP_RELU || k == GCL_OP_CAT;      // producers that publish max|x2|
+    }
+    if (!bound) continue;
+    P.po_bwd[i] = o.K > 1 && o.cin >= P.presplit && o.bias < 0 && !may_rv[o.y];
+    bool ok = P.cat_left[i] < 0 && o.y != P.ops.back().y;
+    int readers = 0;
+    for (int j = 0; j < n_ops && ok; ++j) {
+      const gcl_plan_op& r = P.ops[j];
+      if (r.x2 == o.y) ok = false;
+      if (r.x != o.y) continue;
+      ++readers;
+      ok = ok && j < P.suffix_first && conv(r) && !stem_shape(r) && r.K > 1 && r.cin >= P.presplit && r.cout >= P.presplit &&
+           P.mask_from[j] < 0;
+    }
+    P.po_fwd[i] = ok && readers > 0;
+  }
 }
 
 static int check_maps(const Plan& P, const gcl_maps_desc* M) {
@@ -1753,6 +1856,7 @@ void* gcl_plan_create(const gcl_plan_op* ops_host, int32_t n_ops, int32_t n_tens
       ++P->n_bwd;
     }
   }
+  plane_only_analysis(*P);
   return P;
 }
 
@@ -1778,6 +1882,7 @@ int64_t gcl_plan_arena_bytes(void* plan, const gcl_maps_desc* maps_host) {
   if (!P || check_maps(*P, maps_host) != GCL_OK) return -1;
   P->maps = maps_host;
   P->params.assign(P->n_params, nullptr);
+  P->keep_twins = P->keep_fp32;
   long long need = 0;
   const int rc = dry_pass(*P, nullptr, nullptr, true, &need);
   P->forward_done = false;
@@ -1797,6 +1902,7 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
   P->state = state;
   P->A = Arena{(char*)arena, arena_bytes, 0, false};
   P->forward_done = false;
+  P->keep_twins = P->keep_fp32;      // parked with the pass: its backward pass follows the sizing made here
   // size check first (cheap dry run of both passes): never launch into an arena that cannot hold the pass
   long long need = 0;
   if ((rc = dry_pass(*P, x, bn_stats_host, true, &need))) return rc;
@@ -1964,6 +2070,24 @@ int gcl_plan_set_aux_stream(void* plan, void* stream) {
   GCL_CHECK_ARG(P, "gcl_plan_set_aux_stream: null plan");
   P->aux = (hipStream_t)stream;
   return GCL_OK;
+}
+
+int gcl_plan_set_keep_fp32(void* plan, int32_t keep) {
+  Plan* P = (Plan*)plan;
+  GCL_CHECK_ARG(P, "gcl_plan_set_keep_fp32: null plan");
+  P->keep_fp32 = keep != 0;
+  return GCL_OK;
+}
+
+int gcl_plan_plane_only(const void* plan, int32_t* flags_host, int32_t n_ops) {
+  const Plan* P = (const Plan*)plan;
+  GCL_CHECK_ARG(P && flags_host && n_ops == (int32_t)P->ops.size(), "gcl_plan_plane_only: flags_host must hold one word per record");
+  int n = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    flags_host[i] = P->keep_fp32 ? 0 : (P->po_fwd[i] ? 1 : 0) | (P->po_bwd[i] ? 2 : 0);
+    n += (flags_host[i] & 1) + (flags_host[i] >> 1);
+  }
+  return n;
 }
 
 int gcl_plan_touched_suffix(const void* plan) {

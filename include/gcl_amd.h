@@ -534,7 +534,10 @@ int gcl_bn_bwd_apply_ld(const float* x, const float* dy, int32_t dy_ld, const fl
  *             |dx| <= |w rstd| (max|g| + |sum_g| / n + max|xhat| |sum_gx| / n) goes to the zeroed slot dx_amax;
  *             gcl_bn_bwd_apply_planes writes dx's image at that scale.
  * A bound above the true maximum costs range at the bottom of the lo plane (which the range-extended format has to spare),
- * never correctness; consumers derive their scale from the same slot. */
+ * never correctness; consumers derive their scale from the same slot.
+ * With planes != NULL, gcl_bn_apply_planes takes y == NULL and gcl_bn_bwd_apply_planes takes dx == NULL: the fp32 store
+ * alone is skipped (nobody reads the fp32 twin), the image, the ReLU sign bits and dres are what they are with the
+ * pointer given.  A NULL y / dx without planes is GCL_ERR_ARG. */
 int gcl_bn_stats_from_tiles_range(const float* partial, int64_t n_tiles, int64_t n, int32_t c, float eps, float momentum,
                                   float* running_mean, float* running_var, float* mean, float* rstd, float* xrange,
                                   const float* weight, const float* bias, int32_t relu, const int32_t* add_amax,
@@ -1088,6 +1091,18 @@ int gcl_plan_release(void* plan, void* arena);
  * operands by events, while `stream` continues with the input-gradient chain; every gcl_plan_backward call ends with
  * `stream` waiting for them.  NULL (default) = everything on one stream.  Results do not depend on it. */
 int gcl_plan_set_aux_stream(void* plan, void* stream);
+/* Plane-only tensors.  A GCL_OP_CONVBN record whose output is at least presplit_min_c channels wide writes its output (forward)
+ * and its BatchNorm input gradient (backward) as an fp16 hi/lo plane image in the apply pass.  Where gcl_plan_create's reader
+ * analysis shows that every reader takes the image -- convolutions with kernel size > 1 and both widths >= presplit_min_c, in
+ * front of the touched-row suffix -- a training pass writes no fp32 twin of that tensor and reserves no arena for it; results
+ * are bitwise the same.  A residual operand, an ME.cat input, the plan's output, anything a narrow or kernel_size-1 record
+ * reads keeps fp32.  A launch that would read an fp32 form that does not exist returns GCL_ERR_ARG naming the record.
+ * gcl_plan_plane_only: flags_host[n_ops], bit 0 = record i's output, bit 1 = its BatchNorm input gradient is plane-only;
+ * returns how many tensors are (all words 0 while keep-fp32 is set), negative on a bad argument.
+ * gcl_plan_set_keep_fp32(keep != 0): every fp32 twin is written and sized again (for tests and comparisons); it takes
+ * effect with the next gcl_plan_arena_bytes / gcl_plan_forward call, and a backward pass follows its own forward pass. */
+int gcl_plan_set_keep_fp32(void* plan, int32_t keep);
+int gcl_plan_plane_only(const void* plan, int32_t* flags_host, int32_t n_ops);
 /* Touched rows.  The plan's touched-row suffix is the longest chain of row-local records -- GCL_OP_ROWNORM, GCL_OP_RELU,
  * kernel_size-1 GCL_OP_CONV -- that ends at the last record and whose input nothing else reads (ResUNetBN2C: conv1_tr, ReLU,
  * final, the row normalisation, behind the ME.cat); gcl_plan_touched_suffix returns its first record, or the number of records
