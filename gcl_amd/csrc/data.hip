@@ -101,6 +101,10 @@ __global__ void __launch_bounds__(256) k_colocation_hits(const float* __restrict
 #pragma unroll
   for (int wd = 0; wd < 3; ++wd)
   for (unsigned rest = keep[wd]; rest; rest &= rest - 1) {
+    // d2 = (ex ex + ey ey) + ez ez with every product rounded, as the oracle.  Plain operators with contraction switched off
+    // for the block: `__dmul_rn` / `__dadd_rn` fuse like plain operators under the default contraction, which changed the last
+    // bit of d2 and with it the order of points that the oracle sees as exactly equidistant
+#pragma clang fp contract(off)
     const int cand = sub + HITS_LANES * (32 * wd + __builtin_ctz(rest));
     const unsigned t = ((unsigned)cand * MW) >> 16, uz = (t * MW) >> 16;
     const int dz = (int)uz - R, dy = (int)(t - uz * W) - R, dx = (int)((unsigned)cand - t * W) - R;
@@ -109,10 +113,10 @@ __global__ void __launch_bounds__(256) k_colocation_hits(const float* __restrict
     long long s = table_find(table, cap, key);
     if (s < 0) continue;
     int q = (int)table[s].val;
-    double ex = __dsub_rn((double)xyz_cf[3 * (long long)q], px);
-    double ey = __dsub_rn((double)xyz_cf[3 * (long long)q + 1], py);
-    double ez = __dsub_rn((double)xyz_cf[3 * (long long)q + 2], pz);
-    double d2 = __dadd_rn(__dadd_rn(__dmul_rn(ex, ex), __dmul_rn(ey, ey)), __dmul_rn(ez, ez));
+    const double ex = (double)xyz_cf[3 * (long long)q] - px;
+    const double ey = (double)xyz_cf[3 * (long long)q + 1] - py;
+    const double ez = (double)xyz_cf[3 * (long long)q + 2] - pz;
+    const double d2 = (ex * ex + ey * ey) + ez * ez;
     if (!(d2 < r2)) continue;   // strictly inside, as a KD-tree query with distance_upper_bound
     // keep the K best, ascending (d2, row)
     if (n == K && !(d2 < bd[K - 1] || (d2 == bd[K - 1] && q < bi[K - 1]))) continue;
@@ -166,6 +170,7 @@ __global__ void __launch_bounds__(256) k_colocation_hits(const float* __restrict
   if (!live || sub != 0) return;
   cnt[o] = merged;
   double rng = 1e300;
+  // (the squares of float32 values are exact in fp64, so these sums are the same fused or not)
   if (c == 0) {
     double a = xyz_own[3 * ic], b = xyz_own[3 * ic + 1], d = xyz_own[3 * ic + 2];
     rng = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)), __dmul_rn(d, d)));   // centre voxel's sensor range
@@ -332,10 +337,16 @@ __global__ void k_loader_points(const float* __restrict__ xyz_raw, const long lo
   const float x = p[0], y = p[1], z = p[2];
   xyz_own[3 * i] = x; xyz_own[3 * i + 1] = y; xyz_own[3 * i + 2] = z;
   const double* m = to_center + 12 * cloud;
-  // (x m0 + y m1) + z m2, then + t: the order of a 3-term dot product followed by the broadcast add, no contraction
-  xyz_cf[3 * i] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, m[0]), __dmul_rn(y, m[1])), __dmul_rn(z, m[2])), m[3]);
-  xyz_cf[3 * i + 1] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, m[4]), __dmul_rn(y, m[5])), __dmul_rn(z, m[6])), m[7]);
-  xyz_cf[3 * i + 2] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, m[8]), __dmul_rn(y, m[9])), __dmul_rn(z, m[10])), m[11]);
+  // (x m0 + y m1) + z m2, then + t: the order of a 3-term dot product followed by the broadcast add, every product rounded.
+  // Plain operators with contraction switched off for the block: `__dmul_rn` / `__dadd_rn` fuse like plain operators under
+  // the default contraction, and where the three products cancel a fused product changes the float32 result's leading bits
+  {
+#pragma clang fp contract(off)
+    const double xd = x, yd = y, zd = z;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      xyz_cf[3 * i + k] = (float)(((xd * m[4 * k] + yd * m[4 * k + 1]) + zd * m[4 * k + 2]) + m[4 * k + 3]);
+  }
 }
 
 // ---- centroid of every cloud of the batch: fp64 sums of the fp32 points in an order that depends on nothing but the point's
