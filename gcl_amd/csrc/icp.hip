@@ -15,7 +15,7 @@
 //
 // Blocks of a finished pair return on reading `done`.  Every candidate position comes out of a binary search over the pair's
 // own key range and is used as a position in that range only; the row stored beside a point is compared and written, never
-// dereferenced.
+// dereferenced.  The search of k_icp_step has a TWIN in multiway.hip (k_info_step): a change to one belongs in both.
 #include "common.h"
 #include "fpgrid.h"
 #include "kabsch.h"

@@ -172,35 +172,21 @@ def icp_refine(src_keypts, tgt_keypts, pred_trans):
     return r.transformation.to(pred_trans.device).float()
 
 
-def refine_pair_poses(pairs, icp_voxel_size=0.05, max_distance=0.2, max_iteration=200):
-    """The batch form of the pair loaders' ``_get_icp``.  ``pairs``: 1 .. 32 dicts ``{"xyz0", "xyz1": raw float32 [P, 3]
-    host arrays, "M": 4 x 4, the odometry pose that moves xyz0 into xyz1's frame}``.  Both scans are downsampled to the first
-    point of every ``icp_voxel_size`` voxel (``sparse_quantize(xyz / voxel, return_index=True)``, the loader's device
-    voxeliser as ``build_pair_batch_gpu`` calls it), the selected xyz0 is registered onto the selected xyz1 from ``init = M``
-    -- the iterates of the reference's "move by M, start at the identity" -- and the answer is the reference's
-    ``M2 = M @ T_icp`` with ``T_icp = T_total inv(M)`` (its multiplication order is kept as it is): float64 [B, 4, 4] on the
-    host, ready to be a pair's ``"trans"``.  Host reads: the voxeliser's row counts, then the [B, 16] transformations."""
-    B = len(pairs)
-    if not 1 <= B <= 32:
-        raise ValueError("1 .. 32 pairs per call (64 clouds share the voxeliser's table)")
-    voxel = float(icp_voxel_size)
+def voxelise_clouds(clouds, voxel):
+    """The loader's device voxeliser over 1 .. 64 raw host clouds (float32 [P_c, 3]) in one pass: the first point of every
+    ``voxel`` voxel of every cloud (``sparse_quantize(xyz / voxel, return_index=True)``).  Returns (xyz float32 [P, 3] on the
+    device, whose first rows are the selected points cloud after cloud; starts: host list [n_clouds + 1] of the clouds'
+    first rows).  One host read: the row counts."""
+    n_clouds = len(clouds)
+    if not 1 <= n_clouds <= 64:
+        raise ValueError(f"1 .. 64 clouds per call (they share the voxeliser's table), got {n_clouds}")
+    clouds = [np.asarray(x, dtype=np.float32) for x in clouds]
+    for x in clouds:
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError(f"a cloud must be [P, 3], got {x.shape}")
+    voxel = float(voxel)
     if not (0.0 < voxel < 3.0e38):
-        raise ValueError(f"icp_voxel_size must be positive and finite, got {voxel}")
-    d = _distance(max_distance)
-    max_iteration, _, _ = _criteria(max_iteration, 1e-6, 1e-6)
-    clouds, Ms = [], []
-    for p in pairs:
-        for k in ("xyz0", "xyz1"):
-            x = np.asarray(p[k], dtype=np.float32)
-            if x.ndim != 2 or x.shape[1] != 3:
-                raise ValueError(f"{k} must be [P, 3], got {x.shape}")
-            clouds.append(x)
-        M = np.asarray(p["M"], dtype=np.float64)
-        if M.shape != (4, 4) or not np.isfinite(M).all():
-            raise ValueError("M must be a finite 4 x 4 matrix")
-        Ms.append(M)
-    Ms = np.stack(Ms)
-    n_clouds = 2 * B
+        raise ValueError(f"the voxel size must be positive and finite, got {voxel}")
     offs = np.zeros(n_clouds + 1, dtype=np.int64)
     offs[1:] = np.cumsum([len(c) for c in clouds])
     P = int(offs[-1])
@@ -244,6 +230,38 @@ def refine_pair_poses(pairs, icp_voxel_size=0.05, max_distance=0.2, max_iteratio
     for c in range(n_clouds - 1, -1, -1):                                    # a cloud without rows starts where the next does
         if starts[c] < 0:
             starts[c] = starts[c + 1]
+    return xyz, starts
+
+
+def refine_pair_poses(pairs, icp_voxel_size=0.05, max_distance=0.2, max_iteration=200):
+    """The batch form of the pair loaders' ``_get_icp``.  ``pairs``: 1 .. 32 dicts ``{"xyz0", "xyz1": raw float32 [P, 3]
+    host arrays, "M": 4 x 4, the odometry pose that moves xyz0 into xyz1's frame}``.  Both scans are downsampled to the first
+    point of every ``icp_voxel_size`` voxel (``sparse_quantize(xyz / voxel, return_index=True)``, the loader's device
+    voxeliser as ``build_pair_batch_gpu`` calls it), the selected xyz0 is registered onto the selected xyz1 from ``init = M``
+    -- the iterates of the reference's "move by M, start at the identity" -- and the answer is the reference's
+    ``M2 = M @ T_icp`` with ``T_icp = T_total inv(M)`` (its multiplication order is kept as it is): float64 [B, 4, 4] on the
+    host, ready to be a pair's ``"trans"``.  Host reads: the voxeliser's row counts, then the [B, 16] transformations."""
+    B = len(pairs)
+    if not 1 <= B <= 32:
+        raise ValueError("1 .. 32 pairs per call (64 clouds share the voxeliser's table)")
+    voxel = float(icp_voxel_size)
+    if not (0.0 < voxel < 3.0e38):
+        raise ValueError(f"icp_voxel_size must be positive and finite, got {voxel}")
+    d = _distance(max_distance)
+    max_iteration, _, _ = _criteria(max_iteration, 1e-6, 1e-6)
+    clouds, Ms = [], []
+    for p in pairs:
+        for k in ("xyz0", "xyz1"):
+            x = np.asarray(p[k], dtype=np.float32)
+            if x.ndim != 2 or x.shape[1] != 3:
+                raise ValueError(f"{k} must be [P, 3], got {x.shape}")
+            clouds.append(x)
+        M = np.asarray(p["M"], dtype=np.float64)
+        if M.shape != (4, 4) or not np.isfinite(M).all():
+            raise ValueError("M must be a finite 4 x 4 matrix")
+        Ms.append(M)
+    Ms = np.stack(Ms)
+    xyz, starts = voxelise_clouds(clouds, voxel)
     side = lambda k: torch.cat([xyz[starts[2 * b + k]:starts[2 * b + k + 1]] for b in range(B)])
     count = lambda k: np.concatenate([[0], np.cumsum([starts[2 * b + k + 1] - starts[2 * b + k] for b in range(B)])])
     r = registration_icp_batch(side(0), count(0), side(1), count(1), d, Ms, max_iteration)

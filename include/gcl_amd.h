@@ -1333,6 +1333,54 @@ int gcl_icp_register_batch(const float* xyz0, const int64_t* offsets0_host, cons
                            const double* init, int32_t max_iteration, double relative_fitness, double relative_rmse,
                            void* scratch, double* T, double* stats, int32_t* status, int32_t* corr, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Multiway registration (csrc/multiway.hip, csrc/posegraph.h): what lib/complement_data_loader.py:407-516 does with open3d
+ * after the pairwise ICPs, restated from open3d's published source (DESIGN.md "Multiway registration" holds the semantics).
+ * All arithmetic is fp64; nothing is read back, there are no atomics: a pair's matrix and a graph's result are bitwise the
+ * same alone, anywhere in a batch and on every run.
+ *
+ * gcl_info_matrix_batch: get_information_matrix_from_point_clouds for n_pairs pairs in the layout of
+ * gcl_icp_register_batch (xyz0 / xyz1, host and device offsets, the sorted keys and order of a gcl_fpfh_cell_keys grid built
+ * at THIS call's (float)max_correspondence_distance).  transformation: DEVICE double [n_pairs, 16].  The correspondence of
+ * source row i is the ICP's: the nearest target row of the same pair to p = T x_i with d2 <= distance^2, ties to the lowest
+ * row.  info (double [n_pairs, 36], row-major 6 x 6, rotation part first) = sum over the correspondences of G^T G, G's rows
+ * being (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1) of the TARGET point (x, y, z); info[5][5] is the number
+ * of correspondences.  An empty cloud or a pair without correspondences gives the zero matrix (all bits zero: the negated
+ * entries are formed as 0 - v).  Three launches.
+ * scratch: gcl_info_scratch_bytes(total0, total1, n_pairs) bytes (0 for arguments out of range).
+ *
+ * gcl_multiway_compose: the pose graphs of the reference's full_registration.  Graph g owns the nodes node_offsets[g] ..
+ * node_offsets[g + 1] - 1 (n of them, 1 .. 8) and the edges edge_offsets[g] .. (n (n - 1) / 2 of them: every pair s < t in
+ * the order s = 0 .. n - 1, t = s + 1 .. n - 1); offsets are DEVICE int32 [n_graphs + 1].  T_icp (double [total_edges, 16])
+ * are the pairs' transformations in that order.  Writes nodes (double [total_nodes, 16]: node 0 = I, node k =
+ * inverse(T_icp(k - 1, k) ... T_icp(0, 1)), the rigid inverse), edges (int32 [total_edges, 2]: s, t) and uncertain (int32
+ * [total_edges]: t != s + 1).  One thread per graph.
+ *
+ * gcl_posegraph_optimize_batch: global_optimization with GlobalOptimizationLevenbergMarquardt, one workgroup per graph (at
+ * most 8 nodes and 28 edges; the 48 x 48 system lives in LDS).  nodes / edges / edge_T / edge_info / uncertain as above
+ * (device; edge_info double [total_edges, 36]).  params: HOST double [12] = max_correspondence_distance,
+ * edge_prune_threshold, preference_loop_closure, reference_node, then the convergence criteria max_iteration (<= 1000),
+ * min_relative_increment, min_relative_residual_increment, min_right_term, min_residual, max_iteration_lm (<= 100),
+ * upper_scale_factor, lower_scale_factor.  Outputs: poses (double [total_nodes, 16]), confidence (double [total_edges]),
+ * kept (int32 [total_edges]), stats (double [n_graphs, 3]: linear solves of pass 1, of pass 2, the final residual) and
+ * status (int32 [n_graphs]): 0; 1: the line-process weight is 0 (no edge carries a correspondence); 2: a non-finite input;
+ * 3: a pivot of the L D L^T was not positive; for 1 .. 3 the input poses are returned, every edge kept at confidence 1.
+ * 4: the graph's structure is out of range (the caller validates it; nothing else is written for that graph).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t gcl_info_scratch_bytes(int64_t total0, int64_t total1, int32_t n_pairs);
+int gcl_info_matrix_batch(const float* xyz0, const int64_t* offsets0_host, const int64_t* offsets0, const float* xyz1,
+                          const int64_t* offsets1_host, const int64_t* offsets1, int32_t n_pairs, const int64_t* sorted_keys,
+                          const int64_t* order, const double* transformation, double max_correspondence_distance,
+                          void* scratch, double* info, void* stream);
+int gcl_multiway_compose(const int32_t* node_offsets, const int32_t* edge_offsets, int32_t n_graphs, int32_t total_nodes,
+                         int32_t total_edges, const double* T_icp, double* nodes, int32_t* edges, int32_t* uncertain,
+                         void* stream);
+int gcl_posegraph_optimize_batch(const double* nodes, const int32_t* node_offsets, const int32_t* edges,
+                                 const int32_t* edge_offsets, const double* edge_T, const double* edge_info,
+                                 const int32_t* uncertain, int32_t n_graphs, int32_t total_nodes, int32_t total_edges,
+                                 const double* params, double* poses, double* confidence, int32_t* kept, double* stats,
+                                 int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
