@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GCL_LIB_PATH", os.path.join(CSRC, "libgcl_hip.so"))   # override: diagnostic builds only
 SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip", "ransac.hip", "regstats.hip", "fpfh.hip",
-           "valpose.hip", "pairmatch.hip", "icp.hip", "instnorm.hip", "multiway.hip"]
+           "valpose.hip", "pairmatch.hip", "icp.hip", "instnorm.hip", "multiway.hip", "nghb.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gcl_amd.h")
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -257,12 +257,18 @@ SIGNATURES = {
     "gcl_multiway_compose": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gcl_posegraph_optimize_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_f64), _vp, _vp,
                                             _vp, _vp, _vp, _vp]),
+    "gcl_nghb_range_max": (_i32, [_vp, _i64, ctypes.POINTER(_i64), _i32, _vp, _vp, _vp, _vp]),
+    "gcl_nghb_flags": (_i32, [_vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp]),
+    "gcl_nghb_scratch_len": (_i64, [_i64]),
+    "gcl_nghb_compact": (_i32, [_vp, _vp, _i64, ctypes.POINTER(_i64), _i32, _vp, _vp, _vp, _vp]),
 }
 
 PAIR_CHUNK = 128   # GCL_PAIR_CHUNK
 TRIPLET_OUT = 20   # GCL_TRIPLET_OUT
 PAIR_SQ, PAIR_SQ_POS, PAIR_NEG, PAIR_DIST = 0, 1, 2, 3      # GCL_PAIR_*
 FPFH_MAX_NN, FPFH_MAX_CLOUDS, FPFH_BINS = 128, 32767, 33     # GCL_FPFH_*
+NGHB_MAX_SCANS = 256   # GCL_NGHB_MAX_SCANS
 
 _lib = None
 
@@ -287,7 +293,7 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into csrc/libgcl_hip.so (in-tree, so it travels to the GPU box)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kabsch.h"), os.path.join(CSRC, "fpgrid.h"),
-            os.path.join(CSRC, "posegraph.h"), HEADER]
+            os.path.join(CSRC, "posegraph.h"), os.path.join(CSRC, "loader.h"), HEADER]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH

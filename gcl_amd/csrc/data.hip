@@ -11,12 +11,11 @@
 // Integer / index work: results are compared bit-exactly with the CPU oracle (distances are evaluated in fp64 from the
 // same fp32 inputs and without fused multiply-add, like the oracle's KD-tree).
 #include "common.h"
+#include "loader.h"
 
 #include <limits.h>
 
 namespace gcl {
-
-__device__ __forceinline__ int floor_to_int(float v) { return (int)floorf(v); }
 
 __global__ void k_voxel_coords(const float* __restrict__ xyz, long long p, float voxel, int batch_id, int4* coords) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,61 +234,9 @@ __global__ void k_colocation_emit(const int* __restrict__ hits, const int* __res
 // through ONE coordinate table whose batch id is the cloud's number in the batch (lib/colocation_data_loader.py:440-446 gives
 // the clouds of a batch consecutive ids too), so that the loader makes two host synchronisations per batch instead of ~ 9 per
 // sample, and no host round trip for the neighbours' centre-frame points ---------------------------------------------------
-struct CloudOffsets {
-  long long off[65];      // point offsets of up to 64 clouds + the total
-};
-// ---- the loader's augmentation on the device: rotation about the cloud's centroid and the sample's scale, folded into the two
-// kernels that touch every point anyway (lib/colocation_data_loader.py:349-370, lib/data_loaders.py:476-492) ----------------
-// aug: double[n_clouds][12] from the host = R (9, row-major), the scale (1.0: none), rotated (0 / 1), one spare;
-// aff: double[n_clouds][12] = T_c = [R | R (-centroid)] from k_cloud_affines.
-// A cloud that is not rotated stays float32 in both of the reference's loaders: y = x * fp32(scale).  A rotated cloud is
-//   AUG_F32 (co-location loaders: apply_transform casts the transform to float32, colocation_data_loader.py:80-85):
-//           y = ((x0 r0 + x1 r1) + x2 r2) + t in fp32, y * fp32(scale), floor(y / fp32(voxel)), representative y;
-//   AUG_F64 (pair loaders keep float64 through sparse_quantize, data_loaders.py:125-129):
-//           the same expression in fp64, scale * y, floor(y / voxel) by fp64 division, representative fp32(y).
-// No product is contracted with a sum: the blocks below switch contraction off (`__fmul_rn` and its kin are plain operators
-// to this compiler and fuse like them).  AUG_NONE is the key-less path: y = x.
-enum { AUG_NONE = 0, AUG_F32 = 1, AUG_F64 = 2 };
-
-template <int MODE>
-__device__ __forceinline__ void loader_point(const float* __restrict__ p, int cloud, const double* __restrict__ aug,
-                                             const double* __restrict__ aff, float voxel, double voxel_d, float y[3], int v[3]) {
-  const float x0 = p[0], x1 = p[1], x2 = p[2];
-  if constexpr (MODE == AUG_NONE) {
-    y[0] = x0; y[1] = x1; y[2] = x2;
-    // floor(xyz / voxel_size) with the correctly rounded fp32 division numpy performs (util/misc.py:117)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = floor_to_int(__fdiv_rn(y[k], voxel));
-  } else {
-    const double scale = aug[12 * cloud + 9];
-    const bool rotated = aug[12 * cloud + 10] != 0.0;
-    const double* T = aff + 12 * cloud;
-    if (!rotated) {
-      y[0] = x0 * (float)scale; y[1] = x1 * (float)scale; y[2] = x2 * (float)scale;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] = floor_to_int(__fdiv_rn(y[k], voxel));
-    } else if constexpr (MODE == AUG_F32) {
-#pragma clang fp contract(off)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float r0 = (float)T[4 * k], r1 = (float)T[4 * k + 1], r2 = (float)T[4 * k + 2], t = (float)T[4 * k + 3];
-        const float q = ((x0 * r0 + x1 * r1) + x2 * r2) + t;
-        y[k] = q * (float)scale;
-        v[k] = floor_to_int(__fdiv_rn(y[k], voxel));
-      }
-    } else {
-#pragma clang fp contract(off)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double q = (((double)x0 * T[4 * k] + (double)x1 * T[4 * k + 1]) + (double)x2 * T[4 * k + 2]) + T[4 * k + 3];
-        const double yd = scale * q;
-        y[k] = (float)yd;
-        v[k] = (int)floor(yd / voxel_d);
-      }
-    }
-  }
-}
-
+// The loader's augmentation -- rotation about the cloud's centroid and the sample's scale -- is folded into the two kernels
+// that touch every point anyway: loader_point<MODE> (loader.h, with CloudOffsets and the aug / aff tables' layout; csrc/nghb.hip
+// applies the same arithmetic).  AUG_NONE is the key-less path: y = x.
 template <int MODE>
 __global__ void k_voxel_coords_multi(const float* __restrict__ xyz, long long p, CloudOffsets co, int n_clouds, float voxel,
                                      double voxel_d, const double* __restrict__ aug, const double* __restrict__ aff,
@@ -353,11 +300,6 @@ __global__ void k_loader_points(const float* __restrict__ xyz_raw, const long lo
 // position in ITS cloud -- chunks of CENT_CHUNK points from the cloud's first point on, 256 strided running sums per chunk and
 // a fixed LDS tree over them, then the same shape over the cloud's chunk sums.  No atomics: the centroid of a cloud is bitwise
 // the same alone, anywhere in any batch, and on every run.
-constexpr int CENT_CHUNK = 1024;
-struct CloudChunks {
-  long long off[65];      // point offsets, as CloudOffsets
-  int chunk0[65];         // first chunk of every cloud + the total
-};
 
 __device__ __forceinline__ void tree_sum3(double s[3], double (*sh)[256]) {
   const int t = threadIdx.x;

@@ -34,6 +34,22 @@ def draw_scale(pyrandom, min_scale, max_scale):
     return None
 
 
+def draw_complement_pair(randg, pyrandom, rotation_range, random_rotation, random_scale, min_scale, max_scale):
+    """The draws of one ``PairComplement*Dataset.__getitem__`` in the reference's order (lib/complement_data_loader.py:598-605,
+    :656-658; the nuScenes twin :1040-1044, :1089-1091): the T0 draws, then the T1 draws -- each ``sample_rotation``'s
+    ``rand(3)``, ``rand(1)`` from ``randg`` -- then the scale's one or two ``random()`` calls from ``pyrandom``.
+    ``rotation_range`` is passed on literally: the KITTI loader passes ``2 * np.pi`` under its hard-coded
+    ``test_augmentation`` (which also switches the rotation on, so pass ``random_rotation=True`` for it), ``np.pi / 4``
+    otherwise, as the nuScenes loader always does.  Without ``random_rotation`` / ``random_scale`` the respective generator
+    is not touched.  Returns ``{"rotation0", "rotation1", "scale"}`` (None: not drawn), the keys
+    ``build_complement_pair_batch_gpu`` reads."""
+    R0 = R1 = None
+    if random_rotation:
+        R0 = sample_rotation(randg, rotation_range)
+        R1 = sample_rotation(randg, rotation_range)
+    return {"rotation0": R0, "rotation1": R1, "scale": draw_scale(pyrandom, min_scale, max_scale) if random_scale else None}
+
+
 def checked_rotation(R, what="rotation"):
     """``R`` as a 3 x 3 fp64 array; ValueError unless max|R^T R - I| <= 1e-6."""
     R = np.asarray(R, dtype=np.float64)

@@ -21,6 +21,37 @@ from gcl_amd.lib.colocation_data_gpu import AUG_F64, _cap
 from gcl_amd.util.pointcloud import matches_on_device, pack_params
 
 
+def filled_starts(starts):
+    """``gcl_cloud_row_starts``' list with the -1 of a cloud without rows replaced: it starts where the next one does."""
+    starts = list(starts)
+    for c in range(len(starts) - 2, -1, -1):
+        if starts[c] < 0:
+            starts[c] = starts[c + 1]
+    return starts
+
+
+def sides_and_matches(xyz, coords, starts, B, trans, radii, table, cap, voxel_size, K):
+    """The tail the pair builders share.  ``xyz`` / ``coords``: the voxel representatives and coordinates of a table whose
+    clouds 2 b and 2 b + 1 are pair b's source and target (further clouds may follow them); ``starts``: their first rows.  The
+    table numbers the rows pair-major; the trainers want the sources and the targets apart, the batch id = the pair's number,
+    and the matches of the whole batch in one count and one emit (one host read: the totals).  Returns
+    ``(xyz0, xyz1, C0, C1, n0, n1, o0, o1, pairs, totals)``."""
+    dev = xyz.device
+    side = lambda t, k: torch.cat([t[starts[2 * b + k]:starts[2 * b + k + 1]] for b in range(B)])
+    xyz0, xyz1, C0, C1 = side(xyz, 0), side(xyz, 1), side(coords, 0), side(coords, 1)
+    C0[:, 0] >>= 1                                           # cloud id 2 b + k -> pair number b
+    C1[:, 0] >>= 1
+    n0 = [starts[2 * b + 1] - starts[2 * b] for b in range(B)]
+    n1 = [starts[2 * b + 2] - starts[2 * b + 1] for b in range(B)]
+    o0, o1 = np.concatenate([[0], np.cumsum(n0)]), np.concatenate([[0], np.cumsum(n1)])
+    ph, lay = pack_params(o0, o1, trans, radii, table_row0=[starts[2 * b + 1] for b in range(B)])
+    params = torch.empty(ph.numel(), dtype=torch.int64, device=dev)
+    params.copy_(ph, non_blocking=True)
+    pairs, totals, _ = matches_on_device(xyz0, xyz1, params, lay, B, table, cap, voxel_size, max(radii), K, cloud0=1,
+                                         cloud_stride=2, absolute=True)
+    return xyz0, xyz1, C0, C1, n0, n1, o0, o1, pairs, totals
+
+
 def build_pair_batch_gpu(raw_pairs, voxel_size, device, K=None, stream=None):
     """``raw_pairs``: list of ``{"xyz0", "xyz1": float32 [P, 3] host arrays (after the loader's rotation / scale), "trans":
     4 x 4 (cloud 0 -> cloud 1), "radius": the pair's matching radius (:486-490)}``.  Returns the dict of ``collate_pair_fn``
@@ -127,23 +158,9 @@ def build_pair_batch_gpu(raw_pairs, voxel_size, device, K=None, stream=None):
             d[head:head + tg].copy_(host[head:head + tg], non_blocking=True)
         if m[4]:
             raise ValueError(f"{m[4]} points outside the packable voxel range")
-        starts = m[8:8 + n_clouds + 1]
-        for c in range(n_clouds - 1, -1, -1):                    # a cloud without rows starts where the next one does
-            if starts[c] < 0:
-                starts[c] = starts[c + 1]
-        # the table numbers the rows of all 2 B clouds, pair-major; the trainers want the sources and the targets apart
-        side = lambda t, k: torch.cat([t[starts[2 * b + k]:starts[2 * b + k + 1]] for b in range(B)])
-        xyz0, xyz1, C0, C1 = side(xyz, 0), side(xyz, 1), side(coords, 0), side(coords, 1)
-        C0[:, 0] >>= 1                                           # cloud id 2 b + k -> pair number b
-        C1[:, 0] >>= 1
-        n0 = [starts[2 * b + 1] - starts[2 * b] for b in range(B)]
-        n1 = [starts[2 * b + 2] - starts[2 * b + 1] for b in range(B)]
-        o0, o1 = np.concatenate([[0], np.cumsum(n0)]), np.concatenate([[0], np.cumsum(n1)])
-        ph, lay = pack_params(o0, o1, trans, radii, table_row0=[starts[2 * b + 1] for b in range(B)])
-        params = torch.empty(ph.numel(), dtype=torch.int64, device=dev)
-        params.copy_(ph, non_blocking=True)
-        pairs, totals, _ = matches_on_device(xyz0, xyz1, params, lay, B, table, cap, voxel_size, max(radii), K, cloud0=1,
-                                             cloud_stride=2, absolute=True)          # host read 2: the match totals
+        starts = filled_starts(m[8:8 + n_clouds + 1])
+        xyz0, xyz1, C0, C1, n0, n1, o0, o1, pairs, totals = sides_and_matches(xyz, coords, starts, B, trans, radii, table, cap,
+                                                                              voxel_size, K)      # host read 2: the match totals
         keep = [b for b in range(B) if totals[b] > 0]
         if len(keep) == B:
             pcd0, pcd1, T_gt = xyz0, xyz1, T_all

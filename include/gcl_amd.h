@@ -1381,6 +1381,44 @@ int gcl_posegraph_optimize_batch(const double* nodes, const int32_t* node_offset
                                  const double* params, double* poses, double* confidence, int32_t* kept, double* stats,
                                  int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The complement pair loaders' neighbourhood cloud (PairComplementKittiDataset / PairComplementNuscenesDataset.__getitem__,
+ * lib/complement_data_loader.py:576-628, :1028-1060): for every SIDE of a batch (a pair's centre scan; n_sides <= 64, side
+ * 2 b + s of sample b) its complement scans are moved into the centre frame, cropped to the centre scan's range and
+ * concatenated in order.  All arithmetic is float32 with every product and sum rounded on its own, apply_transform's
+ * q = ((x0 r0 + x1 r1) + x2 r2) + t with the transform rounded to float32 first, the squared range (x^2 + y^2) + z^2.
+ *   aug_dev / aff_dev      the tables of gcl_cloud_affines, DEVICE double[>= n_sides][12]: only aug's `rotated` column and the
+ *                          T_s = [R | R (-centroid)] of a rotated side are read; the scale is NOT applied here (the reference
+ *                          crops before it scales, :623-628 before :656-662).
+ * gcl_nghb_range_max       max_dev float[n_clouds]: over cloud c of gcl_voxel_coords_multi's layout (cloud_offsets_host: HOST
+ *                          int64[n_clouds + 1]) the maximum of the squared range of f32(T_c) x, or of x where the cloud is not
+ *                          rotated; 0 for an empty cloud.  An LDS tree per 1024 points, then an integer atomic max on the bit
+ *                          pattern: the same bits alone, anywhere in a batch, on every run.  One memset, one launch.
+ * gcl_nghb_flags           one thread per complement point.  cmpl [pc, 3]: the raw complement scans of all sides, side after
+ *                          side; scan_offsets_host: HOST int64[n_scans + 1] point offsets; scan_side_host: HOST int32[n_scans],
+ *                          the side of every scan, not descending; n_scans <= GCL_NGHB_MAX_SCANS; scan_aff_dev: DEVICE
+ *                          double[n_scans][12], row-major 3 x 4, complement -> centre (list_M).  moved [pc, 3] = f32(M_k) x,
+ *                          moved again by f32(T_s) where side s is rotated (the second transform acts on the rounded result of
+ *                          the first); flags int32[pc] = 1 where the squared range of `moved` is strictly below max_dev[s].
+ *                          pc = 0 launches nothing.
+ * gcl_nghb_compact         out [kept, 3] = the flagged rows of `moved` in order (capacity pc rows); side_offsets_host: HOST
+ *                          int64[n_sides + 1] point offsets of the sides in cmpl; kept_dev: DEVICE int32[n_sides + 1] = kept
+ *                          points of every side, then their total.  scratch: int32[gcl_nghb_scratch_len(pc)] = pc +
+ *                          pc / 2048 + 64 (0 for pc <= 0).  One scan (gcl_exclusive_scan_i32) and one launch; pc = 0 zeroes
+ *                          kept_dev.
+ * Every entry returns GCL_ERR_ARG before anything is launched for a negative count, more than 64 clouds / sides, offsets that
+ * do not ascend from 0 to the point count, or a null pointer where the sizes need one.
+ * ---------------------------------------------------------------------------------------------- */
+#define GCL_NGHB_MAX_SCANS 256
+int gcl_nghb_range_max(const float* xyz, int64_t p, const int64_t* cloud_offsets_host, int32_t n_clouds, const double* aug_dev,
+                       const double* aff_dev, float* max_dev, void* stream);
+int gcl_nghb_flags(const float* cmpl, int64_t pc, const int64_t* scan_offsets_host, const int32_t* scan_side_host,
+                   int32_t n_scans, int32_t n_sides, const double* scan_aff_dev, const double* aug_dev, const double* aff_dev,
+                   const float* max_dev, float* moved, int32_t* flags, void* stream);
+int64_t gcl_nghb_scratch_len(int64_t pc);
+int gcl_nghb_compact(const float* moved, const int32_t* flags, int64_t pc, const int64_t* side_offsets_host, int32_t n_sides,
+                     int32_t* scratch, float* out, int32_t* kept_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
