@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GCL_LIB_PATH", os.path.join(CSRC, "libgcl_hip.so"))   # override: diagnostic builds only
 SOURCES = ["coords.hip", "conv.hip", "norm.hip", "loss.hip", "pairloss.hip", "data.hip", "sc2pcr.hip", "plan.hip", "match.hip", "ransac.hip", "regstats.hip", "fpfh.hip",
-           "valpose.hip", "pairmatch.hip", "icp.hip", "instnorm.hip", "multiway.hip", "nghb.hip"]
+           "valpose.hip", "pairmatch.hip", "icp.hip", "instnorm.hip", "multiway.hip", "nghb.hip", "ordered.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "gcl_amd.h")
 
 _vp, _i32, _i64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
@@ -235,6 +235,23 @@ SIGNATURES = {
     "gcl_pair_terms_fwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "gcl_pair_terms_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "gcl_group_loss_records": (_i64, [_i64, _i32, _i32]),
+    "gcl_group_loss_bwd_emit": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                       _vp]),
+    "gcl_circle_group_records": (_i64, [_i64, _i32, _i32]),
+    "gcl_circle_group_bwd_emit": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _i32, _vp]),
+    "gcl_neg_loss_records": (_i64, [_i32]),
+    "gcl_neg_loss_bwd_emit": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "gcl_triplet_records": (_i64, [_i32]),
+    "gcl_triplet_bwd_emit": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _i32, _vp]),
+    "gcl_pair_terms_records": (_i64, [_i32]),
+    "gcl_pair_terms_bwd_emit": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _i32, _vp]),
+    "gcl_ordered_row_sum_window": (_i32, []),
+    "gcl_ordered_row_sum_scratch_len": (_i64, [_i32, _i64]),
+    "gcl_ordered_row_sum": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp]),
     "gcl_fpfh_cell_keys": (_i32, [_vp, _i64, _vp, _i32, _f32, _vp, _vp]),
     "gcl_fpfh_neighbours": (_i32, [_vp, _i64, _vp, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
     "gcl_fpfh_normals": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
@@ -293,7 +310,7 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into csrc/libgcl_hip.so (in-tree, so it travels to the GPU box)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kabsch.h"), os.path.join(CSRC, "fpgrid.h"),
-            os.path.join(CSRC, "posegraph.h"), os.path.join(CSRC, "loader.h"), HEADER]
+            os.path.join(CSRC, "posegraph.h"), os.path.join(CSRC, "loader.h"), os.path.join(CSRC, "losssink.h"), HEADER]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH

@@ -6,6 +6,7 @@
 // mask; here each selected group is one wavefront (lane = channel), the pairwise distance + row minimum never
 // leaves registers/LDS, and the positive-pair mask is evaluated on the device from (index, group) directly.
 #include "common.h"
+#include "losssink.h"
 
 #include <limits.h>
 #include <math.h>
@@ -100,6 +101,9 @@ __global__ void __launch_bounds__(64) k_group_loss_fwd(const float* __restrict__
   }
 }
 
+// SINK (losssink.h): float atomics into dF, or records.  Record slots of wave s: rec_off[s] + (j - b) for member j, then
+// (GL_PAIR) the two drawn members ra, rb; rec_off = exclusive sums of the window lengths (k_group_rec_off).
+template <class SINK>
 __global__ void __launch_bounds__(64) k_group_loss_bwd(const float* __restrict__ f, int c,
                                                        const long long* __restrict__ index,
                                                        const long long* __restrict__ goff,
@@ -107,10 +111,13 @@ __global__ void __launch_bounds__(64) k_group_loss_bwd(const float* __restrict__
                                                        const long long* __restrict__ sel, float pos_thresh,
                                                        float finest_thresh, int flags, const int* __restrict__ pairpos,
                                                        const float* __restrict__ gpos,
-                                                       const float* __restrict__ gfin, float* df) {
+                                                       const float* __restrict__ gfin, const int* __restrict__ rec_off,
+                                                       SINK sink) {
   const int lane = threadIdx.x;
   const long long gi = sel[blockIdx.x];
   const long long b = goff[gi], e = goff[gi + 1];
+  long long slot = 0;
+  if constexpr (SINK::kRecords) slot = rec_off[blockIdx.x];
   const GroupStats g = group_stats(f, c, index, flag, b, e, lane);
   const int* pp = pairpos ? pairpos + 2 * blockIdx.x : nullptr;
   float posv, finv;
@@ -155,14 +162,14 @@ __global__ void __launch_bounds__(64) k_group_loss_bwd(const float* __restrict__
         if (j == g.tpos) gr -= fin_scale * dt;
       }
     }
-    if (lane < c && gr != 0.f) atomicAdd(&df[row * c + lane], gr);
+    if (lane < c) sink.put(0, slot + (j - b), row, c, lane, gr, true);
   }
   if ((flags & GL_PAIR) && gp != 0.f && lane < c) {
     const long long ra = index[b + pp[0]], rb = index[b + pp[1]];
     const float diff = f[ra * c + lane] - f[rb * c + lane];
     const float coef = gp * (sq ? 2.f : 1.f / posv);
-    atomicAdd(&df[ra * c + lane], coef * diff);
-    atomicAdd(&df[rb * c + lane], -coef * diff);
+    sink.put(0, slot + (e - b), ra, c, lane, coef * diff, false);
+    sink.put(0, slot + (e - b) + 1, rb, c, lane, -coef * diff, false);
   }
 }
 
@@ -238,7 +245,10 @@ __global__ void __launch_bounds__(64) k_circle_group_fwd(const float* __restrict
   }
 }
 
-// dF += gpos dpos/dF + gfin dfin/dF + (1/n) gmean (gradient arriving at the group's mean feature), float atomics
+// dF += gpos dpos/dF + gfin dfin/dF + (1/n) gmean (gradient arriving at the group's mean feature): float atomics, or
+// records (SINK, losssink.h) at rec_off[s] + (j - b) for member j, then the finest member's collected gt, then (GL_PAIR)
+// ra, rb
+template <class SINK>
 __global__ void __launch_bounds__(64) k_circle_group_bwd(const float* __restrict__ f, int c,
                                                          const long long* __restrict__ index,
                                                          const long long* __restrict__ goff,
@@ -247,10 +257,13 @@ __global__ void __launch_bounds__(64) k_circle_group_bwd(const float* __restrict
                                                          float finest_thresh, float S, int flags,
                                                          const int* __restrict__ pairpos,
                                                          const float* __restrict__ gpos, const float* __restrict__ gfin,
-                                                         const float* __restrict__ gmean, float* df) {
+                                                         const float* __restrict__ gmean,
+                                                         const int* __restrict__ rec_off, SINK sink) {
   const int lane = threadIdx.x;
   const long long gi = sel[blockIdx.x];
   const long long b = goff[gi], e = goff[gi + 1];
+  long long slot = 0;
+  if constexpr (SINK::kRecords) slot = rec_off[blockIdx.x];
   const GroupStats g = group_stats(f, c, index, flag, b, e, lane);
   const float gp = gpos[blockIdx.x], gf = gfin[blockIdx.x];
   const float gm = (gmean && lane < c) ? gmean[(long long)blockIdx.x * c + lane] * g.inv_n : 0.f;
@@ -296,9 +309,9 @@ __global__ void __launch_bounds__(64) k_circle_group_bwd(const float* __restrict
         if (!(flags & GL_BLOCK)) gt -= dfi;
       }
     }
-    if (lane < c && gr != 0.f) atomicAdd(&df[row * c + lane], gr);
+    if (lane < c) sink.put(0, slot + (j - b), row, c, lane, gr, true);
   }
-  if (lane < c && gt != 0.f) atomicAdd(&df[index[g.tpos] * c + lane], gt);
+  if (lane < c) sink.put(0, slot + (e - b), index[g.tpos], c, lane, gt, true);
   if ((flags & GL_PAIR) && gp != 0.f) {                  // wave-uniform
     const int* pp = pairpos + 2 * blockIdx.x;
     const long long ra = index[b + pp[0]], rb = index[b + pp[1]];
@@ -309,8 +322,8 @@ __global__ void __launch_bounds__(64) k_circle_group_bwd(const float* __restrict
     const float dist = sq ? d2 : sqrtf(d2 + 1e-7f);
     const float coef = gp * sigmoid_f(dist - pos_thresh) * (sq ? 2.f : 1.f / dist);
     if (lane < c) {
-      atomicAdd(&df[ra * c + lane], coef * diff);
-      atomicAdd(&df[rb * c + lane], -coef * diff);
+      sink.put(0, slot + (e - b) + 1, ra, c, lane, coef * diff, false);
+      sink.put(0, slot + (e - b) + 2, rb, c, lane, -coef * diff, false);
     }
   }
 }
@@ -785,13 +798,15 @@ __global__ void __launch_bounds__(256) k_neg_loss_fwd(const float* __restrict__ 
   }
 }
 
+// float atomics, or records (SINK, losssink.h) at 2 r (sel1[r]) and 2 r + 1 (sel2[arg[r]])
+template <class SINK>
 __global__ void __launch_bounds__(64) k_neg_loss_bwd(const float* __restrict__ f, int c,
                                                      const long long* __restrict__ sel1,
                                                      const long long* __restrict__ sel2,
                                                      const int* __restrict__ arg, const float* __restrict__ dmin,
                                                      const unsigned char* __restrict__ keep, float thresh,
                                                      const float* __restrict__ out, const float* __restrict__ gneg,
-                                                     float* df) {
+                                                     SINK sink) {
   const int r = blockIdx.x, lane = threadIdx.x;
   if (!keep[r] || lane >= c) return;
   float D = dmin[r];
@@ -799,8 +814,33 @@ __global__ void __launch_bounds__(64) k_neg_loss_bwd(const float* __restrict__ f
   long long ra = sel1[r], rb = sel2[arg[r]];
   float coef = gneg[0] * (-2.f * (thresh - D) / out[1]) / D;   // dL/dD * dD/d(d2) * 2 == ... * (a - b) / D
   float diff = f[ra * c + lane] - f[rb * c + lane];
-  atomicAdd(&df[ra * c + lane], coef * diff);
-  atomicAdd(&df[rb * c + lane], -coef * diff);
+  sink.put(0, 2ll * r, ra, c, lane, coef * diff, false);
+  sink.put(0, 2ll * r + 1, rb, c, lane, -coef * diff, false);
+}
+
+// rec_off[s] = the sum over t < s of (members of group sel[t] + extra), rec_off[n_sel] = the total: the record window of
+// every wave of an *_emit launch, made on the device (no host read).  One workgroup, chunks of 256 groups.
+__global__ void __launch_bounds__(256) k_group_rec_off(const long long* __restrict__ goff, const long long* __restrict__ sel,
+                                                       int n_sel, int extra, int* __restrict__ rec_off) {
+  __shared__ int part[256];
+  const int t = threadIdx.x;
+  int carry = 0;
+  for (int base = 0; base < n_sel; base += 256) {
+    const int i = base + t;
+    const int v = (i < n_sel) ? (int)(goff[sel[i] + 1] - goff[sel[i]]) + extra : 0;
+    part[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const int x = (t >= o) ? part[t - o] : 0;
+      __syncthreads();
+      part[t] += x;
+      __syncthreads();
+    }
+    if (i < n_sel) rec_off[i] = carry + part[t] - v;
+    carry += part[255];
+    __syncthreads();
+  }
+  if (t == 0) rec_off[n_sel] = carry;
 }
 
 
@@ -879,9 +919,41 @@ int gcl_group_loss_bwd(const float* f, int32_t c, const int64_t* index, const in
                 "gcl_group_loss_bwd: bad flags / pair positions missing");
   GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_group_loss_bwd: feature width must be <= 64 (got %d)", c);
   if (n_sel <= 0) return GCL_OK;
-  hipLaunchKernelGGL(k_group_loss_bwd, dim3(n_sel), dim3(64), 0, (hipStream_t)stream, f, c, (const long long*)index,
-                     (const long long*)goff, finest_flag, (const long long*)sel, pos_thresh, finest_thresh, flags,
-                     (flags & GL_PAIR) ? pairpos : nullptr, gpos, gfin, df);
+  hipLaunchKernelGGL(k_group_loss_bwd<AtomicSink>, dim3(n_sel), dim3(64), 0, (hipStream_t)stream, f, c,
+                     (const long long*)index, (const long long*)goff, finest_flag, (const long long*)sel, pos_thresh,
+                     finest_thresh, flags, (flags & GL_PAIR) ? pairpos : nullptr, gpos, gfin, (const int*)nullptr,
+                     AtomicSink{{df, nullptr}});
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_group_loss_records(int64_t n_members, int32_t n_sel, int32_t flags) {
+  if (n_members < 0 || n_sel <= 0) return 0;
+  return n_members + (int64_t)n_sel * ((flags & GL_PAIR) ? 2 : 0);
+}
+
+int gcl_group_loss_bwd_emit(const float* f, int32_t c, const int64_t* index, const int64_t* goff,
+                            const uint8_t* finest_flag, const int64_t* sel, int32_t n_sel, float pos_thresh,
+                            float finest_thresh, int32_t flags, const int32_t* pairpos, const float* gpos,
+                            const float* gfin, int32_t* rec_off, int32_t* rec_row, float* rec_val, int32_t n_rec,
+                            void* stream) {
+  GCL_CHECK_ARG(n_sel >= 0 && n_rec >= 0, "gcl_group_loss_bwd_emit: negative count (n_sel = %d, n_rec = %d)", n_sel, n_rec);
+  GCL_CHECK_ARG(flags >= 0 && flags < 16 && (!(flags & GL_PAIR) || pairpos),
+                "gcl_group_loss_bwd_emit: bad flags / pair positions missing");
+  GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_group_loss_bwd_emit: feature width must lie in 1 .. 64 (got %d)", c);
+  GCL_CHECK_ARG(n_rec == 0 || (rec_row && rec_val), "gcl_group_loss_bwd_emit: null pointer (rec_row / rec_val)");
+  GCL_CHECK_ARG(n_sel == 0 || (f && index && goff && finest_flag && sel && gpos && gfin && rec_off),
+                "gcl_group_loss_bwd_emit: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  rec_fill(rec_row, n_rec, st);
+  if (n_sel > 0) {
+    hipLaunchKernelGGL(k_group_rec_off, dim3(1), dim3(256), 0, st, (const long long*)goff, (const long long*)sel, n_sel,
+                       (flags & GL_PAIR) ? 2 : 0, rec_off);
+    hipLaunchKernelGGL(k_group_loss_bwd<RecordSink>, dim3(n_sel), dim3(64), 0, st, f, c, (const long long*)index,
+                       (const long long*)goff, finest_flag, (const long long*)sel, pos_thresh, finest_thresh, flags,
+                       (flags & GL_PAIR) ? pairpos : nullptr, gpos, gfin, (const int*)rec_off,
+                       RecordSink{{rec_row, nullptr}, {rec_val, nullptr}, (long long)n_rec});
+  }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -911,9 +983,41 @@ int gcl_circle_group_bwd(const float* f, int32_t c, const int64_t* index, const 
   GCL_CHECK_ARG(flags >= 0 && flags < 8 && (!(flags & GL_PAIR) || pairpos) && log_scale > 0,
                 "gcl_circle_group_bwd: bad flags / pair positions missing / log_scale");
   if (n_sel <= 0) return GCL_OK;
-  hipLaunchKernelGGL(k_circle_group_bwd, dim3(n_sel), dim3(64), 0, (hipStream_t)stream, f, c, (const long long*)index,
-                     (const long long*)goff, finest_flag, (const long long*)sel, pos_thresh, finest_thresh, log_scale,
-                     flags, pairpos, gpos, gfin, gmean, df);
+  hipLaunchKernelGGL(k_circle_group_bwd<AtomicSink>, dim3(n_sel), dim3(64), 0, (hipStream_t)stream, f, c,
+                     (const long long*)index, (const long long*)goff, finest_flag, (const long long*)sel, pos_thresh,
+                     finest_thresh, log_scale, flags, pairpos, gpos, gfin, gmean, (const int*)nullptr,
+                     AtomicSink{{df, nullptr}});
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_circle_group_records(int64_t n_members, int32_t n_sel, int32_t flags) {
+  if (n_members < 0 || n_sel <= 0) return 0;
+  return n_members + (int64_t)n_sel * ((flags & GL_PAIR) ? 3 : 1);
+}
+
+int gcl_circle_group_bwd_emit(const float* f, int32_t c, const int64_t* index, const int64_t* goff,
+                              const uint8_t* finest_flag, const int64_t* sel, int32_t n_sel, float pos_thresh,
+                              float finest_thresh, float log_scale, int32_t flags, const int32_t* pairpos,
+                              const float* gpos, const float* gfin, const float* gmean, int32_t* rec_off,
+                              int32_t* rec_row, float* rec_val, int32_t n_rec, void* stream) {
+  GCL_CHECK_ARG(n_sel >= 0 && n_rec >= 0, "gcl_circle_group_bwd_emit: negative count (n_sel = %d, n_rec = %d)", n_sel, n_rec);
+  GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_circle_group_bwd_emit: feature width must lie in 1 .. 64 (got %d)", c);
+  GCL_CHECK_ARG(flags >= 0 && flags < 8 && (!(flags & GL_PAIR) || pairpos) && log_scale > 0,
+                "gcl_circle_group_bwd_emit: bad flags / pair positions missing / log_scale");
+  GCL_CHECK_ARG(n_rec == 0 || (rec_row && rec_val), "gcl_circle_group_bwd_emit: null pointer (rec_row / rec_val)");
+  GCL_CHECK_ARG(n_sel == 0 || (f && index && goff && finest_flag && sel && gpos && gfin && rec_off),
+                "gcl_circle_group_bwd_emit: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  rec_fill(rec_row, n_rec, st);
+  if (n_sel > 0) {
+    hipLaunchKernelGGL(k_group_rec_off, dim3(1), dim3(256), 0, st, (const long long*)goff, (const long long*)sel, n_sel,
+                       (flags & GL_PAIR) ? 3 : 1, rec_off);
+    hipLaunchKernelGGL(k_circle_group_bwd<RecordSink>, dim3(n_sel), dim3(64), 0, st, f, c, (const long long*)index,
+                       (const long long*)goff, finest_flag, (const long long*)sel, pos_thresh, finest_thresh, log_scale,
+                       flags, pairpos, gpos, gfin, gmean, (const int*)rec_off,
+                       RecordSink{{rec_row, nullptr}, {rec_val, nullptr}, (long long)n_rec});
+  }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -1155,8 +1259,28 @@ int gcl_neg_loss_bwd(const float* f, int32_t c, const int64_t* sel1, const int64
                      const float* gneg, float* df, void* stream) {
   GCL_CHECK_ARG(f && sel1 && sel2 && arg && dmin && keep && out && gneg && df && m > 0, "gcl_neg_loss_bwd: bad argument");
   GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_neg_loss_bwd: feature width must be <= 64");
-  hipLaunchKernelGGL(k_neg_loss_bwd, dim3(m), dim3(64), 0, (hipStream_t)stream, f, c, (const long long*)sel1,
-                     (const long long*)sel2, arg, dmin, keep, thresh, out, gneg, df);
+  hipLaunchKernelGGL(k_neg_loss_bwd<AtomicSink>, dim3(m), dim3(64), 0, (hipStream_t)stream, f, c, (const long long*)sel1,
+                     (const long long*)sel2, arg, dmin, keep, thresh, out, gneg, AtomicSink{{df, nullptr}});
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_neg_loss_records(int32_t m) { return m > 0 ? 2 * (int64_t)m : 0; }
+
+int gcl_neg_loss_bwd_emit(const float* f, int32_t c, const int64_t* sel1, const int64_t* sel2, const int32_t* arg,
+                          const float* dmin, const uint8_t* keep, int32_t m, float thresh, const float* out,
+                          const float* gneg, int32_t* rec_row, float* rec_val, int32_t n_rec, void* stream) {
+  GCL_CHECK_ARG(m >= 0 && n_rec >= 0, "gcl_neg_loss_bwd_emit: negative count (m = %d, n_rec = %d)", m, n_rec);
+  GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_neg_loss_bwd_emit: feature width must lie in 1 .. 64 (got %d)", c);
+  GCL_CHECK_ARG(n_rec >= 2 * (int64_t)m, "gcl_neg_loss_bwd_emit: n_rec = %d is below gcl_neg_loss_records(m) = 2 m", n_rec);
+  GCL_CHECK_ARG(n_rec == 0 || (rec_row && rec_val), "gcl_neg_loss_bwd_emit: null pointer (rec_row / rec_val)");
+  GCL_CHECK_ARG(m == 0 || (f && sel1 && sel2 && arg && dmin && keep && out && gneg), "gcl_neg_loss_bwd_emit: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  rec_fill(rec_row, n_rec, st);
+  if (m > 0)
+    hipLaunchKernelGGL(k_neg_loss_bwd<RecordSink>, dim3(m), dim3(64), 0, st, f, c, (const long long*)sel1,
+                       (const long long*)sel2, arg, dmin, keep, thresh, out, gneg,
+                       RecordSink{{rec_row, nullptr}, {rec_val, nullptr}, (long long)n_rec});
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -5,13 +5,16 @@
 // these losses as 25 - 40 small torch launches around a device -> host copy of the arg-minima and np.isin on the CPU;
 // here the membership test is one hash-table probe on the device, every term of a loss is one launch and its mean a
 // second one (one workgroup, fp64 sums in a fixed tree: the value does not depend on the launch), and the backward pass
-// is one launch of float atomics into caller-zeroed buffers, like every other loss backward of this library.
+// is one launch of float atomics into caller-zeroed buffers, like every other loss backward of this library -- or, through
+// the *_emit entries, the same kernel writing contribution records for gcl_ordered_row_sum (losssink.h, ordered.hip).
 //
 // Layout of a row in a wave: a feature row of C <= 16 / 32 / 64 channels takes a quarter / half / whole wave (lane =
 // channel inside its sub-wave), so a wave works on 4 / 2 / 1 triplets at a time and the atomic instruction of the
 // backward pass covers whole 64 / 128-byte row segments.  Distances keep the (a - b)^2 form of lib/metrics.py:22-25.
 #include "common.h"
+#include "losssink.h"
 
+#include <limits.h>
 #include <math.h>
 
 namespace gcl {
@@ -182,14 +185,17 @@ __global__ void __launch_bounds__(256) k_triplet_reduce(const float* __restrict_
   }
 }
 
-template <int W>
+// SINK (losssink.h): float atomics into dF0 / dF1, or records.  TWO record lists, one per cloud, with the same slots
+// 3 t (anchor), 3 t + 1 (positive), 3 t + 2 (negative): a contribution stands in the list of the cloud it goes to, and the
+// slot of the other list keeps its -1.
+template <int W, class SINK>
 __global__ void __launch_bounds__(256) k_triplet_bwd(const float* __restrict__ f0, long long n0,
                                                      const float* __restrict__ f1, long long n1, int c,
                                                      const long long* __restrict__ ap, const long long* __restrict__ neg,
                                                      const unsigned char* __restrict__ tag,
                                                      const unsigned char* __restrict__ keep, int m,
                                                      const float* __restrict__ work, const float* __restrict__ out,
-                                                     const float* __restrict__ g, float* df0, float* df1) {
+                                                     const float* __restrict__ g, SINK sink) {
   constexpr int R = 64 / W;
   const int lane = threadIdx.x & 63, sub = lane / W, ch = lane % W, wave = threadIdx.x >> 6;
   const long long t = ((long long)blockIdx.x * 4 + wave) * R + sub;
@@ -201,11 +207,10 @@ __global__ void __launch_bounds__(256) k_triplet_bwd(const float* __restrict__ f
   const float gs = g[0] / out[1];
   const float a = r.fa[r.ra * c + ch], p = r.fo[r.rp * c + ch], n = r.fo[r.rn * c + ch];
   const float u = gs * (a - p) / work[(long long)m + t], v = gs * (a - n) / work[2ll * m + t];
-  float* da = (tag[t] & 1) ? df1 : df0;
-  float* d_o = (tag[t] & 1) ? df0 : df1;
-  atomicAdd(&da[r.ra * c + ch], u - v);
-  atomicAdd(&d_o[r.rp * c + ch], -u);
-  atomicAdd(&d_o[r.rn * c + ch], v);
+  const int da = tag[t] & 1, d_o = da ^ 1;             // the anchor's cloud, the other cloud
+  sink.put(da, 3 * t, r.ra, c, ch, u - v, false);
+  sink.put(d_o, 3 * t + 1, r.rp, c, ch, -u, false);
+  sink.put(d_o, 3 * t + 2, r.rn, c, ch, v, false);
 }
 
 // ---- pair terms -----------------------------------------------------------------------------------------------------
@@ -278,12 +283,13 @@ __global__ void __launch_bounds__(256) k_pair_reduce(const float* __restrict__ w
   }
 }
 
-template <int W>
+// SINK: as k_triplet_bwd; slot t of list 0 (row of F0) and of list 1 (row of F1)
+template <int W, class SINK>
 __global__ void __launch_bounds__(256) k_pair_bwd(const float* __restrict__ f0, long long n0, const float* __restrict__ f1,
                                                   long long n1, int c, const long long* __restrict__ pairs,
                                                   const unsigned char* __restrict__ keep, int m, int mode, float thresh,
                                                   float eps, const float* __restrict__ work, const float* __restrict__ out,
-                                                  const float* __restrict__ g, float* df0, float* df1) {
+                                                  const float* __restrict__ g, SINK sink) {
   constexpr int R = 64 / W;
   const int lane = threadIdx.x & 63, sub = lane / W, ch = lane % W, wave = threadIdx.x >> 6;
   const long long t = ((long long)blockIdx.x * 4 + wave) * R + sub;
@@ -303,8 +309,8 @@ __global__ void __launch_bounds__(256) k_pair_bwd(const float* __restrict__ f0, 
   }
   if (coef == 0.f) return;
   const float diff = f0[ra * c + ch] - f1[rb * c + ch];
-  atomicAdd(&df0[ra * c + ch], coef * diff);
-  atomicAdd(&df1[rb * c + ch], -coef * diff);
+  sink.put(0, t, ra, c, ch, coef * diff, false);
+  sink.put(1, t, rb, c, ch, -coef * diff, false);
 }
 
 static int sub_width(int c) { return c <= 16 ? 16 : (c <= 32 ? 32 : 64); }
@@ -319,6 +325,13 @@ using namespace gcl;
     if ((W) == 16) hipLaunchKernelGGL(KERNEL<16>, dim3(GRID), dim3(256), 0, ST, __VA_ARGS__);       \
     else if ((W) == 32) hipLaunchKernelGGL(KERNEL<32>, dim3(GRID), dim3(256), 0, ST, __VA_ARGS__);  \
     else hipLaunchKernelGGL(KERNEL<64>, dim3(GRID), dim3(256), 0, ST, __VA_ARGS__);                 \
+  } while (0)
+// the backward kernels: the sink is the second template argument
+#define PL_DISPATCH_SINK(KERNEL, SINK, W, GRID, ST, ...)                                                       \
+  do {                                                                                                         \
+    if ((W) == 16) hipLaunchKernelGGL((KERNEL<16, SINK>), dim3(GRID), dim3(256), 0, ST, __VA_ARGS__);          \
+    else if ((W) == 32) hipLaunchKernelGGL((KERNEL<32, SINK>), dim3(GRID), dim3(256), 0, ST, __VA_ARGS__);     \
+    else hipLaunchKernelGGL((KERNEL<64, SINK>), dim3(GRID), dim3(256), 0, ST, __VA_ARGS__);                    \
   } while (0)
 
 extern "C" {
@@ -381,8 +394,36 @@ int gcl_triplet_bwd(const float* f0, int64_t n0, const float* f1, int64_t n1, in
   GCL_CHECK_ARG(f0 && f1 && ap && neg && tag && work && out && g && df0 && df1, "gcl_triplet_bwd: null pointer");
   GCL_CHECK_ARG(n0 >= 0 && n1 >= 0, "gcl_triplet_bwd: negative row count");
   const int w = sub_width(c);
-  PL_DISPATCH(k_triplet_bwd, w, row_grid(m, w), (hipStream_t)stream, f0, (long long)n0, f1, (long long)n1, c,
-              (const long long*)ap, (const long long*)neg, tag, keep, m, work, out, g, df0, df1);
+  const AtomicSink sink{{df0, df1}};
+  PL_DISPATCH_SINK(k_triplet_bwd, AtomicSink, w, row_grid(m, w), (hipStream_t)stream, f0, (long long)n0, f1, (long long)n1,
+                   c, (const long long*)ap, (const long long*)neg, tag, keep, m, work, out, g, sink);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_triplet_records(int32_t m) { return m > 0 ? 3 * (int64_t)m : 0; }
+
+int gcl_triplet_bwd_emit(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* ap,
+                         const int64_t* neg, const uint8_t* tag, const uint8_t* keep, int32_t m, const float* work,
+                         const float* out, const float* g, int32_t* rec_row0, float* rec_val0, int32_t* rec_row1,
+                         float* rec_val1, int32_t n_rec, void* stream) {
+  GCL_CHECK_ARG(m >= 0 && n_rec >= 0, "gcl_triplet_bwd_emit: negative count (m = %d, n_rec = %d)", m, n_rec);
+  GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_triplet_bwd_emit: feature width must lie in 1 .. 64 (got %d)", c);
+  GCL_CHECK_ARG(n_rec >= 3 * (int64_t)m, "gcl_triplet_bwd_emit: n_rec = %d is below gcl_triplet_records(m) = 3 m", n_rec);
+  GCL_CHECK_ARG(n_rec == 0 || (rec_row0 && rec_val0 && rec_row1 && rec_val1),
+                "gcl_triplet_bwd_emit: null pointer (the record lists)");
+  GCL_CHECK_ARG(m == 0 || (f0 && f1 && ap && neg && tag && work && out && g), "gcl_triplet_bwd_emit: null pointer");
+  GCL_CHECK_ARG(n0 >= 0 && n1 >= 0 && n0 <= INT_MAX && n1 <= INT_MAX,
+                "gcl_triplet_bwd_emit: row counts must lie in 0 .. 2^31 - 1 (record rows are int32)");
+  hipStream_t st = (hipStream_t)stream;
+  rec_fill(rec_row0, n_rec, st);
+  rec_fill(rec_row1, n_rec, st);
+  if (m > 0) {
+    const int w = sub_width(c);
+    const RecordSink sink{{rec_row0, rec_row1}, {rec_val0, rec_val1}, (long long)n_rec};
+    PL_DISPATCH_SINK(k_triplet_bwd, RecordSink, w, row_grid(m, w), st, f0, (long long)n0, f1, (long long)n1, c,
+                     (const long long*)ap, (const long long*)neg, tag, keep, m, work, out, g, sink);
+  }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
@@ -417,8 +458,37 @@ int gcl_pair_terms_bwd(const float* f0, int64_t n0, const float* f1, int64_t n1,
   GCL_CHECK_ARG(f0 && f1 && pairs && work && out && g && df0 && df1, "gcl_pair_terms_bwd: null pointer");
   GCL_CHECK_ARG(n0 >= 0 && n1 >= 0 && eps >= 0.f, "gcl_pair_terms_bwd: negative row count / eps");
   const int w = sub_width(c);
-  PL_DISPATCH(k_pair_bwd, w, row_grid(m, w), (hipStream_t)stream, f0, (long long)n0, f1, (long long)n1, c,
-              (const long long*)pairs, keep, m, mode, thresh, eps, work, out, g, df0, df1);
+  const AtomicSink sink{{df0, df1}};
+  PL_DISPATCH_SINK(k_pair_bwd, AtomicSink, w, row_grid(m, w), (hipStream_t)stream, f0, (long long)n0, f1, (long long)n1, c,
+                   (const long long*)pairs, keep, m, mode, thresh, eps, work, out, g, sink);
+  GCL_CHECK_LAUNCH();
+  return GCL_OK;
+}
+
+int64_t gcl_pair_terms_records(int32_t m) { return m > 0 ? (int64_t)m : 0; }
+
+int gcl_pair_terms_bwd_emit(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* pairs,
+                            const uint8_t* keep, int32_t m, int32_t mode, float thresh, float eps, const float* work,
+                            const float* out, const float* g, int32_t* rec_row0, float* rec_val0, int32_t* rec_row1,
+                            float* rec_val1, int32_t n_rec, void* stream) {
+  GCL_CHECK_ARG(m >= 0 && n_rec >= 0, "gcl_pair_terms_bwd_emit: negative count (m = %d, n_rec = %d)", m, n_rec);
+  GCL_CHECK_ARG(c >= 1 && c <= 64, "gcl_pair_terms_bwd_emit: feature width must lie in 1 .. 64 (got %d)", c);
+  GCL_CHECK_ARG(mode >= PT_SQ && mode < PT_DIST, "gcl_pair_terms_bwd_emit: mode %d has no backward pass", mode);
+  GCL_CHECK_ARG(n_rec >= (int64_t)m, "gcl_pair_terms_bwd_emit: n_rec = %d is below gcl_pair_terms_records(m) = m", n_rec);
+  GCL_CHECK_ARG(n_rec == 0 || (rec_row0 && rec_val0 && rec_row1 && rec_val1),
+                "gcl_pair_terms_bwd_emit: null pointer (the record lists)");
+  GCL_CHECK_ARG(m == 0 || (f0 && f1 && pairs && work && out && g), "gcl_pair_terms_bwd_emit: null pointer");
+  GCL_CHECK_ARG(n0 >= 0 && n1 >= 0 && n0 <= INT_MAX && n1 <= INT_MAX && eps >= 0.f,
+                "gcl_pair_terms_bwd_emit: row counts must lie in 0 .. 2^31 - 1 (record rows are int32), eps >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  rec_fill(rec_row0, n_rec, st);
+  rec_fill(rec_row1, n_rec, st);
+  if (m > 0) {
+    const int w = sub_width(c);
+    const RecordSink sink{{rec_row0, rec_row1}, {rec_val0, rec_val1}, (long long)n_rec};
+    PL_DISPATCH_SINK(k_pair_bwd, RecordSink, w, row_grid(m, w), st, f0, (long long)n0, f1, (long long)n1, c,
+                     (const long long*)pairs, keep, m, mode, thresh, eps, work, out, g, sink);
+  }
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }

@@ -21,6 +21,7 @@ from torch.autograd.function import once_differentiable
 
 import gcl_amd.MinkowskiEngine as ME
 from gcl_amd import _lib
+from gcl_amd.lib import ordered
 from gcl_amd.model import load_model
 
 # defaults = config.py of the reference overridden by scripts/train_gcl_kitti.sh
@@ -33,6 +34,9 @@ DEFAULT_CONFIG = dict(
     square_loss=True, block_finest_gradient=False, use_hard_negative=True, use_pair_group_positive_loss=False,
     use_group_circle_loss=False, safe_radius=0.75, voxel_size=0.3,
     triplet_num_pos=256, triplet_num_hn=512, triplet_num_rand=1024,      # config.py:71-73 (the pair trainers, lib/trainer.py)
+    # opt-in: the loss backward writes contribution records and adds them row by row in a fixed order instead of scattering
+    # float atomics (gcl_amd/lib/ordered.py): two runs of the same steps are then bitwise identical
+    deterministic_loss_backward=False,
 )
 
 
@@ -54,7 +58,9 @@ class _GCLLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, F, index, goff, flag, sel, sel1, sel2, pos_thresh, fin_thresh, neg_thresh, flags=0,
-                pairpos=None):
+                pairpos=None, rec_members=None):
+        """``rec_members``: None = the backward pass scatters float atomics; else a host-known bound of the sum of the
+        selected groups' sizes (``ordered.members_bound``), and the backward pass runs emit -> ordered row sum."""
         lib = _lib.require_gpu()
         F = F.contiguous()
         n, c = F.shape
@@ -88,13 +94,14 @@ class _GCLLossFn(torch.autograd.Function):
                    "gcl_neg_loss_fwd")
         ctx.save_for_backward(F, index, goff, flag, sel, sel1, sel2, dmin, arg, keep, out, pairpos)
         ctx.th = (pos_thresh, fin_thresh, neg_thresh, int(flags))
+        ctx.rec_members = rec_members
         ctx.touched = _TOUCHED_REQUEST
         return pos, fin, out[0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gpos, gfin, gneg):
-        return (_GCLLossFn.backward_terms(ctx, gpos, gfin, gneg),) + (None,) * 11
+        return (_GCLLossFn.backward_terms(ctx, gpos, gfin, gneg),) + (None,) * 12
 
     @staticmethod
     def backward_terms(ctx, gpos, gfin, gneg):
@@ -108,14 +115,31 @@ class _GCLLossFn(torch.autograd.Function):
         # gave its block to the next temporary -- gpos and gfin (expanded tensors out of sum()'s backward) then shared one
         # address and the kernel read gfin for both, unnoticed while pos_weight == finest_weight (every test, the defaults)
         gpos_c, gfin_c = gpos.contiguous(), gfin.contiguous()
-        _lib.check(lib.gcl_group_loss_bwd(_lib.ptr(F), c, _lib.ptr(index), _lib.ptr(goff), _lib.ptr(flag),
-                                          _lib.ptr(sel), sel.shape[0], pos_thresh, fin_thresh, flags,
-                                          _lib.ptr(pairpos), _lib.ptr(gpos_c), _lib.ptr(gfin_c), _lib.ptr(dF), st),
-                   "gcl_group_loss_bwd")
         g = gneg.reshape(1).contiguous()
-        _lib.check(lib.gcl_neg_loss_bwd(_lib.ptr(F), c, _lib.ptr(sel1), _lib.ptr(sel2), _lib.ptr(arg), _lib.ptr(dmin),
-                                        _lib.ptr(keep), sel1.shape[0], neg_thresh, _lib.ptr(out), _lib.ptr(g),
-                                        _lib.ptr(dF), st), "gcl_neg_loss_bwd")
+        if ctx.rec_members is not None:
+            # ONE record list for both entries, the group loss's window first (call order), then ONE ordered sum into dF
+            n_sel, m = sel.shape[0], sel1.shape[0]
+            cap_g = int(lib.gcl_group_loss_records(int(ctx.rec_members), n_sel, flags))
+            cap_n = int(lib.gcl_neg_loss_records(m))
+            rec_row, rec_val = ordered.records(cap_g + cap_n, c, F.device)
+            rec_off = torch.empty(n_sel + 1, dtype=torch.int32, device=F.device)
+            row_n, val_n = rec_row[cap_g:], rec_val[cap_g:]
+            _lib.check(lib.gcl_group_loss_bwd_emit(_lib.ptr(F), c, _lib.ptr(index), _lib.ptr(goff), _lib.ptr(flag),
+                                                   _lib.ptr(sel), n_sel, pos_thresh, fin_thresh, flags, _lib.ptr(pairpos),
+                                                   _lib.ptr(gpos_c), _lib.ptr(gfin_c), _lib.ptr(rec_off), _lib.ptr(rec_row),
+                                                   _lib.ptr(rec_val), cap_g, st), "gcl_group_loss_bwd_emit")
+            _lib.check(lib.gcl_neg_loss_bwd_emit(_lib.ptr(F), c, _lib.ptr(sel1), _lib.ptr(sel2), _lib.ptr(arg),
+                                                 _lib.ptr(dmin), _lib.ptr(keep), m, neg_thresh, _lib.ptr(out), _lib.ptr(g),
+                                                 _lib.ptr(row_n), _lib.ptr(val_n), cap_n, st), "gcl_neg_loss_bwd_emit")
+            ordered.ordered_row_sum(rec_row, rec_val, dF)
+        else:
+            _lib.check(lib.gcl_group_loss_bwd(_lib.ptr(F), c, _lib.ptr(index), _lib.ptr(goff), _lib.ptr(flag),
+                                              _lib.ptr(sel), sel.shape[0], pos_thresh, fin_thresh, flags,
+                                              _lib.ptr(pairpos), _lib.ptr(gpos_c), _lib.ptr(gfin_c), _lib.ptr(dF), st),
+                       "gcl_group_loss_bwd")
+            _lib.check(lib.gcl_neg_loss_bwd(_lib.ptr(F), c, _lib.ptr(sel1), _lib.ptr(sel2), _lib.ptr(arg), _lib.ptr(dmin),
+                                            _lib.ptr(keep), sel1.shape[0], neg_thresh, _lib.ptr(out), _lib.ptr(g),
+                                            _lib.ptr(dF), st), "gcl_neg_loss_bwd")
         req, ctx.touched = getattr(ctx, "touched", None), None
         if req is not None:        # every row written above: members of the selected groups, sel1, sel2[arg] (a subset of sel2)
             req[0].touch_loss_rows(index, goff, sel, sel1, sel2, n, req[1])
@@ -131,10 +155,10 @@ class _GCLTotalLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, F, index, goff, flag, sel, sel1, sel2, pos_thresh, fin_thresh, neg_thresh, flags, pairpos,
-                w_pos, w_fin, w_neg):
+                w_pos, w_fin, w_neg, rec_members=None):
         lib = _lib.require_gpu()
         pos, fin, neg = _GCLLossFn.forward(ctx, F, index, goff, flag, sel, sel1, sel2, pos_thresh, fin_thresh, neg_thresh,
-                                           flags, pairpos)
+                                           flags, pairpos, rec_members)
         out = torch.empty(4, dtype=torch.float32, device=F.device)
         _lib.check(lib.gcl_loss_combine(_lib.ptr(pos), _lib.ptr(fin), pos.shape[0], _lib.ptr(neg), float(w_pos),
                                         float(w_fin), float(w_neg), _lib.ptr(out), _lib.stream()), "gcl_loss_combine")
@@ -154,10 +178,14 @@ class _GCLTotalLossFn(torch.autograd.Function):
         _lib.check(lib.gcl_loss_seed(_lib.ptr(g), ctx.w[0], ctx.w[1], ctx.w[2], n_sel, _lib.ptr(seeds),
                                      _lib.ptr(seeds[n_sel:]), _lib.ptr(seeds[2 * n_sel:]), _lib.stream()), "gcl_loss_seed")
         dF = _GCLLossFn.backward_terms(ctx, seeds[:n_sel], seeds[n_sel:2 * n_sel], seeds[2 * n_sel:])
-        return (dF,) + (None,) * 14
+        return (dF,) + (None,) * 15
 
 
 LOSS_SQRT, LOSS_BLOCK, LOSS_PAIR, LOSS_NOFIN = 1, 2, 4, 8      # GCL_LOSS_* of include/gcl_amd.h
+
+RANDOM_NEG_NOT_DETERMINISTIC = (
+    "deterministic_loss_backward cannot be combined with use_hard_negative=False: that negative term (_RandomNegFn) is a "
+    "debug path of torch operators whose backward pass ends in index_add_ (float atomics); it has no ordered form")
 
 
 # Serialises every use of numpy's GLOBAL RandomState by the trainer's threads: legacy_choice holds it from get_state to
@@ -229,7 +257,7 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
                             points=None, batch_lengths=None, pos_thresh=0.1, neg_thresh=1.4, finest_thresh=0.2,
                             draws=None, square_loss=True, block_finest_gradient=False,
                             use_pair_group_positive_loss=False, use_hard_negative=True, finest_term=True,
-                            prepared=None, total_weights=None, selections=None):
+                            prepared=None, total_weights=None, selections=None, deterministic_loss_backward=False):
     """(pos_loss, finest_loss, neg_loss) of lib/colocation_trainer.py:430-535 with its four config switches
     (defaults = scripts/train_gcl_kitti.sh:96-105).  ``finest_term=False`` gives ``location_contrastive_loss``
     (:734-809) when combined with ``square_loss=False``.
@@ -244,6 +272,10 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
     hard negatives): returns ``(total, pos, fin, neg)`` from one autograd node instead -- same values, the scalar arithmetic
     in one launch each way; only ``total`` carries a gradient.  ``selections``: the device tensor ``upload_selections`` made of
     ``draws[:3]`` earlier in the step (the trainer builds the network's touched-row list from it before the forward pass).
+    ``deterministic_loss_backward``: the backward pass writes contribution records and adds them in a fixed order instead
+    of scattering float atomics (``gcl_amd/lib/ordered.py``): the same dF bit for bit on every run.  The record list is
+    sized from the selected groups' sizes, so pass ``group`` as a host tensor where you can.  Not offered with
+    ``use_hard_negative=False``, whose negative term is a debug path of torch operators ending in ``index_add_``.
     """
     dev = F_out.device
     n_out = F_out.shape[0]
@@ -256,6 +288,8 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
     pos_sel, sel_hn1, sel_hn2 = draws[:3]
     pair_pos = draws[3] if len(draws) > 3 else None
     rand_cols = draws[4] if len(draws) > 4 else None
+    if deterministic_loss_backward and not use_hard_negative:
+        raise ValueError(RANDOM_NEG_NOT_DETERMINISTIC)
     if not use_hard_negative and rand_cols is None:
         raise ValueError("use_hard_negative=False needs the drawn columns (draws[4])")
     if use_pair_group_positive_loss and pair_pos is None:
@@ -269,15 +303,16 @@ def finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_po
         torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev, non_blocking=True)
     n_pos, n_hn = len(pos_sel), len(sel_hn1)
     sel_all = selections if selections is not None else upload_selections(pos_sel, sel_hn1, sel_hn2, dev)
+    rec_members = ordered.members_bound(group, pos_sel, index) if deterministic_loss_backward else None
     if total_weights is not None and use_hard_negative:
         # the trainer's step: (total, pos, fin, neg) from one autograd node (``_GCLTotalLossFn``); only total has a gradient
         return _GCLTotalLossFn.apply(F_out, index, goff, flag, sel_all[:n_pos], sel_all[n_pos:n_pos + n_hn],
                                      sel_all[n_pos + n_hn:], float(pos_thresh), float(finest_thresh), float(neg_thresh),
                                      flags, to_dev32(pair_pos) if use_pair_group_positive_loss else None,
-                                     *[float(w) for w in total_weights])
+                                     *[float(w) for w in total_weights], rec_members)
     pos, fin, neg = _GCLLossFn.apply(F_out, index, goff, flag, sel_all[:n_pos], sel_all[n_pos:n_pos + n_hn],
                                      sel_all[n_pos + n_hn:], float(pos_thresh), float(finest_thresh), float(neg_thresh),
-                                     flags, to_dev32(pair_pos) if use_pair_group_positive_loss else None)
+                                     flags, to_dev32(pair_pos) if use_pair_group_positive_loss else None, rec_members)
     if not use_hard_negative:
         neg = random_negative_term(F_out, sel_all[n_pos:n_pos + n_hn], sel_all[n_pos + n_hn:], rand_cols, group, index,
                                    index_hash, float(neg_thresh))
@@ -368,21 +403,23 @@ def random_negative_term(F_out, sel1, sel2, cols, group, index, index_hash, neg_
 
 def location_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster=256, max_hn_samples=2048,
                               points=None, batch_lengths=None, pos_thresh=0.1, neg_thresh=1.4, draws=None,
-                              use_pair_group_positive_loss=False, use_hard_negative=True):
+                              use_pair_group_positive_loss=False, use_hard_negative=True,
+                              deterministic_loss_backward=False):
     """lib/colocation_trainer.py:734-809 (the trainer's loss when finest_weight == 0): non-squared positive term, no
     finest term (returned as 0), the same negative term."""
     return finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
                                    points, batch_lengths, pos_thresh, neg_thresh, 0.0, draws, square_loss=False,
                                    block_finest_gradient=False,
                                    use_pair_group_positive_loss=use_pair_group_positive_loss,
-                                   use_hard_negative=use_hard_negative, finest_term=False)
+                                   use_hard_negative=use_hard_negative, finest_term=False,
+                                   deterministic_loss_backward=deterministic_loss_backward)
 
 
 class _CircleGroupFn(torch.autograd.Function):
     """Per-group terms of location_circle_loss and the groups' mean features (gcl_circle_group_fwd / _bwd)."""
 
     @staticmethod
-    def forward(ctx, F, index, goff, flag, sel, pos_thresh, fin_thresh, log_scale, flags, pairpos):
+    def forward(ctx, F, index, goff, flag, sel, pos_thresh, fin_thresh, log_scale, flags, pairpos, rec_members=None):
         lib = _lib.require_gpu()
         F = F.contiguous()
         n, c = F.shape
@@ -398,6 +435,7 @@ class _CircleGroupFn(torch.autograd.Function):
                                             _lib.ptr(mean), _lib.stream()), "gcl_circle_group_fwd")
         ctx.save_for_backward(F, index, goff, flag, sel, pairpos)
         ctx.cfg = (pos_thresh, fin_thresh, log_scale, int(flags))
+        ctx.rec_members = rec_members             # as in _GCLLossFn
         return pos, fin, mean
 
     @staticmethod
@@ -408,11 +446,22 @@ class _CircleGroupFn(torch.autograd.Function):
         pos_thresh, fin_thresh, log_scale, flags = ctx.cfg
         dF = torch.zeros_like(F)
         gpos_c, gfin_c, gmean_c = gpos.contiguous(), gfin.contiguous(), gmean.contiguous()     # named: see _GCLLossFn
+        if ctx.rec_members is not None:
+            n_sel, c = sel.shape[0], F.shape[1]
+            cap = int(lib.gcl_circle_group_records(int(ctx.rec_members), n_sel, flags))
+            rec_row, rec_val = ordered.records(cap, c, F.device)
+            rec_off = torch.empty(n_sel + 1, dtype=torch.int32, device=F.device)
+            _lib.check(lib.gcl_circle_group_bwd_emit(_lib.ptr(F), c, _lib.ptr(index), _lib.ptr(goff), _lib.ptr(flag),
+                                                     _lib.ptr(sel), n_sel, pos_thresh, fin_thresh, log_scale, flags,
+                                                     _lib.ptr(pairpos), _lib.ptr(gpos_c), _lib.ptr(gfin_c), _lib.ptr(gmean_c),
+                                                     _lib.ptr(rec_off), _lib.ptr(rec_row), _lib.ptr(rec_val), cap,
+                                                     _lib.stream()), "gcl_circle_group_bwd_emit")
+            return (ordered.ordered_row_sum(rec_row, rec_val, dF),) + (None,) * 10
         _lib.check(lib.gcl_circle_group_bwd(_lib.ptr(F), F.shape[1], _lib.ptr(index), _lib.ptr(goff), _lib.ptr(flag),
                                             _lib.ptr(sel), sel.shape[0], pos_thresh, fin_thresh, log_scale, flags,
                                             _lib.ptr(pairpos), _lib.ptr(gpos_c), _lib.ptr(gfin_c), _lib.ptr(gmean_c),
                                             _lib.ptr(dF), _lib.stream()), "gcl_circle_group_bwd")
-        return (dF,) + (None,) * 9
+        return (dF,) + (None,) * 10
 
 
 def draw_circle_selections(n_groups, max_pos_cluster, group_sizes=None, pair_positive=False):
@@ -431,11 +480,13 @@ def draw_circle_selections(n_groups, max_pos_cluster, group_sizes=None, pair_pos
 def location_circle_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster=256, max_hn_samples=None,
                          points=None, batch_lengths=None, pos_thresh=0.1, neg_thresh=1.4, finest_thresh=0.2,
                          safe_radius=0.75, log_scale=16, draws=None, square_loss=True, block_finest_gradient=True,
-                         use_pair_group_positive_loss=False):
+                         use_pair_group_positive_loss=False, deterministic_loss_backward=False):
     """(pos_loss, finest_loss, neg_loss) of lib/colocation_trainer.py:538-681.  ``points`` [N, 3] (the trainer passes
     the voxel coordinates ``sinput_C[:, 1:]``, :858) and ``batch_lengths`` (rows per sample) are required here.
     The per-group terms and the group means come from one HIP kernel pair; the negative term is a handful of torch
-    operations on the [M, M] matrices of the M <= max_pos_cluster selected groups (:642-676)."""
+    operations on the [M, M] matrices of the M <= max_pos_cluster selected groups (:642-676).
+    ``deterministic_loss_backward``: the per-group kernel's backward pass runs emit -> ordered row sum (see
+    ``finest_contrastive_loss``); the torch operations of the negative term are left as they are."""
     dev = F_out.device
     group_t = torch.as_tensor(group)
     n_groups = int(group_t.shape[0])
@@ -456,8 +507,9 @@ def location_circle_loss(F_out, group, index, index_hash, finest_flag, max_pos_c
     flag = torch.as_tensor(finest_flag).to(dev).to(torch.uint8).contiguous()
     sel = torch.from_numpy(np.ascontiguousarray(pos_sel, dtype=np.int64)).to(dev)
     pp = None if pair_pos is None else torch.from_numpy(np.ascontiguousarray(pair_pos, dtype=np.int32)).to(dev)
+    rec_members = ordered.members_bound(group_t, pos_sel, index_d) if deterministic_loss_backward else None
     pos, fin, feats_sel = _CircleGroupFn.apply(F_out, index_d, goff, flag, sel, float(pos_thresh), float(finest_thresh),
-                                               float(log_scale), flags, pp)
+                                               float(log_scale), flags, pp, rec_members)
     pos_loss, finest_loss = pos.sum() / len(pos_sel), fin.sum() / len(pos_sel)
     # anchors: first member of every selected group (:583) and the sample it belongs to (:589-591)
     pivot = index_d[goff[sel]]
@@ -482,6 +534,8 @@ class FinestContrastiveLossTrainer:
     def __init__(self, config=None, model=None, device=None, ddp=None):
         self.config = config or make_config()
         cfg = self.config
+        if getattr(cfg, "deterministic_loss_backward", False) and not cfg.use_hard_negative:
+            raise ValueError(RANDOM_NEG_NOT_DETERMINISTIC)
         self.device = torch.device(device if device is not None else "cuda:0")
         if model is None:
             Model = load_model(cfg.model)
@@ -559,20 +613,22 @@ class FinestContrastiveLossTrainer:
     def location_loss(self, F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
                       points=None, batch_lengths=None, draws=None, prepared=None, total_weights=None, selections=None):
         cfg = self.config
+        det = bool(getattr(cfg, "deterministic_loss_backward", False))
         if cfg.use_group_circle_loss:         # lib/colocation_trainer.py:423-424
             return location_circle_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
                                         points, batch_lengths, cfg.pos_thresh, cfg.neg_thresh, cfg.finest_thresh,
                                         cfg.safe_radius, 16, draws, cfg.square_loss, cfg.block_finest_gradient,
-                                        cfg.use_pair_group_positive_loss)
+                                        cfg.use_pair_group_positive_loss, deterministic_loss_backward=det)
         if cfg.finest_weight == 0:            # lib/colocation_trainer.py:425-428
             return location_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster,
                                              max_hn_samples, points, batch_lengths, cfg.pos_thresh, cfg.neg_thresh,
-                                             draws, cfg.use_pair_group_positive_loss, cfg.use_hard_negative)
+                                             draws, cfg.use_pair_group_positive_loss, cfg.use_hard_negative,
+                                             deterministic_loss_backward=det)
         return finest_contrastive_loss(F_out, group, index, index_hash, finest_flag, max_pos_cluster, max_hn_samples,
                                        points, batch_lengths, cfg.pos_thresh, cfg.neg_thresh, cfg.finest_thresh, draws,
                                        cfg.square_loss, cfg.block_finest_gradient, cfg.use_pair_group_positive_loss,
                                        cfg.use_hard_negative, prepared=prepared, total_weights=total_weights,
-                                       selections=selections)
+                                       selections=selections, deterministic_loss_backward=det)
 
     def forward_loss(self, input_dict, draws=None, fused_total=False, selections=None):
         """``fused_total``: the weighted total comes out of the loss node itself (one optimizer step on one batch; with
@@ -585,8 +641,11 @@ class FinestContrastiveLossTrainer:
         F_out = self.model(sinput).F
         fuse = (fused_total and not cfg.use_group_circle_loss and cfg.finest_weight != 0 and cfg.use_hard_negative
                 and os.environ.get("GCL_FUSED_LOSS_TOTAL", "1") == "1")
+        group = input_dict["group"]
+        if getattr(cfg, "deterministic_loss_backward", False):     # the record list is sized from the sizes on the HOST
+            group = input_dict.get("_group_host", group)
         terms = self.location_loss(
-            F_out, input_dict["group"], input_dict["index"], input_dict.get("index_hash"), input_dict["finest_flag"],
+            F_out, group, input_dict["index"], input_dict.get("index_hash"), input_dict["finest_flag"],
             max_pos_cluster=cfg.num_pos_per_batch * cfg.batch_size,
             max_hn_samples=cfg.num_hn_samples_per_batch * cfg.batch_size,
             points=input_dict["sinput_C"][:, 1:] if cfg.use_group_circle_loss else None,

@@ -19,6 +19,7 @@ import torch.nn.functional as F_
 from torch.autograd.function import once_differentiable
 
 from gcl_amd import _lib
+from gcl_amd.lib import ordered
 from gcl_amd.lib.metrics import pdist_min
 
 
@@ -31,10 +32,15 @@ def draw_hardest_selections(N0, N1, n_pos_pairs, num_pos, num_hn_samples):
 
 
 def contrastive_hardest_negative_loss(F0, F1, positive_pairs, num_pos=5192, num_hn_samples=2048, pos_thresh=0.1,
-                                      neg_thresh=1.4, draws=None):
+                                      neg_thresh=1.4, draws=None, deterministic_loss_backward=False):
     """Returns (pos_loss, neg_loss) like HardestContrastiveLossTrainer.contrastive_hardest_negative_loss
     (``self.pos_thresh`` / ``self.neg_thresh`` become arguments).  F0 [N0, C], F1 [N1, C] on the GPU; positive_pairs
-    int [P, 2].  ``draws = (sel0, sel1, pos_sel or None)`` replays recorded selections."""
+    int [P, 2].  ``draws = (sel0, sel1, pos_sel or None)`` replays recorded selections.
+    ``deterministic_loss_backward``: the three terms come from the pair-term kernels (GCL_PAIR_SQ_POS over the sampled
+    positives, GCL_PAIR_NEG with eps 1e-7 over the mined pairs of either direction, the membership test a hash-table
+    probe) with the ordered backward, instead of torch's gather / index_put_ (float atomics in its backward pass)."""
+    if deterministic_loss_backward:
+        return _hardest_contrastive_on_kernels(F0, F1, positive_pairs, num_pos, num_hn_samples, pos_thresh, neg_thresh, draws)
     dev = F0.device
     N0, N1 = len(F0), len(F1)
     pairs = torch.as_tensor(np.asarray(positive_pairs) if not torch.is_tensor(positive_pairs) else positive_pairs)
@@ -63,6 +69,42 @@ def contrastive_hardest_negative_loss(F0, F1, positive_pairs, num_pos=5192, num_
     neg_loss0 = F_.relu(neg_thresh - D01min[mask0]).pow(2)
     neg_loss1 = F_.relu(neg_thresh - D10min[mask1]).pow(2)
     return pos_loss.mean(), (neg_loss0.mean() + neg_loss1.mean()) / 2
+
+
+def _hardest_contrastive_on_kernels(F0, F1, positive_pairs, num_pos, num_hn_samples, pos_thresh, neg_thresh, draws):
+    """contrastive_hardest_negative_loss on gcl_pair_terms_fwd / _bwd_emit: the same three means (lib/trainer.py:441-462)."""
+    _require_gpu_features(F0, F1)
+    dev = F0.device
+    N0, N1 = len(F0), len(F1)
+    pairs_d = _pairs_on_device(positive_pairs, dev)
+    if draws is None:
+        draws = draw_hardest_selections(N0, N1, len(pairs_d), num_pos, num_hn_samples)
+    sel0, sel1, pos_sel = draws
+    seed = max(N0, N1)
+    with torch.cuda.device(dev):
+        parts = _upload([sel0, sel1] + ([pos_sel] if pos_sel is not None else []), dev)
+        sel0_d, sel1_d = parts[0], parts[1]
+        sample = pairs_d if pos_sel is None else pairs_d.index_select(0, parts[2])
+        ns = int(sample.shape[0])
+        ind0, ind1 = sample[:, 0].contiguous(), sample[:, 1].contiguous()
+        _, a01 = pdist_min(F0, F1, "L2", rows_a=ind0, rows_b=sel1_d)
+        _, a10 = pdist_min(F1, F0, "L2", rows_a=ind1, rows_b=sel0_d)
+        table, cap = _key_table(pairs_d, seed)
+        n01 = torch.empty(ns, dtype=torch.int64, device=dev)
+        n10 = torch.empty(ns, dtype=torch.int64, device=dev)
+        mask0 = _key_mask(table, cap, seed, sample, 0, b=sel1_d, b_arg=a01, b_out=n01)       # key (ind0, sel1[a01])
+        mask1 = _key_mask(table, cap, seed, sample, 1, b=sel0_d, b_arg=a10, b_out=n10)       # key (sel0[a10], ind1)
+        pos = _PairTermsFn.apply(F0, F1, sample, None, _lib.PAIR_SQ_POS, float(pos_thresh), 0.0, True)
+        neg0 = _PairTermsFn.apply(F0, F1, torch.stack([ind0, n01], 1), mask0, _lib.PAIR_NEG, float(neg_thresh), 1e-7, True)
+        neg1 = _PairTermsFn.apply(F0, F1, torch.stack([n10, ind1], 1), mask1, _lib.PAIR_NEG, float(neg_thresh), 1e-7, True)
+    return pos, (neg0 + neg1) / 2
+
+
+def _reduce_pair_records(recs, dF0, dF1):
+    """The two record lists of a pair-family emit entry (one per cloud) into dF0 and dF1."""
+    (row0, val0), (row1, val1) = recs
+    ordered.ordered_row_sum(row0, val0, dF0)
+    ordered.ordered_row_sum(row1, val1, dF1)
 
 
 # ---- the rest of the pair family on the HIP kernels of csrc/pairloss.hip ---------------------------------------------
@@ -133,8 +175,9 @@ class _TripletFn(torch.autograd.Function):
     gradient."""
 
     @staticmethod
-    def forward(ctx, F0, F1, ap, neg, tag, keep, margin):
+    def forward(ctx, F0, F1, ap, neg, tag, keep, margin, deterministic=False):
         lib = _lib.require_gpu()
+        ctx.deterministic = bool(deterministic)
         F0, F1 = F0.contiguous(), F1.contiguous()
         m, c = int(ap.shape[0]), int(F0.shape[1])
         if F1.shape[1] != c:
@@ -158,19 +201,28 @@ class _TripletFn(torch.autograd.Function):
         dF0, dF1 = torch.zeros_like(F0), torch.zeros_like(F1)
         g = gloss.reshape(1).contiguous().float()
         m = int(ap.shape[0])
-        if m:
+        if m and ctx.deterministic:
+            c, n_rec = int(F0.shape[1]), int(lib.gcl_triplet_records(m))
+            recs = (ordered.records(n_rec, c, F0.device), ordered.records(n_rec, c, F0.device))
+            _lib.check(lib.gcl_triplet_bwd_emit(_lib.ptr(F0), F0.shape[0], _lib.ptr(F1), F1.shape[0], c, _lib.ptr(ap),
+                                                _lib.ptr(neg), _lib.ptr(tag), _lib.ptr(keep), m, _lib.ptr(work), _lib.ptr(out),
+                                                _lib.ptr(g), _lib.ptr(recs[0][0]), _lib.ptr(recs[0][1]), _lib.ptr(recs[1][0]),
+                                                _lib.ptr(recs[1][1]), n_rec, _lib.stream()), "gcl_triplet_bwd_emit")
+            _reduce_pair_records(recs, dF0, dF1)
+        elif m:
             _lib.check(lib.gcl_triplet_bwd(_lib.ptr(F0), F0.shape[0], _lib.ptr(F1), F1.shape[0], F0.shape[1], _lib.ptr(ap),
                                            _lib.ptr(neg), _lib.ptr(tag), _lib.ptr(keep), m, _lib.ptr(work), _lib.ptr(out),
                                            _lib.ptr(g), _lib.ptr(dF0), _lib.ptr(dF1), _lib.stream()), "gcl_triplet_bwd")
-        return dF0, dF1, None, None, None, None, None
+        return dF0, dF1, None, None, None, None, None, None
 
 
 class _PairTermsFn(torch.autograd.Function):
     """Mean over the kept pairs of one of the GCL_PAIR_* terms (gcl_pair_terms_fwd / _bwd)."""
 
     @staticmethod
-    def forward(ctx, F0, F1, pairs, keep, mode, thresh, eps):
+    def forward(ctx, F0, F1, pairs, keep, mode, thresh, eps, deterministic=False):
         lib = _lib.require_gpu()
+        ctx.deterministic = bool(deterministic)
         F0, F1 = F0.contiguous(), F1.contiguous()
         m, c = int(pairs.shape[0]), int(F0.shape[1])
         if F1.shape[1] != c:
@@ -194,12 +246,21 @@ class _PairTermsFn(torch.autograd.Function):
         dF0, dF1 = torch.zeros_like(F0), torch.zeros_like(F1)
         g = gmean.reshape(1).contiguous().float()
         m = int(pairs.shape[0])
-        if m:
+        if m and ctx.deterministic:
+            c, n_rec = int(F0.shape[1]), int(lib.gcl_pair_terms_records(m))
+            recs = (ordered.records(n_rec, c, F0.device), ordered.records(n_rec, c, F0.device))
+            _lib.check(lib.gcl_pair_terms_bwd_emit(_lib.ptr(F0), F0.shape[0], _lib.ptr(F1), F1.shape[0], c, _lib.ptr(pairs),
+                                                   _lib.ptr(keep), m, mode, thresh, eps, _lib.ptr(work), _lib.ptr(out),
+                                                   _lib.ptr(g), _lib.ptr(recs[0][0]), _lib.ptr(recs[0][1]),
+                                                   _lib.ptr(recs[1][0]), _lib.ptr(recs[1][1]), n_rec, _lib.stream()),
+                       "gcl_pair_terms_bwd_emit")
+            _reduce_pair_records(recs, dF0, dF1)
+        elif m:
             _lib.check(lib.gcl_pair_terms_bwd(_lib.ptr(F0), F0.shape[0], _lib.ptr(F1), F1.shape[0], F0.shape[1],
                                               _lib.ptr(pairs), _lib.ptr(keep), m, mode, thresh, eps, _lib.ptr(work),
                                               _lib.ptr(out), _lib.ptr(g), _lib.ptr(dF0), _lib.ptr(dF1), _lib.stream()),
                        "gcl_pair_terms_bwd")
-        return dF0, dF1, None, None, None, None, None
+        return dF0, dF1, None, None, None, None, None, None
 
 
 def _mean_pair_distance(F0, F1, pairs_d):
@@ -234,7 +295,7 @@ def generate_rand_negative_pairs(positive_pairs, hash_seed, N0, N1, N_neg=0, dra
         return cand, _key_mask(table, cap, hash_seed, cand)
 
 
-def contrastive_random_negative_loss(F0, F1, positive_pairs, neg_thresh=1.4, draws=None):
+def contrastive_random_negative_loss(F0, F1, positive_pairs, neg_thresh=1.4, draws=None, deterministic_loss_backward=False):
     """``(pos_loss_mean, neg_loss_mean)`` of ContrastiveLossTrainer's step (lib/trainer.py:253-273, without ``/ iter_size``):
     mean |F0[i] - F1[j]|^2 over ALL positive pairs, and mean relu(neg_thresh - sqrt(|F0[a] - F1[b]|^2 + 1e-4))^2 over the
     random pairs that are no positive pair.  ``draws``: recorded candidates (``draw_rand_negative_pairs``).  No copy to the
@@ -244,8 +305,9 @@ def contrastive_random_negative_loss(F0, F1, positive_pairs, neg_thresh=1.4, dra
     N0, N1 = len(F0), len(F1)
     pairs_d = _pairs_on_device(positive_pairs, dev)
     cand, keep = generate_rand_negative_pairs(pairs_d, max(N0, N1), N0, N1, draws=draws, device=dev)
-    pos = _PairTermsFn.apply(F0, F1, pairs_d, None, _lib.PAIR_SQ, 0.0, 0.0)
-    neg = _PairTermsFn.apply(F0, F1, cand, keep, _lib.PAIR_NEG, float(neg_thresh), 1e-4)
+    det = bool(deterministic_loss_backward)
+    pos = _PairTermsFn.apply(F0, F1, pairs_d, None, _lib.PAIR_SQ, 0.0, 0.0, det)
+    neg = _PairTermsFn.apply(F0, F1, cand, keep, _lib.PAIR_NEG, float(neg_thresh), 1e-4, det)
     return pos, neg
 
 
@@ -277,7 +339,7 @@ def draw_hardest_triplet_selections(N0, N1, n_pos_pairs, num_pos, num_hn_samples
 
 
 def triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=None, num_rand_triplet=1024, neg_thresh=1.4,
-                 draws=None, details=None):
+                 draws=None, details=None, deterministic_loss_backward=False):
     """``(loss, pos_dist.mean(), rand_neg_dist.mean())`` of TripletLossTrainer.triplet_loss (lib/trainer.py:545-592;
     ``self.neg_thresh``, the margin, becomes an argument; ``num_hn_samples`` is unused, as there).  Random triplets
     (anchor F0[i], positive F1[j] of a drawn positive pair, a drawn row of F1 as negative), those whose (anchor, negative)
@@ -303,7 +365,8 @@ def triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=None, num_
         rand_ap = pairs_d.index_select(0, rand_d)
         table, cap = _key_table(pairs_d, seed)
         keep = _key_mask(table, cap, seed, rand_ap, 0, b=neg_d)
-        loss, stats = _TripletFn.apply(F0, F1, rand_ap, neg_d, tag_d, keep, float(neg_thresh))
+        loss, stats = _TripletFn.apply(F0, F1, rand_ap, neg_d, tag_d, keep, float(neg_thresh),
+                                       bool(deterministic_loss_backward))
         sample = pairs_d if pos_sel is None else pairs_d.index_select(0, parts[2])
         pos_dist = _mean_pair_distance(F0, F1, sample)
     if details is not None:
@@ -312,7 +375,7 @@ def triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=None, num_
 
 
 def hardest_triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=512, num_rand_triplet=1024,
-                         neg_thresh=1.4, draws=None, details=None):
+                         neg_thresh=1.4, draws=None, details=None, deterministic_loss_backward=False):
     """``(loss, pos_dist.mean(), (D01min.mean() + D10min.mean()) / 2)`` of HardestTripletLossTrainer.triplet_loss
     (lib/trainer.py:671-744).  The random triplets of ``triplet_loss`` plus, for every sampled positive pair (i, j), the
     hardest negative of F0[i] among ``num_hn_samples`` drawn rows of F1 and of F1[j] among as many rows of F0
@@ -355,7 +418,7 @@ def hardest_triplet_loss(F0, F1, positive_pairs, num_pos=1024, num_hn_samples=51
             _key_mask(table, cap, seed, ap[nr:nr + ns], 0, b=sel1_d, b_arg=a01, b_out=neg_d[nr:nr + ns],
                       keep=keep[nr:nr + ns])
             _key_mask(table, cap, seed, ap[nr + ns:], 1, b=sel0_d, b_arg=a10, b_out=neg_d[nr + ns:], keep=keep[nr + ns:])
-        loss, stats = _TripletFn.apply(F0, F1, ap, neg_d, tag_d, keep, float(neg_thresh))
+        loss, stats = _TripletFn.apply(F0, F1, ap, neg_d, tag_d, keep, float(neg_thresh), bool(deterministic_loss_backward))
     if details is not None:
         details.update(rand_mask=keep[:nr], mask0=keep[nr:nr + ns], mask1=keep[nr + ns:], neg01=neg_d[nr:nr + ns],
                        neg10=neg_d[nr + ns:])
@@ -395,6 +458,8 @@ class ContrastiveLossTrainer:
                                              weight_decay=cfg.weight_decay)
         self.scheduler = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, cfg.exp_gamma)
         self.neg_weight = cfg.neg_weight
+        # the loss backward as records + ordered row sum (gcl_amd/lib/ordered.py): read by every pair trainer's pair_loss
+        self.deterministic = bool(getattr(cfg, "deterministic_loss_backward", False))
         self._params = [p for p in self.model.parameters()]
 
     # -- what the four trainers differ in ---------------------------------------------------------------------------------
@@ -405,7 +470,8 @@ class ContrastiveLossTrainer:
 
     def pair_loss(self, F0, F1, pos_pairs, draws):
         """``(loss, parts)``: the scalar that is back-propagated (before ``/ iter_size``) and the reported terms."""
-        pos, neg = contrastive_random_negative_loss(F0, F1, pos_pairs, self.config.neg_thresh, draws=draws)
+        pos, neg = contrastive_random_negative_loss(F0, F1, pos_pairs, self.config.neg_thresh, draws=draws,
+                                                    deterministic_loss_backward=self.deterministic)
         return pos + self.neg_weight * neg, (pos, neg)
 
     # -- the step ---------------------------------------------------------------------------------------------------------
@@ -484,7 +550,8 @@ class HardestContrastiveLossTrainer(ContrastiveLossTrainer):
         cfg = self.config
         pos, neg = contrastive_hardest_negative_loss(F0, F1, pos_pairs, num_pos=cfg.num_pos_per_batch * cfg.batch_size,
                                                      num_hn_samples=cfg.num_hn_samples_per_batch * cfg.batch_size,
-                                                     pos_thresh=cfg.pos_thresh, neg_thresh=cfg.neg_thresh, draws=draws)
+                                                     pos_thresh=cfg.pos_thresh, neg_thresh=cfg.neg_thresh, draws=draws,
+                                                     deterministic_loss_backward=self.deterministic)
         return pos + self.neg_weight * neg, (pos, neg)
 
 
@@ -506,7 +573,8 @@ class TripletLossTrainer(ContrastiveLossTrainer):
     def pair_loss(self, F0, F1, pos_pairs, draws):
         num_pos, num_hn, num_rand = self._counts()
         loss, pos_dist, neg_dist = triplet_loss(F0, F1, pos_pairs, num_pos=num_pos, num_hn_samples=num_hn,
-                                                num_rand_triplet=num_rand, neg_thresh=self.config.neg_thresh, draws=draws)
+                                                num_rand_triplet=num_rand, neg_thresh=self.config.neg_thresh, draws=draws,
+                                                deterministic_loss_backward=self.deterministic)
         return loss, (pos_dist, neg_dist)
 
 
@@ -523,5 +591,5 @@ class HardestTripletLossTrainer(TripletLossTrainer):
         num_pos, num_hn, num_rand = self._counts()
         loss, pos_dist, neg_dist = hardest_triplet_loss(F0, F1, pos_pairs, num_pos=num_pos, num_hn_samples=num_hn,
                                                         num_rand_triplet=num_rand, neg_thresh=self.config.neg_thresh,
-                                                        draws=draws)
+                                                        draws=draws, deterministic_loss_backward=self.deterministic)
         return loss, (pos_dist, neg_dist)

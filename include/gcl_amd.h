@@ -1230,6 +1230,87 @@ int gcl_pair_terms_bwd(const float* f0, int64_t n0, const float* f1, int64_t n1,
                        const float* out, const float* g, float* df0, float* df1, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Loss backward without float atomics: contribution records and the ordered row sum (csrc/ordered.hip).
+ *
+ * Every loss backward entry above has an *_emit twin with the same arguments, which writes its contributions as
+ * RECORDS instead of adding them into dF: record i = (rec_row[i] int32, rec_val[i][0 .. c) float).  The twin runs the
+ * SAME kernel body (the sink is a template parameter), so the values are those the atomic entry hands to atomicAdd.
+ *
+ * The contribution list of an entry: its (destination row, value[c]) pairs in the order its kernel would issue them if
+ * the grid ran one wave at a time in ascending blockIdx, inside a wave in program order.  A record has a FIXED position:
+ *   gcl_group_loss_bwd_emit     wave s = selected group s, window rec_off[s] .. rec_off[s + 1): its n_s members in index
+ *                               order, then (GCL_LOSS_PAIR) the two drawn members ra, rb
+ *   gcl_circle_group_bwd_emit   its n_s members, then the finest member's collected gradient, then (GCL_LOSS_PAIR) ra, rb
+ *   gcl_neg_loss_bwd_emit       2 r: sel1[r], 2 r + 1: sel2[arg[r]]
+ *   gcl_triplet_bwd_emit        3 t: anchor, 3 t + 1: positive, 3 t + 2: negative
+ *   gcl_pair_terms_bwd_emit     t
+ * rec_off (int32 [n_sel + 1], an OUTPUT) = the exclusive sums of the window lengths n_s + extra, made on the device;
+ * rec_off[n_sel] = the records the entry needs.  The caller sizes the lists from host-known sizes:
+ *   gcl_group_loss_records(n_members, n_sel, flags)    = n_members + n_sel * (GCL_LOSS_PAIR ? 2 : 0)
+ *   gcl_circle_group_records(n_members, n_sel, flags)  = n_members + n_sel * (GCL_LOSS_PAIR ? 3 : 1)
+ *   gcl_neg_loss_records(m) = 2 m,  gcl_triplet_records(m) = 3 m,  gcl_pair_terms_records(m) = m        (0 for counts <= 0)
+ * with n_members = the sum of the selected groups' sizes (or any bound of it, such as the length of `index` when the
+ * selected groups are distinct).  n_rec = the capacity of the lists the caller passes: the three per-item entries refuse
+ * an n_rec below their count; the two group entries cannot know n_members without a host read and DROP a record whose
+ * slot is at or past n_rec (nothing is written out of bounds; rec_off[n_sel] > n_rec tells).
+ *
+ * Rules of a list:
+ *   - every entry first sets rec_row[0 .. n_rec) = -1.  A contribution the atomic kernel skips -- a wave that returns
+ *     early (both upstream gradients zero or both hinges inactive, an inactive hinge of the negative term or of a
+ *     triplet / pair), a keep == 0 item, a row id outside its cloud, the GCL_LOSS_PAIR slots of a group whose positive
+ *     term has no gradient -- and every unused slot therefore is a record with row -1; its value is not written.
+ *   - a value vector is recorded WHOLE.  The atomic kernels skip a lane whose value is exactly 0.f (the members' and the
+ *     finest member's contributions), the record keeps the zero: the ordered result may differ from an atomic one in the
+ *     sign of a zero and in nothing else.
+ *   - the pair family writes TWO lists, one per cloud (rec_row0 / rec_val0 -> dF0, rec_row1 / rec_val1 -> dF1), both with
+ *     the slots above and n_rec records each: a contribution stands in the list of the cloud it goes to, the same slot
+ *     of the other list is -1.  (A single list with a cloud tag would make the reduction filter; two lists reduce with
+ *     two plain calls.)
+ *   - several entries into one dF (group loss, then the negative term): one list, the entries' windows one after the other
+ *     in call order (pass each entry its part of rec_row / rec_val).
+ *
+ * gcl_ordered_row_sum: for every row r in [0, n_rows) named by at least one record,
+ *     dF[r] = fl(... fl(fl(dF[r] + v_1) + v_2) ... + v_k)   in fp32, over the row's records in ascending list position;
+ * the sum starts from what dF[r] holds (the atomic entries' "accumulates into a pre-filled buffer"); rows no record
+ * names are not written; records with a row < 0 or >= n_rows are skipped.  By construction this is one of the results
+ * the atomic kernels may produce -- and the same bits on every run.  c <= 64, n_rows < 2^31.  No host read; integer
+ * atomics only count and place, and a row's record ids are put in ascending order (a bitmap per window of
+ * gcl_ordered_row_sum_window() consecutive ids, in LDS, by the wave that owns the row) before anything is added; a row
+ * may be named by any number of records.  scratch: int32 [gcl_ordered_row_sum_scratch_len(n_rec, n_rows)] =
+ * 2 + 2 n_rows + 3 n_rec (0 when either count is <= 0).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t gcl_group_loss_records(int64_t n_members, int32_t n_sel, int32_t flags);
+int gcl_group_loss_bwd_emit(const float* f, int32_t c, const int64_t* index, const int64_t* goff,
+                            const uint8_t* finest_flag, const int64_t* sel, int32_t n_sel, float pos_thresh,
+                            float finest_thresh, int32_t flags, const int32_t* pairpos, const float* gpos,
+                            const float* gfin, int32_t* rec_off, int32_t* rec_row, float* rec_val, int32_t n_rec,
+                            void* stream);
+int64_t gcl_circle_group_records(int64_t n_members, int32_t n_sel, int32_t flags);
+int gcl_circle_group_bwd_emit(const float* f, int32_t c, const int64_t* index, const int64_t* goff,
+                              const uint8_t* finest_flag, const int64_t* sel, int32_t n_sel, float pos_thresh,
+                              float finest_thresh, float log_scale, int32_t flags, const int32_t* pairpos,
+                              const float* gpos, const float* gfin, const float* gmean, int32_t* rec_off,
+                              int32_t* rec_row, float* rec_val, int32_t n_rec, void* stream);
+int64_t gcl_neg_loss_records(int32_t m);
+int gcl_neg_loss_bwd_emit(const float* f, int32_t c, const int64_t* sel1, const int64_t* sel2, const int32_t* arg,
+                          const float* dmin, const uint8_t* keep, int32_t m, float thresh, const float* out,
+                          const float* gneg, int32_t* rec_row, float* rec_val, int32_t n_rec, void* stream);
+int64_t gcl_triplet_records(int32_t m);
+int gcl_triplet_bwd_emit(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* ap,
+                         const int64_t* neg, const uint8_t* tag, const uint8_t* keep, int32_t m, const float* work,
+                         const float* out, const float* g, int32_t* rec_row0, float* rec_val0, int32_t* rec_row1,
+                         float* rec_val1, int32_t n_rec, void* stream);
+int64_t gcl_pair_terms_records(int32_t m);
+int gcl_pair_terms_bwd_emit(const float* f0, int64_t n0, const float* f1, int64_t n1, int32_t c, const int64_t* pairs,
+                            const uint8_t* keep, int32_t m, int32_t mode, float thresh, float eps, const float* work,
+                            const float* out, const float* g, int32_t* rec_row0, float* rec_val0, int32_t* rec_row1,
+                            float* rec_val1, int32_t n_rec, void* stream);
+int32_t gcl_ordered_row_sum_window(void);
+int64_t gcl_ordered_row_sum_scratch_len(int32_t n_rec, int64_t n_rows);
+int gcl_ordered_row_sum(const int32_t* rec_row, const float* rec_val, int32_t n_rec, int32_t c, int64_t n_rows,
+                        int32_t* scratch, float* df, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * FPFH descriptors (csrc/fpfh.hip): what open3d's estimate_normals + compute_fpfh_feature give, made on the device for
  * the `descriptor: fpfh` arm of the SC2-PCR benchmark (scripts/SC2_PCR/dataset.py:66-74 only loads them).  xyz [n, 3]
  * is a concatenation of n_clouds clouds; offsets (DEVICE int64 [n_clouds + 1], ascending, offsets[0] = 0,
