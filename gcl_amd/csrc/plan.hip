@@ -15,6 +15,7 @@
 
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <utility>
 #include <vector>
@@ -542,7 +543,7 @@ struct TState {            // a tensor of the pass (forward value or gradient)
   void* planes = nullptr;    // gcl_split_planes image, or NULL = not made yet
   int ld = 0;                // row pitch in floats when the tensor is a column slice of a wider one (gradients of ME.cat
                              // inputs: slices of the gradient of the cat's output), 0 = its own channel count
-  bool plane_only = false;   // ptr is NULL on purpose: every reader takes `planes` (plane_only_analysis), no fp32 form exists
+  bool plane_only = false;   // ptr is NULL on purpose: every reader takes `planes` (analyse_graph), no fp32 form exists
 };
 
 // in front of every launch that reads the fp32 form of a tensor: a reader the analysis overlooked ends here, on the host
@@ -590,6 +591,16 @@ struct PassState {        // everything one forward pass leaves behind for its b
   bool keep_twins = false;          // Plan::keep_fp32 as it stood when the pass was sized: both passes of one arena agree
 };
 
+struct Readers {      // who reads a tensor, by record: found once, what every analysis of the record graph asks
+  int maker = -1;             // the record that makes it (-1: the plan's input)
+  std::vector<int> x, x2;     // the records that read it as x / as x2, ascending; a record that reads it as both is in both
+  bool output = false;        // the last record's output: the caller reads it
+  int count() const { return (int)(x.size() + x2.size()); }      // (a record that reads it twice counts twice)
+  bool only(int rec) const {      // nobody but record rec reads it
+    return !output && std::count(x.begin(), x.end(), rec) + std::count(x2.begin(), x2.end(), rec) == count();
+  }
+};
+
 struct Plan : PassState {   // the base part is the pass being enqueued right now
   std::vector<PassState*> passes;   // passes waiting for their backward pass (several forwards may be outstanding)
   std::vector<gcl_plan_op> ops;
@@ -601,22 +612,19 @@ struct Plan : PassState {   // the base part is the pass being enqueued right no
   long long bytes_fwd = 0, bytes_bwd = 0, wgs_fwd = 0, wgs_bwd = 0;
   int n_bwd = 0;
   std::vector<char> made;           // tensor id -> produced by a record of the plan
+  std::vector<Readers> readers;     // tensor id -> who makes and who reads it (analyse_graph)
   std::vector<char> fuse_relu;      // record i is a CONV whose only consumer is the RELU record i + 1: one launch writes relu(y)
   std::vector<int> cat_left;        // record i is a CONVBN whose output is only the LEFT input of CAT record cat_left[i]: its
                                     // BatchNorm apply pass writes into the cat's output (row pitch = the cat's width)
   std::vector<int> mask_from;       // record i is a convolution whose input is the output of RELU record mask_from[i] and that
                                     // ReLU's only consumer: its input-gradient epilogue applies the ReLU's backward (-1: no)
-  // plane-only tensors (plane_only_analysis): record i is a CONVBN in bound mode whose output y (po_fwd) / whose BatchNorm
+  // plane-only tensors (analyse_graph): record i is a CONVBN in bound mode whose output y (po_fwd) / whose BatchNorm
   // input gradient dx (po_bwd) every reader takes as a plane image -- the apply pass writes no fp32 twin and the arena holds
   // none.  keep_fp32 (gcl_plan_set_keep_fp32, tests): every twin is written, as if both vectors were all zero
   std::vector<char> po_fwd, po_bwd;
   bool keep_fp32 = false;
   // device tables (inside the caller's `state` buffer), re-uploaded when a parameter pointer changes
   std::vector<long long> host_tables, uploaded;
-  // inference passes (gcl_plan_forward_eval): BatchNorm in eval mode folded into the convolution epilogue
-  bool eval = false;
-  void* const* bn_eval = nullptr;   // per BatchNorm: scale, shift, mean, rstd (device pointers)
-  bool eval_repack = true;
   // optional second stream for the weight gradients (off the critical path of the backward pass)
   hipStream_t aux = nullptr;
   std::vector<hipEvent_t> events;
@@ -670,27 +678,31 @@ static int ensure_planes(Plan& P, TState& ts, long long n, int c, hipStream_t st
 // The weight gradient of a record is needed only by the optimizer: with an aux stream it is enqueued there, ordered
 // behind everything the main stream has issued so far (its operands), and the main stream goes on with the input-gradient
 // chain.  join_aux makes the main stream wait for all of it (end of a backward segment).
+// fork / join events are re-used pass after pass (recording re-arms them): the next one, created when the pool is used up
+static hipError_t next_event(Plan& P, hipEvent_t* e) {
+  if (P.events_used == P.events.size()) {
+    hipEvent_t fresh;
+    const hipError_t err = hipEventCreateWithFlags(&fresh, hipEventDisableTiming);
+    if (err != hipSuccess) return err;
+    P.events.push_back(fresh);
+  }
+  *e = P.events[P.events_used++];
+  return hipSuccess;
+}
+
 static hipStream_t fork_aux(Plan& P, hipStream_t st) {
   if (!P.aux || P.A.dry) return st;
-  if (P.events_used == P.events.size()) {
-    hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return st;
-    P.events.push_back(e);
-  }
-  hipEvent_t e = P.events[P.events_used++];
-  if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(P.aux, e, 0) != hipSuccess) return st;
+  hipEvent_t e;
+  if (next_event(P, &e) != hipSuccess || hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(P.aux, e, 0) != hipSuccess)
+    return st;
   P.aux_dirty = true;
   return P.aux;
 }
 
 static int join_aux(Plan& P, hipStream_t st) {
   if (!P.aux || !P.aux_dirty || P.A.dry) return GCL_OK;
-  if (P.events_used == P.events.size()) {
-    hipEvent_t e;
-    GCL_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    P.events.push_back(e);
-  }
-  hipEvent_t e = P.events[P.events_used++];
+  hipEvent_t e;
+  GCL_CHECK_HIP(next_event(P, &e));
   GCL_CHECK_HIP(hipEventRecord(e, P.aux));
   GCL_CHECK_HIP(hipStreamWaitEvent(st, e, 0));
   P.aux_dirty = false;
@@ -716,19 +728,30 @@ struct ProfScope {      // brackets one launch with events when profiling is arm
   ~ProfScope() { if (r) (void)hipEventRecord(r->e1, st); }
 };
 
-static bool is_stem(const gcl_plan_op& op, const gcl_map_desc& m) {
-  return op.cin <= 4 && (op.cout % 32) == 0 && !op.transpose && m.kernel_size > 1 && op.bias < 0;
+// The Cin <= 4 first layer, convolved by the VALU stem kernels on the fp32 weights.  Decided from the record alone, so the
+// constructor, the reader analysis and both passes agree: K > 1 stands for the map's kernel_size > 1, because check_maps pins
+// m.K == op.K for the maps of every pass and a map's K is kernel_size^3.
+static bool is_conv(const gcl_plan_op& op) { return op.kind == GCL_OP_CONVBN || op.kind == GCL_OP_CONV; }
+static bool stem_shape(const gcl_plan_op& op) {
+  return op.cin <= 4 && (op.cout % 32) == 0 && !op.transpose && op.K > 1 && op.bias < 0;
 }
 
-// occupancy rows of the first layer: measured once per pass, per cloud (the reference's training loaders jitter the centre
-// cloud of a sample only), spread to rows -- device flags, no host decision
-static int stem_flag(Plan& P, const gcl_plan_op& op, const gcl_map_desc& m, const TState& x, long long n_in, hipStream_t st) {
+// the first layer's convolution into the caller's [n_out, cout] block.  Its occupancy rows are measured once per pass, per cloud
+// (the reference's training loaders jitter the centre cloud of a sample only), spread to rows: device flags, no host decision
+static int stem_forward(Plan& P, int i, long long n_in, long long n_out, float* y, hipStream_t st) {
   Arena& A = P.A;
-  if (!m.presence || P.not_ones) return GCL_OK;
-  constexpr int CLOUD_FLAGS = 4096;      // batch indices beyond this take the table path
-  int32_t* cloud = A.take_n<int32_t>(CLOUD_FLAGS);
-  P.not_ones = A.take_n<int32_t>(n_in);
-  PLAN_CALL(gcl_not_ones_rows(x.ptr, op.cin, P.maps->coords[op.level_in], n_in, cloud, CLOUD_FLAGS, P.not_ones, (void*)st));
+  const gcl_plan_op& op = P.ops[i];
+  const gcl_map_desc& m = P.maps->maps[op.map];
+  const TState& x = P.t[op.x];
+  NEED_F32(x, i, "its input (first layer)");
+  if (m.presence && !P.not_ones) {
+    constexpr int CLOUD_FLAGS = 4096;      // batch indices beyond this take the table path
+    int32_t* cloud = A.take_n<int32_t>(CLOUD_FLAGS);
+    P.not_ones = A.take_n<int32_t>(n_in);
+    PLAN_CALL(gcl_not_ones_rows(x.ptr, op.cin, P.maps->coords[op.level_in], n_in, cloud, CLOUD_FLAGS, P.not_ones, (void*)st));
+  }
+  PLAN_CALL(gcl_stem_fwd(x.ptr, (const float*)P.params[op.w], m.nbr, n_out, op.K, op.cin, op.cout, y, m.presence,
+                         m.presence ? P.not_ones : nullptr, (void*)st));
   return GCL_OK;
 }
 
@@ -742,53 +765,67 @@ static SortedTable sorted_table(const gcl_map_desc& m, bool transposed) {
   return transposed ? SortedTable{m.tbl_t, m.order_t, m.mask_t} : SortedTable{m.tbl_n, m.order_n, m.mask_n};
 }
 
-// the convolution of a CONVBN / CONV record (ops._SparseConvFn.forward); returns its output in *y_out
-// rows > 0: a kernel_size-1 record of the touched-row suffix whose input is a compact [rows, cin] tensor
-static int conv_forward(Plan& P, int i, float** y_out, float** stats_out, hipStream_t st, int32_t** relu_amax_out,
-                        long long rows = 0) {
-  Arena& A = P.A;
+// The fp16x3 launch of a CONVBN / CONV record off the first layer, in training and in inference alike: conv_prepare makes
+// what it reads besides x (the packs, max|x|, the map's sorted table; `who`: the entry, for the error text) ...
+static int conv_prepare(Plan& P, int i, long long n_in, const char* who, hipStream_t st) {
   const gcl_plan_op& op = P.ops[i];
-  const gcl_maps_desc& M = *P.maps;
-  const gcl_map_desc& m = M.maps[op.map];
-  const long long n_in = rows > 0 ? rows : M.n_rows[op.level_in], n_out = rows > 0 ? rows : M.n_rows[op.level_out];
-  TState& x = P.t[op.x];
-  float* y = A.take_n<float>(n_out * op.cout);
-  *y_out = y;
-  *stats_out = nullptr;
-  *relu_amax_out = nullptr;
-  const float* W = (const float*)P.params[op.w];
-  if (is_stem(op, m)) {
-    NEED_F32(x, i, "its input (first layer)");
-    int rcs = stem_flag(P, op, m, x, n_in, st);
-    if (rcs) return rcs;
-    PLAN_CALL(gcl_stem_fwd(x.ptr, W, m.nbr, n_out, op.K, op.cin, op.cout, y, m.presence, m.presence ? P.not_ones : nullptr,
-                           (void*)st));
-    return GCL_OK;
-  }
-  const int wi = P.widx[op.w];
-  if (P.fwd_packs_pending && !A.dry) {      // first convolution that reads packed weights
+  const gcl_map_desc& m = P.maps->maps[op.map];
+  if (P.fwd_packs_pending && !P.A.dry) {      // first convolution that reads the packs forward_setup made on the aux stream
     GCL_CHECK_HIP(hipStreamWaitEvent(st, P.fwd_packs, 0));
     P.fwd_packs_pending = false;
   }
-  int rc = ensure_amax(P, x, n_in * op.cin, st, i);
-  if (rc) return rc;
-  P.saved[i].x_amax = x.amax;
-  const bool pl = op.cin >= P.presplit;
-  if (pl && (rc = ensure_planes(P, x, n_in, op.cin, st, i))) return rc;
-  if (!pl) NEED_F32(x, i, "its input");
-  float* stats = nullptr;
-  if (op.kind == GCL_OP_CONVBN) stats = A.take_n<float>(cdiv(n_out, 128) * 4 * op.cout);      // sum, squares, min, max per column and 128-row tile
-  *stats_out = stats;
+  GCL_CHECK_ARG(P.A.dry || m.kernel_size == 1 || sorted_table(m, op.transpose).tbl,
+                "%s: record %d needs a sorted table the maps do not carry", who, i);
+  return ensure_amax(P, P.t[op.x], n_in * op.cin, st, i);
+}
+// ... and conv_launch issues it with the operands of the caller's mode (gcl_conv_fwd_fused's, `stats` as the flags define it)
+static int conv_launch(Plan& P, int i, bool planes, long long n_in, long long n_out, const float* bias, const float* col_scale,
+                       const float* residual, int relu, int32_t* y_amax, float* y, float* stats, int flags, hipStream_t st) {
+  Arena& A = P.A;
+  const gcl_plan_op& op = P.ops[i];
+  const gcl_map_desc& m = P.maps->maps[op.map];
+  const TState& x = P.t[op.x];
   const SortedTable T = sorted_table(m, op.transpose);
-  GCL_CHECK_ARG(A.dry || m.kernel_size == 1 || T.tbl, "gcl_plan_forward: record %d needs a sorted table the maps do not carry", i);
-  const float* bias = op.bias >= 0 ? (const float*)P.params[op.bias] : nullptr;
+  const int wi = P.widx[op.w];
+  if (!planes) NEED_F32(x, i, "its input");
   ProfScope ps(P, st, 0, (double)(m.kernel_size > 1 ? m.n_pairs : n_out), op.cin, op.cout, n_in, n_out, op.K);
-  int32_t* relu_amax = (op.kind == GCL_OP_CONV && P.fuse_relu[i]) ? new_slot(P) : nullptr;
-  *relu_amax_out = relu_amax;
-  PLAN_CALL(gcl_conv_fwd_fused(pl ? (const float*)x.planes : x.ptr, n_in, pl ? 1 : 0, P.pack_fwd + P.off_fwd[wi], 4, x.amax,
+  PLAN_CALL(gcl_conv_fwd_fused(planes ? (const float*)x.planes : x.ptr, n_in, planes ? 1 : 0, P.pack_fwd + P.off_fwd[wi], 4, x.amax,
                                P.w_amax + (long long)wi * GCL_AMAX_WORDS, T.tbl, T.order, T.mask, n_out, op.K, op.cin, op.cout,
-                               bias, nullptr, nullptr, relu_amax ? 1 : 0, relu_amax, y, stats, 0, (void*)st));
+                               bias, col_scale, residual, relu, y_amax, y, stats, flags, (void*)st));
   return GCL_OK;
+}
+
+// The convolution of a CONVBN / CONV record in a training pass (ops._SparseConvFn.forward), which is all of a CONV record
+// rows > 0: a kernel_size-1 record of the touched-row suffix whose input is a compact [rows, cin] tensor
+struct ConvOut {
+  int rc;
+  float* y;         // [n_out, cout]
+  float* stats;     // CONVBN off the first layer: sum, squares, min, max per column and 128-row tile
+};
+static ConvOut conv_forward(Plan& P, int i, hipStream_t st, long long rows = 0) {
+  Arena& A = P.A;
+  const gcl_plan_op& op = P.ops[i];
+  const long long n_in = rows > 0 ? rows : P.maps->n_rows[op.level_in], n_out = rows > 0 ? rows : P.maps->n_rows[op.level_out];
+  TState& x = P.t[op.x];
+  ConvOut out{GCL_OK, A.take_n<float>(n_out * op.cout), nullptr};
+  if (op.kind == GCL_OP_CONV) P.t[op.y].ptr = out.y;
+  if (stem_shape(op)) {
+    out.rc = stem_forward(P, i, n_in, n_out, out.y, st);
+    return out;
+  }
+  if ((out.rc = conv_prepare(P, i, n_in, "gcl_plan_forward", st))) return out;
+  P.saved[i].x_amax = x.amax;
+  const bool planes = op.cin >= P.presplit;
+  if (planes && (out.rc = ensure_planes(P, x, n_in, op.cin, st, i))) return out;
+  if (op.kind == GCL_OP_CONVBN) out.stats = A.take_n<float>(cdiv(n_out, 128) * 4 * op.cout);
+  int32_t* relu_amax = nullptr;
+  if (op.kind == GCL_OP_CONV && P.fuse_relu[i]) {      // the epilogue applies the ReLU record that follows: both tensor ids name relu(conv(x))
+    relu_amax = P.t[op.y].amax = new_slot(P);
+    P.t[P.ops[i + 1].y] = P.t[op.y];
+  }
+  out.rc = conv_launch(P, i, planes, n_in, n_out, op.bias >= 0 ? (const float*)P.params[op.bias] : nullptr, nullptr, nullptr,
+                       relu_amax ? 1 : 0, relu_amax, out.y, out.stats, 0, st);
+  return out;
 }
 
 static int upload_tables(Plan& P, hipStream_t st) {
@@ -796,24 +833,18 @@ static int upload_tables(Plan& P, hipStream_t st) {
   const size_t n = P.worder.size();
   std::vector<long long>& h = P.host_tables;
   h.assign((size_t)state_words(P), 0);
-  long long wg = 0;
+  P.wgs_fwd = P.wgs_bwd = 0;
+  size_t row = 0;      // of the input-gradient descriptors: one per kernel that needs an input gradient
+  auto desc = [&](long long* d, size_t q, long long mode, long long off, long long& wgs) {
+    d[0] = h[q]; d[1] = P.wK[q]; d[2] = P.wcin[q]; d[3] = P.wcout[q]; d[4] = mode; d[5] = (long long)q; d[6] = off; d[7] = wgs;
+    wgs += cdiv(h[n + q], 256);
+  };
   for (size_t q = 0; q < n; ++q) {
     h[q] = (long long)(uintptr_t)P.params[P.worder[q]];
     h[n + q] = P.wK[q] * P.wcin[q] * P.wcout[q];
-    long long* d = &h[2 * n + 8 * q];
-    d[0] = h[q]; d[1] = P.wK[q]; d[2] = P.wcin[q]; d[3] = P.wcout[q]; d[4] = 0; d[5] = (long long)q; d[6] = P.off_fwd[q]; d[7] = wg;
-    wg += cdiv(h[n + q], 256);
+    desc(&h[2 * n + 8 * q], q, 0, P.off_fwd[q], P.wgs_fwd);
+    if (P.wmode[q]) desc(&h[2 * n + 8 * n + 8 * row++], q, P.wmode[q], P.off_bwd[q], P.wgs_bwd);
   }
-  P.wgs_fwd = wg;
-  wg = 0;
-  size_t row = 0;
-  for (size_t q = 0; q < n; ++q) {
-    if (!P.wmode[q]) continue;
-    long long* d = &h[2 * n + 8 * n + 8 * row++];
-    d[0] = h[q]; d[1] = P.wK[q]; d[2] = P.wcin[q]; d[3] = P.wcout[q]; d[4] = P.wmode[q]; d[5] = (long long)q; d[6] = P.off_bwd[q]; d[7] = wg;
-    wg += cdiv(h[n + q], 256);
-  }
-  P.wgs_bwd = wg;
   if (h != P.uploaded) {      // parameters were (re-)seated: rare; the copy is finished before the vector can change
     GCL_CHECK_HIP(hipMemcpyAsync(P.state, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, st));
     GCL_CHECK_HIP(hipStreamSynchronize(st));
@@ -839,15 +870,22 @@ static int spread_rows(Plan& P, float* src, float* norm, const int32_t* rows, lo
   return GCL_OK;
 }
 
-static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float** y_out, hipStream_t st) {
+struct FwdArgs {      // what a forward pass is given.  Its mode is stated here, once, and kept nowhere in the plan
+  const float* x;
+  bool eval;            // inference (gcl_plan_forward_eval): BatchNorm in eval mode folded into the convolution epilogue
+  void* const* bn;      // per BatchNorm -- training: running mean, variance; inference: scale, shift, mean, rstd (NULL: sizing)
+  bool repack;          // inference: max|W| and the packed kernels, which persist in the state buffer, are made again
+};
+
+// Head of a forward pass: the state of the pass reset, its amax slot pool, max|W| and the packed kernels
+static int forward_setup(Plan& P, const FwdArgs& a, hipStream_t st) {
   Arena& A = P.A;
-  const gcl_maps_desc& M = *P.maps;
   const size_t nw = P.worder.size();
   P.t.assign(P.n_tensors, TState());
   P.g.assign(P.n_tensors, TState());
   P.saved.assign(P.ops.size(), OpSaved());
-  if (P.profile && !A.dry) P.prof_used = 0;
-  if (!A.dry) P.events_used = 0;      // fork / join events are re-used pass after pass (recording re-arms them)      // records of a profiled pass stay readable until the next profiled pass
+  if (P.profile && !A.dry) P.prof_used = 0;      // records of a profiled pass stay readable until the next profiled pass
+  if (!A.dry) P.events_used = 0;
   // amax slots of the pass: one zero fill (ops.amax_slot hands out slots of a zero-filled pool)
   P.n_slots = 4 * (long long)P.n_tensors + 2 * (long long)P.ops.size() + 16;
   P.next_slot = 0;
@@ -857,7 +895,7 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
   P.slot_pool = A.take_n<int32_t>(P.n_slots * GCL_AMAX_WORDS);
   if (!A.dry) GCL_CHECK_HIP(hipMemsetAsync(P.slot_pool, 0, (size_t)P.n_slots * GCL_AMAX_WORDS * sizeof(int32_t), st));
   // all convolution kernels: max|W| in one launch, forward packs in one launch (WeightAmaxGroup)
-  if (P.eval) {      // inference: max|W| and the packed kernels persist in the caller's state buffer from pass to pass
+  if (a.eval) {      // inference: max|W| and the packed kernels persist in the caller's state buffer from pass to pass
     char* base = (char*)P.state + ((state_words(P) * 8 + 255) & ~255ll);
     P.w_amax = (int32_t*)base;
     P.pack_fwd = (unsigned char*)(base + (((long long)nw * GCL_AMAX_WORDS * 4 + 255) & ~255ll));
@@ -866,240 +904,246 @@ static int plan_forward(Plan& P, const float* x_in, void* const* bn_stats, float
     P.pack_fwd = (unsigned char*)A.take(P.bytes_fwd);
   }
   P.bwd_packed = false;
+  const bool on_aux = !a.eval && P.aux && P.n_bwd;      // training with an aux stream: the packs are made there
+  const long long* tab = (const long long*)P.state;
   if (nw && !A.dry) {
     int rc = upload_tables(P, st);
     if (rc) return rc;
-    if (!P.eval || P.eval_repack) {
-      const long long* tab = (const long long*)P.state;
-      // training with an aux stream: max|W| and the forward packs are made THERE, beside the first layer (whose kernels
-      // read the fp32 weights); the main stream waits for them in front of its first packed convolution (conv_forward)
-      hipStream_t ps = st;
-      if (!P.eval && P.aux && P.n_bwd) ps = fork_aux(P, st);
+    if (!a.eval || a.repack) {
+      // on the aux stream max|W| and the forward packs are made beside the first layer (whose kernels read the fp32
+      // weights); the main stream waits for them in front of its first packed convolution (conv_prepare)
+      hipStream_t ps = on_aux ? fork_aux(P, st) : st;
       PLAN_CALL(gcl_amax_multi((const float* const*)tab, (const int64_t*)(tab + nw), (int32_t)nw, P.w_amax, (void*)ps));
       PLAN_CALL(gcl_pack_weights_multi((const int64_t*)(tab + 2 * nw), (int32_t)nw, P.wgs_fwd, 4, P.w_amax, P.pack_fwd, (void*)ps));
       if (ps != st) {
-        if (P.events_used == P.events.size()) {
-          hipEvent_t e;
-          GCL_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          P.events.push_back(e);
-        }
-        P.fwd_packs = P.events[P.events_used++];
+        GCL_CHECK_HIP(next_event(P, &P.fwd_packs));
         GCL_CHECK_HIP(hipEventRecord(P.fwd_packs, ps));
         P.fwd_packs_pending = true;
       }
     }
   }
-  // with an aux stream the input-gradient packs (needed by the first record of the backward pass) are made there now,
-  // beside the forward convolutions, instead of at the head of the backward pass
-  if (!P.eval && P.aux && P.n_bwd) {
+  // ... and so are the input-gradient packs (needed by the first record of the backward pass): now, beside the forward
+  // convolutions, instead of at the head of the backward pass
+  if (on_aux) {
     P.pack_bwd = (unsigned char*)A.take(P.bytes_bwd);
     if (!A.dry) {
       hipStream_t ws = fork_aux(P, st);
-      const long long* tab = (const long long*)P.state;
       PLAN_CALL(gcl_pack_weights_multi((const int64_t*)(tab + 2 * nw + 8 * nw), P.n_bwd, P.wgs_bwd, 4, P.w_amax, P.pack_bwd,
                                        (void*)ws));
     }
     P.bwd_packed = true;
   }
-  P.t[0].ptr = (float*)x_in;
-  // maps of a split build (gcl_maps_build_split): the first record that uses a map made on the side stream waits for it
-  bool late_pending = !A.dry && M.ready_event && M.late_mask;
-  for (size_t i = 0; i < P.ops.size(); ++i) {
-    const gcl_plan_op& op = P.ops[i];
-    // touched-row suffix on the rows of the pass's list: its input gathered once (the dense tensor's max-abs slot bounds the
-    // rows picked from it: no gcl_amax pass), then the records below with fwd_cap rows
-    const bool compact = P.fwd_cap > 0 && (int)i >= P.suffix_first;
-    const long long n_out = compact ? P.fwd_cap : M.n_rows[op.level_out];
-    if (compact && (int)i == P.suffix_first) {
-      TState& xs = P.t[op.x];
-      NEED_F32(xs, i, "the input of the touched-row suffix");
-      float* cx = A.take_n<float>(P.fwd_cap * op.cin);
-      PLAN_CALL(gcl_gather_rows(xs.ptr, xs.ld ? xs.ld : op.cin, M.n_rows[op.level_in], P.fwd_rows, P.fwd_cap, op.cin, 0.f, cx,
-                                (void*)st));
-      int32_t* slot = xs.amax;
-      xs = TState();      // nothing but the suffix reads this tensor, in either pass
-      xs.ptr = cx;
-      xs.amax = slot;
-    }
-    if (late_pending && (op.kind == GCL_OP_CONVBN || op.kind == GCL_OP_CONV) && ((M.late_mask >> op.map) & 1)) {
-      GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));
-      late_pending = false;
-    }
-    TState& y = P.t[op.y];
-    int rc;
-    switch (op.kind) {
-      case GCL_OP_CONVBN: {
-        if (P.eval) {      // ME.conv_bn in inference (ops.conv_bn_eval): conv + BatchNorm(running stats) + residual + ReLU, one launch
-          const gcl_map_desc& m = M.maps[op.map];
-          const long long n_in = M.n_rows[op.level_in];
-          TState& x = P.t[op.x];
-          const int c = op.cout;
-          const float* res = op.x2 >= 0 ? P.t[op.x2].ptr : nullptr;
-          NEED_F32(x, i, "its input (inference)");      // (an inference pass keeps every tensor in fp32: never taken)
-          if (op.x2 >= 0) NEED_F32(P.t[op.x2], i, "its residual operand");
-          y.ptr = A.take_n<float>(n_out * c);
-          y.amax = new_slot(P);
-          void* const* be = P.bn_eval ? P.bn_eval + 4 * op.bn : nullptr;
-          if (is_stem(op, m)) {      // the Cin <= 4 first layer: VALU convolution, then the BatchNorm apply pass
-            float* cy = A.take_n<float>(n_out * c);
-            unsigned long long* mask = op.relu ? A.take_n<unsigned long long>(gcl_bn_mask_len(n_out, c)) : nullptr;
-            if ((rc = stem_flag(P, op, m, x, n_in, st))) return rc;
-            PLAN_CALL(gcl_stem_fwd(x.ptr, (const float*)P.params[op.w], m.nbr, n_out, op.K, op.cin, c, cy, m.presence,
-                                   m.presence ? P.not_ones : nullptr, (void*)st));
-            PLAN_CALL(gcl_bn_apply(cy, n_out, c, (const float*)be[2], (const float*)be[3], (const float*)P.params[op.bn_w],
-                                   (const float*)P.params[op.bn_b], res, op.relu, y.ptr, (uint64_t*)mask, y.amax, (void*)st));
-            break;
-          }
-          const int wi = P.widx[op.w];
-          if ((rc = ensure_amax(P, x, n_in * op.cin, st, (int)i))) return rc;
-          const SortedTable T = sorted_table(m, op.transpose);
-          GCL_CHECK_ARG(A.dry || m.kernel_size == 1 || T.tbl,
-                        "gcl_plan_forward_eval: record %d needs a sorted table the maps do not carry", (int)i);
-          // scratch of the offset-group launches (small deep layers of an inference pass; 0: the shape / size takes another kernel)
-          const long long gs_len = T.tbl ? gcl_conv_fwd_groups_scratch_len(n_out, op.K, op.cin, c) : 0;
-          float* gscratch = gs_len > 0 ? A.take_n<float>(gs_len) : nullptr;
-          ProfScope ps(P, st, 0, (double)(m.kernel_size > 1 ? m.n_pairs : n_out), op.cin, c, n_in, n_out, op.K);
-          PLAN_CALL(gcl_conv_fwd_fused(x.ptr, n_in, 0, P.pack_fwd + P.off_fwd[wi], 4, x.amax,
-                                       P.w_amax + (long long)wi * GCL_AMAX_WORDS, T.tbl, T.order, T.mask, n_out, op.K, op.cin, c,
-                                       (const float*)be[1], (const float*)be[0], res, op.relu, y.amax, y.ptr, gscratch,
-                                       GCL_CONV_TALL, (void*)st));
-          break;
-        }
-        float *cy, *stats;
-        int32_t* unused_slot;
-        if ((rc = conv_forward(P, (int)i, &cy, &stats, st, &unused_slot))) return rc;
-        OpSaved& sv = P.saved[i];
-        sv.conv_out = cy;
-        const int c = op.cout;
-        float* mr = A.take_n<float>(2 * c);
-        sv.mean = mr;
-        sv.rstd = mr + c;
-        float* rm = (float*)bn_stats[2 * op.bn];
-        float* rv = (float*)bn_stats[2 * op.bn + 1];
-        // Bound mode (round 5): this BatchNorm's output is at least `presplit` channels wide, i.e. its consumers read a
-        // plane image: the statistics launch bounds max|y| from the epilogue's column ranges and the apply pass writes the
-        // image itself -- into the image of the ME.cat it writes in place, if so (no gcl_split_planes pass; ops.py mirrors the
-        // slot values: _BatchNormFn, cat_features).  Needs the residual's / the cat partner's max-abs slots, which their
-        // producers have published.
-        const int32_t* res_amax = op.x2 >= 0 ? P.t[op.x2].amax : nullptr;
-        const int32_t* cat_amax = P.cat_left[i] >= 0 ? P.t[P.ops[P.cat_left[i]].x2].amax : nullptr;
-        const bool bound = stats && c >= P.presplit && (c % 32) == 0 && (op.x2 < 0 || res_amax) &&
-                           (P.cat_left[i] < 0 || (cat_amax && (P.ops[P.cat_left[i]].cout % 32) == 0));
-        int32_t* bound_slot = bound ? new_slot(P) : nullptr;
-        if (stats) {       // column sums (and ranges) from the convolution epilogue
-          const long long nt = cdiv(n_out, 128);
-          if (bound) sv.xrange = A.take_n<float>(2 * c);
-          PLAN_CALL(gcl_bn_stats_from_tiles_range(stats, nt, n_out, c, op.eps, op.momentum, rm, rv, sv.mean, sv.rstd, sv.xrange,
-                                                  (const float*)P.params[op.bn_w], (const float*)P.params[op.bn_b], op.relu,
-                                                  res_amax, cat_amax, bound_slot, (void*)st));
-        } else {
-          double* scratch = A.take_n<double>(gcl_bn_scratch_len(n_out, c));
-          PLAN_CALL(gcl_bn_stats(cy, n_out, c, op.eps, op.momentum, rm, rv, scratch, sv.mean, sv.rstd, (void*)st));
-        }
-        if (P.cat_left[i] >= 0) {
-          // y is only the left input of an ME.cat: written straight into the cat's output (row pitch = its width); the
-          // cat record then copies the other input's columns only.  max|y| goes to the cat's slot (the right half adds its own)
-          const gcl_plan_op& cat = P.ops[P.cat_left[i]];
-          TState& cty = P.t[cat.y];
-          cty = TState();
-          cty.ptr = A.take_n<float>(n_out * cat.cout);
-          cty.amax = bound ? bound_slot : new_slot(P);
-          if (bound) cty.planes = A.take(n_out * cat.cout * 4);
-          y.ptr = cty.ptr;
-          y.ld = cat.cout;
-          y.amax = cty.amax;
-          y.planes = nullptr;      // the image belongs to the cat (this tensor's only consumer)
-        } else {
-          // plane-only: every reader of y takes the image (plane_only_analysis) -- no fp32 block in the arena, no fp32 store
-          y.plane_only = bound && !P.keep_twins && P.po_fwd[i];
-          y.ptr = y.plane_only ? nullptr : A.take_n<float>(n_out * c);
-          y.ld = 0;
-          y.amax = bound ? bound_slot : new_slot(P);
-          if (bound) y.planes = A.take(n_out * c * 4);
-        }
-        if (op.relu) sv.mask = A.take_n<unsigned long long>(gcl_bn_mask_len(n_out, c));
-        if (op.x2 >= 0) NEED_F32(P.t[op.x2], i, "its residual operand");
-        const float* res = op.x2 >= 0 ? P.t[op.x2].ptr : nullptr;
-        void* img = !bound ? nullptr : (P.cat_left[i] >= 0 ? P.t[P.ops[P.cat_left[i]].y].planes : y.planes);
-        PLAN_CALL(gcl_bn_apply_planes(cy, n_out, c, sv.mean, sv.rstd, (const float*)P.params[op.bn_w],
-                                      (const float*)P.params[op.bn_b], res, op.relu, y.ptr, y.ld, (uint64_t*)sv.mask, y.amax,
-                                      img, (void*)st));
-        break;
-      }
-      case GCL_OP_CONV: {
-        float *cy, *stats;
-        int32_t* relu_amax;
-        if ((rc = conv_forward(P, (int)i, &cy, &stats, st, &relu_amax, compact ? P.fwd_cap : 0))) return rc;
-        y.ptr = cy;
-        if (relu_amax) {      // the epilogue applied the ReLU record that follows: both tensor ids name relu(conv(x))
-          y.amax = relu_amax;
-          P.t[P.ops[i + 1].y] = y;
-        }
-        break;
-      }
-      case GCL_OP_RELU: {
-        if (i > 0 && P.fuse_relu[i - 1]) {      // written by the convolution in front of it
-          if (compact) y = P.t[op.x];           // (the gathered rows of it when the suffix starts here)
-          break;
-        }
-        const long long n4 = n_out * op.cout / 4;
-        NEED_F32(P.t[op.x], i, "its input");
-        y.ptr = A.take_n<float>(n_out * op.cout);
-        y.amax = new_slot(P);        // published by the kernel itself: the consumer needs no gcl_amax pass
-        if (!A.dry) {
-          hipLaunchKernelGGL(k_relu_fwd, dim3(grid_for(n4)), dim3(256), 0, st, (const float4*)P.t[op.x].ptr, n4, (float4*)y.ptr,
-                             y.amax);
-          GCL_CHECK_LAUNCH();
-        }
-        break;
-      }
-      case GCL_OP_CAT: {
-        const int ca = op.cin, cb = op.cout - op.cin;
-        NEED_F32(P.t[op.x], i, "its left input");
-        NEED_F32(P.t[op.x2], i, "its right input");
-        if (P.t[op.x].ld == op.cout && P.t[op.x].ptr == y.ptr && y.ptr) {      // left input already in place (cat_left)
-          if (!A.dry) {
-            hipLaunchKernelGGL(k_cat_right, dim3(grid_for(n_out * cb / 4)), dim3(256), 0, st, (const float4*)P.t[op.x2].ptr,
-                               cb / 4, n_out, ca / 4, (float4*)y.ptr, y.amax, (unsigned short*)y.planes);
-            GCL_CHECK_LAUNCH();
-          }
-          break;
-        }
-        y.ptr = A.take_n<float>(n_out * op.cout);
-        y.amax = new_slot(P);
-        // max|cat| = the larger of the inputs' slots when both are known (ops.cat_features: a slot may hold a BatchNorm's
-        // bound instead of the measured maximum, and both paths must hand the consumers the same value); else measured
-        const int32_t *sa = P.t[op.x].amax, *sb = P.t[op.x2].amax;
-        if (!A.dry) {
-          const bool both = sa && sb;
-          hipLaunchKernelGGL(k_cat2, dim3(grid_for(n_out * op.cout / 4)), dim3(256), 0, st, (const float4*)P.t[op.x].ptr, ca / 4,
-                             (const float4*)P.t[op.x2].ptr, cb / 4, n_out, (float4*)y.ptr, y.amax, both ? (const int*)sa : nullptr,
-                             both ? (const int*)sb : nullptr);
-          GCL_CHECK_LAUNCH();
-        }
-        break;
-      }
-      case GCL_OP_ROWNORM: {
-        NEED_F32(P.t[op.x], i, "its input");
-        y.ptr = A.take_n<float>(n_out * op.cout);
-        P.saved[i].norm = A.take_n<float>(n_out);
-        PLAN_CALL(gcl_row_normalize_fwd(P.t[op.x].ptr, n_out, op.cout, y.ptr, P.saved[i].norm, (void*)st));
-        break;
-      }
-      default:
-        set_error("gcl_plan_forward: unknown record kind %d", op.kind);
-        return GCL_ERR_ARG;
-    }
+  P.t[0].ptr = (float*)a.x;
+  return GCL_OK;
+}
+
+// ME.conv_bn in a training pass (ops._SparseConvFn, ops._BatchNormFn): convolution, batch statistics, apply pass
+static int convbn_forward(Plan& P, int i, const gcl_plan_op& op, long long n_out, void* const* bn_stats, hipStream_t st) {
+  Arena& A = P.A;
+  const ConvOut conv = conv_forward(P, i, st);
+  if (conv.rc) return conv.rc;
+  OpSaved& sv = P.saved[i];
+  sv.conv_out = conv.y;
+  const int c = op.cout;
+  sv.mean = A.take_n<float>(2 * c);
+  sv.rstd = sv.mean + c;
+  float* rm = (float*)bn_stats[2 * op.bn];
+  float* rv = (float*)bn_stats[2 * op.bn + 1];
+  // y that is only the left input of an ME.cat is written straight into the cat's output (row pitch = its width); the cat
+  // record then copies the other input's columns only
+  const gcl_plan_op* cat = P.cat_left[i] >= 0 ? &P.ops[P.cat_left[i]] : nullptr;
+  // Bound mode (round 5): this BatchNorm's output is at least `presplit` channels wide, i.e. its consumers read a
+  // plane image: the statistics launch bounds max|y| from the epilogue's column ranges and the apply pass writes the
+  // image itself -- into the image of the ME.cat it writes in place, if so (no gcl_split_planes pass; ops.py mirrors the
+  // slot values: _BatchNormFn, cat_features).  Needs the residual's / the cat partner's max-abs slots, which their
+  // producers have published.
+  const int32_t* res_amax = op.x2 >= 0 ? P.t[op.x2].amax : nullptr;
+  const int32_t* cat_amax = cat ? P.t[cat->x2].amax : nullptr;
+  const bool bound = conv.stats && c >= P.presplit && (c % 32) == 0 && (op.x2 < 0 || res_amax) &&
+                     (!cat || (cat_amax && (cat->cout % 32) == 0));
+  int32_t* bound_slot = bound ? new_slot(P) : nullptr;
+  if (conv.stats) {       // column sums (and ranges) from the convolution epilogue
+    if (bound) sv.xrange = A.take_n<float>(2 * c);
+    PLAN_CALL(gcl_bn_stats_from_tiles_range(conv.stats, cdiv(n_out, 128), n_out, c, op.eps, op.momentum, rm, rv, sv.mean, sv.rstd,
+                                            sv.xrange, (const float*)P.params[op.bn_w], (const float*)P.params[op.bn_b], op.relu,
+                                            res_amax, cat_amax, bound_slot, (void*)st));
+  } else {
+    double* scratch = A.take_n<double>(gcl_bn_scratch_len(n_out, c));
+    PLAN_CALL(gcl_bn_stats(conv.y, n_out, c, op.eps, op.momentum, rm, rv, scratch, sv.mean, sv.rstd, (void*)st));
   }
-  if (late_pending) GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));      // (the arena outlives the side stream's work)
-  NEED_F32(P.t[P.ops.back().y], P.ops.size() - 1, "its output (the caller's)");
-  *y_out = P.t[P.ops.back().y].ptr;
-  if (P.fwd_cap > 0) {      // the pass's output stays dense: the rows of the list hold the features, every other row is zero
-    const gcl_plan_op& last = P.ops.back();      // ... and the padding rows of a saved y and norm become (0, 1)
-    return spread_rows(P, *y_out, last.kind == GCL_OP_ROWNORM ? P.saved[P.ops.size() - 1].norm : nullptr, P.fwd_rows, P.fwd_cap,
-                       last.cout, M.n_rows[last.level_out], y_out, st);
+  // the tensor the apply pass writes: y, or the cat's output, which gets the slot of max|y| (the right half adds its own) and
+  // the image.  plane-only: every reader of y takes the image (analyse_graph) -- no fp32 block in the arena, no fp32 store
+  TState& y = P.t[op.y];
+  TState& dst = cat ? P.t[cat->y] : y;
+  const int width = cat ? cat->cout : c;
+  dst.plane_only = !cat && bound && !P.keep_twins && P.po_fwd[i];
+  dst.ptr = dst.plane_only ? nullptr : A.take_n<float>(n_out * width);
+  dst.amax = bound ? bound_slot : new_slot(P);
+  if (bound) dst.planes = A.take(n_out * width * 4);
+  if (cat) {      // y: a column slice of the cat; the image belongs to the cat (this tensor's only consumer)
+    y.ptr = dst.ptr;
+    y.ld = width;
+    y.amax = dst.amax;
+  }
+  if (op.relu) sv.mask = A.take_n<unsigned long long>(gcl_bn_mask_len(n_out, c));
+  if (op.x2 >= 0) NEED_F32(P.t[op.x2], i, "its residual operand");
+  PLAN_CALL(gcl_bn_apply_planes(conv.y, n_out, c, sv.mean, sv.rstd, (const float*)P.params[op.bn_w],
+                                (const float*)P.params[op.bn_b], op.x2 >= 0 ? P.t[op.x2].ptr : nullptr, op.relu, y.ptr, y.ld,
+                                (uint64_t*)sv.mask, y.amax, bound ? dst.planes : nullptr, (void*)st));
+  return GCL_OK;
+}
+
+// ME.conv_bn in inference (ops.conv_bn_eval): conv + BatchNorm(running stats) + residual + ReLU, one launch
+static int convbn_forward_eval(Plan& P, int i, const gcl_plan_op& op, long long n_out, void* const* bn_eval, hipStream_t st) {
+  Arena& A = P.A;
+  const long long n_in = P.maps->n_rows[op.level_in];
+  TState& y = P.t[op.y];
+  const int c = op.cout;
+  const float* res = op.x2 >= 0 ? P.t[op.x2].ptr : nullptr;
+  if (op.x2 >= 0) NEED_F32(P.t[op.x2], i, "its residual operand");
+  y.ptr = A.take_n<float>(n_out * c);
+  y.amax = new_slot(P);
+  void* const* be = bn_eval ? bn_eval + 4 * op.bn : nullptr;      // scale, shift, mean, rstd
+  int rc;
+  if (stem_shape(op)) {      // the first layer: VALU convolution, then the BatchNorm apply pass
+    float* cy = A.take_n<float>(n_out * c);
+    unsigned long long* mask = op.relu ? A.take_n<unsigned long long>(gcl_bn_mask_len(n_out, c)) : nullptr;
+    if ((rc = stem_forward(P, i, n_in, n_out, cy, st))) return rc;
+    PLAN_CALL(gcl_bn_apply(cy, n_out, c, (const float*)be[2], (const float*)be[3], (const float*)P.params[op.bn_w],
+                           (const float*)P.params[op.bn_b], res, op.relu, y.ptr, (uint64_t*)mask, y.amax, (void*)st));
+    return GCL_OK;
+  }
+  if ((rc = conv_prepare(P, i, n_in, "gcl_plan_forward_eval", st))) return rc;
+  // scratch of the offset-group launches (small deep layers of an inference pass; 0: the shape / size takes another kernel)
+  const bool walks = sorted_table(P.maps->maps[op.map], op.transpose).tbl != nullptr;
+  const long long gs_len = walks ? gcl_conv_fwd_groups_scratch_len(n_out, op.K, op.cin, c) : 0;
+  float* gscratch = gs_len > 0 ? A.take_n<float>(gs_len) : nullptr;
+  return conv_launch(P, i, false, n_in, n_out, be ? (const float*)be[1] : nullptr, be ? (const float*)be[0] : nullptr, res,
+                     op.relu, y.amax, y.ptr, gscratch, GCL_CONV_TALL, st);
+}
+
+// compact: the record belongs to the touched-row suffix of a pass that runs it on the n_out rows of its list
+static int relu_forward(Plan& P, int i, const gcl_plan_op& op, long long n_out, bool compact, hipStream_t st) {
+  Arena& A = P.A;
+  TState& y = P.t[op.y];
+  if (i > 0 && P.fuse_relu[i - 1]) {      // written by the convolution in front of it
+    if (compact) y = P.t[op.x];           // (the gathered rows of it when the suffix starts here)
+    return GCL_OK;
+  }
+  const long long n4 = n_out * op.cout / 4;
+  NEED_F32(P.t[op.x], i, "its input");
+  y.ptr = A.take_n<float>(n_out * op.cout);
+  y.amax = new_slot(P);        // published by the kernel itself: the consumer needs no gcl_amax pass
+  if (!A.dry) {
+    hipLaunchKernelGGL(k_relu_fwd, dim3(grid_for(n4)), dim3(256), 0, st, (const float4*)P.t[op.x].ptr, n4, (float4*)y.ptr, y.amax);
+    GCL_CHECK_LAUNCH();
   }
   return GCL_OK;
+}
+
+static int cat_forward(Plan& P, int i, const gcl_plan_op& op, long long n_out, hipStream_t st) {
+  Arena& A = P.A;
+  const TState &xa = P.t[op.x], &xb = P.t[op.x2];
+  TState& y = P.t[op.y];
+  const int ca = op.cin, cb = op.cout - op.cin;
+  NEED_F32(xa, i, "its left input");
+  NEED_F32(xb, i, "its right input");
+  if (xa.ld == op.cout && xa.ptr == y.ptr && y.ptr) {      // left input already in place (cat_left)
+    if (!A.dry) {
+      hipLaunchKernelGGL(k_cat_right, dim3(grid_for(n_out * cb / 4)), dim3(256), 0, st, (const float4*)xb.ptr, cb / 4, n_out,
+                         ca / 4, (float4*)y.ptr, y.amax, (unsigned short*)y.planes);
+      GCL_CHECK_LAUNCH();
+    }
+    return GCL_OK;
+  }
+  y.ptr = A.take_n<float>(n_out * op.cout);
+  y.amax = new_slot(P);
+  // max|cat| = the larger of the inputs' slots when both are known (ops.cat_features: a slot may hold a BatchNorm's
+  // bound instead of the measured maximum, and both paths must hand the consumers the same value); else measured
+  const bool both = xa.amax && xb.amax;
+  if (!A.dry) {
+    hipLaunchKernelGGL(k_cat2, dim3(grid_for(n_out * op.cout / 4)), dim3(256), 0, st, (const float4*)xa.ptr, ca / 4,
+                       (const float4*)xb.ptr, cb / 4, n_out, (float4*)y.ptr, y.amax, both ? (const int*)xa.amax : nullptr,
+                       both ? (const int*)xb.amax : nullptr);
+    GCL_CHECK_LAUNCH();
+  }
+  return GCL_OK;
+}
+
+static int rownorm_forward(Plan& P, int i, const gcl_plan_op& op, long long n_out, hipStream_t st) {
+  Arena& A = P.A;
+  NEED_F32(P.t[op.x], i, "its input");
+  float* y = P.t[op.y].ptr = A.take_n<float>(n_out * op.cout);
+  P.saved[i].norm = A.take_n<float>(n_out);
+  PLAN_CALL(gcl_row_normalize_fwd(P.t[op.x].ptr, n_out, op.cout, y, P.saved[i].norm, (void*)st));
+  return GCL_OK;
+}
+
+// the forward pass of record i.  rows > 0: a record of the touched-row suffix, on the rows of the pass's list
+static int forward_record(Plan& P, int i, const FwdArgs& a, long long rows, hipStream_t st) {
+  const gcl_plan_op& op = P.ops[i];
+  const long long n_out = rows > 0 ? rows : P.maps->n_rows[op.level_out];
+  switch (op.kind) {
+    case GCL_OP_CONVBN: return a.eval ? convbn_forward_eval(P, i, op, n_out, a.bn, st) : convbn_forward(P, i, op, n_out, a.bn, st);
+    case GCL_OP_CONV: return conv_forward(P, i, st, rows).rc;
+    case GCL_OP_RELU: return relu_forward(P, i, op, n_out, rows > 0, st);
+    case GCL_OP_CAT: return cat_forward(P, i, op, n_out, st);
+    case GCL_OP_ROWNORM: return rownorm_forward(P, i, op, n_out, st);
+  }
+  set_error("gcl_plan_forward: unknown record kind %d", op.kind);
+  return GCL_ERR_ARG;
+}
+
+// Head of the touched-row suffix on the rows of the pass's list: its input gathered once (the dense tensor's max-abs slot
+// bounds the rows picked from it: no gcl_amax pass); the records of the suffix then run with fwd_cap rows
+static int suffix_gather(Plan& P, hipStream_t st) {
+  Arena& A = P.A;
+  const gcl_plan_op& op = P.ops[P.suffix_first];
+  TState& xs = P.t[op.x];
+  NEED_F32(xs, P.suffix_first, "the input of the touched-row suffix");
+  float* cx = A.take_n<float>(P.fwd_cap * op.cin);
+  PLAN_CALL(gcl_gather_rows(xs.ptr, xs.ld ? xs.ld : op.cin, P.maps->n_rows[op.level_in], P.fwd_rows, P.fwd_cap, op.cin, 0.f, cx,
+                            (void*)st));
+  int32_t* slot = xs.amax;
+  xs = TState();      // nothing but the suffix reads this tensor, in either pass
+  xs.ptr = cx;
+  xs.amax = slot;
+  return GCL_OK;
+}
+
+// maps of a split build (gcl_maps_build_split): the first record that uses a map made on the side stream waits for it
+static int late_maps_wait(const gcl_maps_desc& M, const gcl_plan_op& op, bool* pending, hipStream_t st) {
+  if (!is_conv(op) || !((M.late_mask >> op.map) & 1)) return GCL_OK;
+  GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));
+  *pending = false;
+  return GCL_OK;
+}
+
+// The last record's output for the caller.  A pass that ran the suffix on a list hands out a dense tensor all the same: the
+// rows of the list hold the features, every other row is zero -- and the padding rows of a saved y and norm become (0, 1)
+static int forward_output(Plan& P, float** y_out, hipStream_t st) {
+  const int last = (int)P.ops.size() - 1;
+  const gcl_plan_op& op = P.ops[last];
+  NEED_F32(P.t[op.y], last, "its output (the caller's)");
+  *y_out = P.t[op.y].ptr;
+  if (P.fwd_cap <= 0) return GCL_OK;
+  return spread_rows(P, *y_out, op.kind == GCL_OP_ROWNORM ? P.saved[last].norm : nullptr, P.fwd_rows, P.fwd_cap, op.cout,
+                     P.maps->n_rows[op.level_out], y_out, st);
+}
+
+static int plan_forward(Plan& P, const FwdArgs& a, float** y_out, hipStream_t st) {
+  const gcl_maps_desc& M = *P.maps;
+  int rc = forward_setup(P, a, st);
+  if (rc) return rc;
+  bool late_pending = !P.A.dry && M.ready_event && M.late_mask;
+  for (int i = 0; i < (int)P.ops.size(); ++i) {
+    const long long rows = (P.fwd_cap > 0 && i >= P.suffix_first) ? P.fwd_cap : 0;
+    if (rows > 0 && i == P.suffix_first && (rc = suffix_gather(P, st))) return rc;
+    if (late_pending && (rc = late_maps_wait(M, P.ops[i], &late_pending, st))) return rc;
+    if ((rc = forward_record(P, i, a, rows, st))) return rc;
+  }
+  if (late_pending) GCL_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)M.ready_event, 0));      // (the arena outlives the side stream's work)
+  return forward_output(P, y_out, st);
 }
 
 struct RowView {
@@ -1234,7 +1278,7 @@ static int conv_backward(Plan& P, int i, TState dy, RowView& V, void* const* gra
   TState& x = P.t[op.x];
   float* dW = (float*)grads[op.w];
   int rc;
-  if (is_stem(op, m)) {
+  if (stem_shape(op)) {
     NEED_F32(x, i, "its input (first layer)");
     NEED_F32(dy, i, "its output gradient (first layer)");
     float* scratch = A.take_n<float>(gcl_stem_bwd_weight_scratch_len(op.K, op.cin, op.cout, n_out));
@@ -1363,9 +1407,9 @@ static int backward_record(Plan& P, int i, RowView& V, void* const* grads, hipSt
       float* sum_gx = (float*)grads[op.bn_w];
       double* scratch = A.take_n<double>(gcl_bn_scratch_len(n_out, c));
       // bound mode: dx is read as a plane image by the input gradient (and by the weight gradient when both widths allow)
-      const bool bound = sv.xrange && c >= P.presplit && !is_stem(op, M.maps[op.map]);
+      const bool bound = sv.xrange && c >= P.presplit && !stem_shape(op);
       // plane-only: the input gradient and the weight gradient of this record both read dx as a plane image
-      // (plane_only_analysis) -- no fp32 block, no fp32 store.  The row-list apply pass keeps its fp32 dx: the analysis
+      // (analyse_graph) -- no fp32 block, no fp32 store.  The row-list apply pass keeps its fp32 dx: the analysis
       // leaves out every record a compact gradient can reach
       TState d;
       d.plane_only = bound && !P.keep_twins && P.po_bwd[i];
@@ -1471,9 +1515,8 @@ static int suffix_backward(Plan& P, const float* dy, void* const* grads, RowView
 }
 
 static int tensor_width(const Plan& P, int tensor) {      // channels of a tensor a record of the plan produces
-  for (const gcl_plan_op& op : P.ops)
-    if (op.y == tensor) return op.cout;
-  return 0;
+  const int maker = P.readers[tensor].maker;
+  return maker >= 0 ? P.ops[maker].cout : 0;
 }
 
 static int plan_backward(Plan& P, const float* dy, void* const* grads, int first, int last, hipStream_t st,
@@ -1559,30 +1602,129 @@ static int plan_backward(Plan& P, const float* dy, void* const* grads, int first
   return join_aux(P, st);      // the caller may hand the gradients of this segment to a collective / the optimizer next
 }
 
-// Reader analysis (gcl_plan_create): which tensors exist as a plane image only.  A CONVBN record in bound mode writes the
-// fp16 hi/lo image of its output y (forward apply pass) and of its BatchNorm input gradient dx (backward apply pass) beside
-// the fp32 tensor, the same number of bytes again.  The default is to keep the fp32 twin; it is dropped only when the record
-// can run in bound mode and EVERY reader provably takes the image:
-//   y  (po_fwd): each reader is a convolution record in front of the touched-row suffix with kernel size > 1 and both
-//                widths >= presplit -- its forward launch (cin >= presplit) and its pair-list weight gradient (pl_w) read
-//                x.planes.  Anything else keeps fp32: a residual operand or an ME.cat input (x2, the in-place cat_left
-//                case), a ReLU / row normalisation, a kernel_size-1 record (row-stream weight gradient), a narrow record
-//                (fp32 weight gradient), the ReLU-mask epilogue (mask_from), the first layer, the suffix (gathers fp32 rows),
-//                the plan's output (the caller's), a tensor nobody reads.
-//   dx (po_bwd): the tensor never leaves backward_record -- its readers are the record's own input gradient (cout >= presplit:
-//                the image) and weight gradient (the image iff pl_w: kernel size > 1, cin >= presplit), so it crosses no
-//                segment cut and reaches no give().  A bias gradient (gcl_col_sum) or the first layer would read fp32, and
-//                a record a compact gradient (TState::rv) can reach runs the row-list apply pass, which keeps its fp32 dx.
-// The passes re-check the run-time half (`bound`) and every fp32 read (NEED_F32): a reader this analysis overlooked is an
-// error return, not a null pointer in a kernel.
-static void plane_only_analysis(Plan& P) {
+// gcl_plan_create, step 1: the records name tensors in the order they are made and every parameter once, in shapes the
+// plan's kernels take.  Leaves made, widx and n_bn behind
+static int validate_records(Plan& P) {
+  for (size_t q = 0; q < P.worder.size(); ++q) {
+    const int p = P.worder[q];
+    GCL_CHECK_ARG(p >= 0 && p < P.n_params && P.widx[p] < 0, "gcl_plan_create: weight_order[%d] is no parameter id, or a second "
+                                                               "mention of one", (int)q);
+    P.widx[p] = (int)q;
+  }
+  std::vector<char> seen_param(P.n_params, 0);
+  auto claim = [&](int p) {       // every parameter belongs to exactly one record (its gradient is written, not added)
+    if (p < 0 || p >= P.n_params || seen_param[p]) return false;
+    seen_param[p] = 1;
+    return true;
+  };
+  auto tensor_ok = [&](int t) { return t >= 0 && t < P.n_tensors; };
+  for (int i = 0; i < (int)P.ops.size(); ++i) {
+    const gcl_plan_op& op = P.ops[i];
+    bool ok = tensor_ok(op.x) && tensor_ok(op.y) && op.y != 0 && !P.made[op.y] && (op.x == 0 || P.made[op.x]) &&
+              op.level_in >= 0 && op.level_in < GCL_MAX_LEVELS && op.level_out >= 0 && op.level_out < GCL_MAX_LEVELS &&
+              op.cin > 0 && op.cout > 0 && (op.x2 < 0 || (tensor_ok(op.x2) && P.made[op.x2]));
+    if (ok && is_conv(op)) {
+      ok = claim(op.w) && op.map >= 0 && op.map < GCL_MAX_MAPS && op.K >= 1 && op.K <= 125;
+      if (ok && op.bias >= 0) ok = claim(op.bias) && op.kind == GCL_OP_CONV;
+      if (ok && op.kind == GCL_OP_CONVBN) ok = claim(op.bn_w) && claim(op.bn_b) && op.bn >= 0 && op.cout % 4 == 0;
+      if (ok && op.kind == GCL_OP_CONVBN && op.bn + 1 > P.n_bn) P.n_bn = op.bn + 1;
+      // the first layer has no input gradient; MFMA shapes otherwise (generic VALU shapes stay on the per-operator path)
+      if (ok) ok = stem_shape(op) ? op.x == 0 : (op.cin % 32) == 0 && (op.cout % 32) == 0 && op.K <= 27 && P.widx[op.w] >= 0;
+    } else if (ok && op.kind == GCL_OP_CAT) {
+      ok = op.x2 >= 0 && op.cin % 4 == 0 && (op.cout - op.cin) > 0 && (op.cout - op.cin) % 4 == 0 && op.level_in == op.level_out;
+    } else if (ok) {
+      ok = (op.kind == GCL_OP_RELU || op.kind == GCL_OP_ROWNORM) && op.cin == op.cout && op.cout % 4 == 0 && op.level_in == op.level_out;
+    }
+    GCL_CHECK_ARG(ok, "gcl_plan_create: record %d is malformed, or of a kind or shape the plan does not take", i);
+    P.made[op.y] = 1;
+  }
+  return GCL_OK;
+}
+
+// step 2: per kernel of weight_order its shape, its input-gradient pack mode and its place in the packs
+static int weight_tables(Plan& P) {
+  for (const gcl_plan_op& op : P.ops) {
+    if (!is_conv(op) || stem_shape(op)) continue;
+    const int q = P.widx[op.w];
+    P.wK[q] = op.K; P.wcin[q] = op.cin; P.wcout[q] = op.cout;
+    // input-gradient layout recorded by the forward pass: mirrored offsets on a stride-1 map, plain transpose otherwise
+    // (the caller tells stride-1 3^3 / 5^3 maps apart through `transpose` and level_in == level_out)
+    if (op.x != 0) P.wmode[q] = (op.K > 1 && !op.transpose && op.level_in == op.level_out) ? 2 : 1;
+  }
+  for (size_t q = 0; q < P.worder.size(); ++q) {
+    GCL_CHECK_ARG(P.wK[q], "gcl_plan_create: weight_order names a parameter no record uses");
+    const long long bytes = (gcl_pack_weights_bytes((int)P.wK[q], (int)P.wcin[q], (int)P.wcout[q], 4) + 255) / 256 * 256;
+    P.off_fwd[q] = P.bytes_fwd;
+    P.bytes_fwd += bytes;
+    if (P.wmode[q]) {
+      P.off_bwd[q] = P.bytes_bwd;
+      P.bytes_bwd += bytes;
+      ++P.n_bwd;
+    }
+  }
+  return GCL_OK;
+}
+
+// step 3: who reads what, once, and the decisions both passes take from it
+static void analyse_graph(Plan& P) {
   const int n_ops = (int)P.ops.size();
+  P.readers.assign(P.n_tensors, Readers());
+  for (int i = 0; i < n_ops; ++i) {
+    const gcl_plan_op& o = P.ops[i];
+    P.readers[o.y].maker = i;
+    P.readers[o.x].x.push_back(i);
+    if (o.x2 >= 0) P.readers[o.x2].x2.push_back(i);
+  }
+  P.readers[P.ops.back().y].output = true;       // the plan's output keeps its own tensor
+  P.fuse_relu.assign(n_ops, 0);
+  P.cat_left.assign(n_ops, -1);
+  P.mask_from.assign(n_ops, -1);
+  for (int i = 0; i < n_ops; ++i) {
+    const gcl_plan_op& a = P.ops[i];
+    if (!is_conv(a) || a.cin <= 4) continue;
+    const Readers &out = P.readers[a.y], &in = P.readers[a.x];
+    const int next = out.x.empty() ? -1 : out.x[0];
+    // CONV directly followed by the RELU that alone reads it (model/resunet.py:222-224: conv1_tr, MEF.relu, final): the
+    // convolution's epilogue applies the ReLU and publishes max|y|
+    if (a.kind == GCL_OP_CONV && next == i + 1 && P.ops[next].kind == GCL_OP_RELU && out.only(next)) P.fuse_relu[i] = 1;
+    if (a.kind == GCL_OP_CONVBN && out.count() == 1 && !out.output && next > i && P.ops[next].kind == GCL_OP_CAT) P.cat_left[i] = next;
+    if (in.maker >= 0 && P.ops[in.maker].kind == GCL_OP_RELU && in.count() == 1 && !in.output) P.mask_from[i] = in.maker;
+  }
+  // touched-row suffix: the longest chain of row-local records that ends at the last record (each one the only reader of the
+  // record in front of it), cut at the front until nothing but the chain reads its input (model/resunet.py:222-230: conv1_tr,
+  // MEF.relu, final, the row normalisation -- behind the ME.cat)
+  auto row_local = [](const gcl_plan_op& o) {
+    return o.kind == GCL_OP_ROWNORM || o.kind == GCL_OP_RELU ||
+           (o.kind == GCL_OP_CONV && o.K == 1 && !o.transpose && o.level_in == o.level_out && o.cin > 4);
+  };
+  int s = n_ops;
+  while (s > 0 && row_local(P.ops[s - 1]) &&
+         (s == n_ops || (P.ops[s].x == P.ops[s - 1].y && P.readers[P.ops[s - 1].y].count() == 1)))
+    --s;
+  while (s < n_ops && P.readers[P.ops[s].x].count() != 1) ++s;
+  P.suffix_first = s;
+  P.suffix_rows_ok = true;
+  for (int i = s; i < n_ops; ++i)
+    if (P.ops[i].kind == GCL_OP_CONV && gcl_conv_bwd_weight_rows_scratch_len(P.ops[i].cin, P.ops[i].cout, 4, 128) <= 0)
+      P.suffix_rows_ok = false;
+  // Plane-only tensors: which tensors exist as a plane image only.  A CONVBN record in bound mode writes the
+  // fp16 hi/lo image of its output y (forward apply pass) and of its BatchNorm input gradient dx (backward apply pass) beside
+  // the fp32 tensor, the same number of bytes again.  The default is to keep the fp32 twin; it is dropped only when the record
+  // can run in bound mode and EVERY reader provably takes the image:
+  //   y  (po_fwd): each reader is a convolution record in front of the touched-row suffix with kernel size > 1 and both
+  //                widths >= presplit -- its forward launch (cin >= presplit) and its pair-list weight gradient (pl_w) read
+  //                x.planes.  Anything else keeps fp32: a residual operand or an ME.cat input (x2, the in-place cat_left
+  //                case), a ReLU / row normalisation, a kernel_size-1 record (row-stream weight gradient), a narrow record
+  //                (fp32 weight gradient), the ReLU-mask epilogue (mask_from), the first layer, the suffix (gathers fp32 rows),
+  //                the plan's output (the caller's), a tensor nobody reads.
+  //   dx (po_bwd): the tensor never leaves backward_record -- its readers are the record's own input gradient (cout >= presplit:
+  //                the image) and weight gradient (the image iff pl_w: kernel size > 1, cin >= presplit), so it crosses no
+  //                segment cut and reaches no give().  A bias gradient (gcl_col_sum) or the first layer would read fp32, and
+  //                a record a compact gradient (TState::rv) can reach runs the row-list apply pass, which keeps its fp32 dx.
+  // The passes re-check the run-time half (`bound`) and every fp32 read (NEED_F32): a reader this analysis overlooked is an
+  // error return, not a null pointer in a kernel.
   P.po_fwd.assign(n_ops, 0);
   P.po_bwd.assign(n_ops, 0);
-  auto stem_shape = [](const gcl_plan_op& o) { return o.cin <= 4 && (o.cout % 32) == 0 && !o.transpose && o.K > 1 && o.bias < 0; };
-  auto conv = [](const gcl_plan_op& o) { return o.kind == GCL_OP_CONVBN || o.kind == GCL_OP_CONV; };
-  std::vector<int> maker(P.n_tensors, -1);
-  for (int i = 0; i < n_ops; ++i) maker[P.ops[i].y] = i;
   // tensors whose gradient can arrive compact: the suffix's input, and from there the inputs of an ME.cat and the residual
   // operand of a CONVBN that takes a compact gradient (its dres stays compact) -- backward_record's rows_ok
   std::vector<char> may_rv(P.n_tensors, 0);
@@ -1595,25 +1737,23 @@ static void plane_only_analysis(Plan& P) {
   }
   for (int i = 0; i < n_ops && i < P.suffix_first; ++i) {
     const gcl_plan_op& o = P.ops[i];
-    // bound mode as plan_forward decides it: column ranges from the MFMA epilogue, a wide output, the residual's slot known
+    // bound mode as convbn_forward decides it: column ranges from the MFMA epilogue, a wide output, the residual's slot known
     bool bound = o.kind == GCL_OP_CONVBN && !stem_shape(o) && o.cout >= P.presplit && (o.cout % 32) == 0;
     if (bound && o.x2 >= 0) {
-      const int k = maker[o.x2] >= 0 ? P.ops[maker[o.x2]].kind : 0;
+      const int maker = P.readers[o.x2].maker;
+      const int k = maker >= 0 ? P.ops[maker].kind : 0;
       bound = k == GCL_OP_CONVBN || k == GCL_OP_RELU || k == GCL_OP_CAT;      // producers that publish max|x2|
     }
     if (!bound) continue;
     P.po_bwd[i] = o.K > 1 && o.cin >= P.presplit && o.bias < 0 && !may_rv[o.y];
-    bool ok = P.cat_left[i] < 0 && o.y != P.ops.back().y;
-    int readers = 0;
-    for (int j = 0; j < n_ops && ok; ++j) {
+    const Readers& R = P.readers[o.y];
+    bool ok = P.cat_left[i] < 0 && !R.output && R.x2.empty() && !R.x.empty();
+    for (int j : R.x) {
       const gcl_plan_op& r = P.ops[j];
-      if (r.x2 == o.y) ok = false;
-      if (r.x != o.y) continue;
-      ++readers;
-      ok = ok && j < P.suffix_first && conv(r) && !stem_shape(r) && r.K > 1 && r.cin >= P.presplit && r.cout >= P.presplit &&
+      ok = ok && j < P.suffix_first && is_conv(r) && !stem_shape(r) && r.K > 1 && r.cin >= P.presplit && r.cout >= P.presplit &&
            P.mask_from[j] < 0;
     }
-    P.po_fwd[i] = ok && readers > 0;
+    P.po_fwd[i] = ok;
   }
 }
 
@@ -1640,22 +1780,56 @@ using namespace gcl;
 
 extern "C" {
 
-// Dry run of a pass -- the forward pass, or the forward and the whole backward pass -- with P's maps, parameters and mode as
-// they stand: *need = the arena bytes it takes.  P.A and P.profile come back as they were.  bn_stats NULL: nobody reads them
-static int dry_pass(Plan& P, const float* x, void* const* bn_stats, bool backward, long long* need) {
+// Dry run of a pass -- the forward pass of inference, the forward and the whole backward pass of training -- with P's maps and
+// parameters as they stand: *need = the arena bytes it takes.  P.A comes back as it was.  Training with a.bn NULL: nobody reads them
+static int dry_pass(Plan& P, FwdArgs a, long long* need) {
   std::vector<void*> nulls(2 * (P.n_bn > 0 ? P.n_bn : 1), nullptr), gn(P.n_params, nullptr);
+  if (!a.eval && !a.bn) a.bn = nulls.data();
   const Arena real = P.A;
-  const bool prof = P.profile;
-  P.A = Arena{DRY_BASE, 0, 0, true};
-  P.profile = false;
+  P.A = Arena{DRY_BASE, 0, 0, true};      // (nothing is profiled in a dry run: ProfScope)
   float* y = nullptr;
-  int rc = plan_forward(P, x, bn_stats ? bn_stats : nulls.data(), &y, nullptr);
-  if (rc == GCL_OK && backward) rc = plan_backward(P, (const float*)DRY_BASE, gn.data(), 0, (int)P.ops.size(), nullptr);
+  int rc = plan_forward(P, a, &y, nullptr);
+  if (rc == GCL_OK && !a.eval) rc = plan_backward(P, (const float*)DRY_BASE, gn.data(), 0, (int)P.ops.size(), nullptr);
   *need = P.A.off;
   P.A = real;
-  P.profile = prof;
   P.relu_masked.clear();      // (a run that stopped early leaves no ReLU flagged as applied)
   return rc;
+}
+
+// Binds the plan to a pass (maps, parameters, state buffer, the fp32-twins setting) and sizes it by a dry run: *need.
+// With an arena the pass is about to be enqueued: the maps are copied -- the backward pass runs after the caller may have
+// released its descriptor -- and the pass must fit, so that nothing is launched into an arena that cannot hold it
+static int bind_pass(Plan& P, const char* who, const gcl_maps_desc* maps, void* const* params, void* state, void* arena,
+                     long long arena_bytes, const FwdArgs& a, long long* need) {
+  int rc = check_maps(P, maps);
+  if (rc) return rc;
+  P.maps = maps;
+  if (arena) {
+    P.maps_copy = *maps;
+    P.maps = &P.maps_copy;
+    P.A = Arena{(char*)arena, arena_bytes, 0, false};
+  }
+  if (params) P.params.assign(params, params + P.n_params);
+  else P.params.assign(P.n_params, nullptr);
+  P.state = state;
+  P.forward_done = false;
+  P.keep_twins = P.keep_fp32;      // parked with the pass: its backward pass follows the sizing made here
+  if ((rc = dry_pass(P, a, need))) return rc;
+  if (arena && *need > arena_bytes) {
+    set_error("%s: arena too small (%lld bytes needed, %lld given)", who, *need, arena_bytes);
+    return GCL_ERR_ARENA;
+  }
+  return GCL_OK;
+}
+
+// behind a pass that was enqueued: it stayed inside its arena and inside its amax slot pool (new_slot)
+static int check_pass(const Plan& P, const char* who) {
+  if (!P.A.fits()) {
+    set_error("%s: arena overrun", who);
+    return GCL_ERR_ARENA;
+  }
+  GCL_CHECK_ARG(!P.slots_exhausted, "%s: amax slot pool exhausted", who);
+  return GCL_OK;
 }
 
 // A forward pass waits for its backward pass in a slot of P.passes, under its arena: park moves the pass being enqueued
@@ -1723,140 +1897,13 @@ void* gcl_plan_create(const gcl_plan_op* ops_host, int32_t n_ops, int32_t n_tens
   P->worder.assign(weight_order_host, weight_order_host + n_weights);
   P->widx.assign(n_params, -1);
   P->made.assign(n_tensors, 0);
-  const size_t nw = (size_t)n_weights;
-  P->wmode.assign(nw, 0);
-  P->wK.assign(nw, 0);
-  P->wcin.assign(nw, 0);
-  P->wcout.assign(nw, 0);
-  P->off_fwd.assign(nw, 0);
-  P->off_bwd.assign(nw, 0);
-  bool ok = true;
-  for (int q = 0; q < n_weights && ok; ++q) {
-    const int p = weight_order_host[q];
-    ok = p >= 0 && p < n_params && P->widx[p] < 0;
-    if (ok) P->widx[p] = q;
-  }
-  std::vector<char> seen_param(n_params, 0);
-  for (int i = 0; i < n_ops && ok; ++i) {
-    const gcl_plan_op& op = P->ops[i];
-    auto tensor_ok = [&](int t) { return t >= 0 && t < n_tensors; };
-    ok = tensor_ok(op.x) && tensor_ok(op.y) && op.y != 0 && !P->made[op.y] && (op.x == 0 || P->made[op.x]) &&
-         op.level_in >= 0 && op.level_in < GCL_MAX_LEVELS && op.level_out >= 0 && op.level_out < GCL_MAX_LEVELS &&
-         op.cin > 0 && op.cout > 0;
-    if (!ok) break;
-    if (op.x2 >= 0) ok = tensor_ok(op.x2) && P->made[op.x2];
-    if (!ok) break;
-    auto claim = [&](int p) {       // every parameter belongs to exactly one record (its gradient is written, not added)
-      if (p < 0 || p >= n_params || seen_param[p]) return false;
-      seen_param[p] = 1;
-      return true;
-    };
-    if (op.kind == GCL_OP_CONVBN || op.kind == GCL_OP_CONV) {
-      ok = claim(op.w) && op.map >= 0 && op.map < GCL_MAX_MAPS && op.K >= 1 && op.K <= 125;
-      if (ok && op.bias >= 0) ok = claim(op.bias) && op.kind == GCL_OP_CONV;
-      if (ok && op.kind == GCL_OP_CONVBN) ok = claim(op.bn_w) && claim(op.bn_b) && op.bn >= 0 && op.cout % 4 == 0;
-      if (ok && op.kind == GCL_OP_CONVBN) P->n_bn = op.bn + 1 > P->n_bn ? op.bn + 1 : P->n_bn;
-      if (!ok) break;
-      const bool stem_shape = op.cin <= 4 && (op.cout % 32) == 0 && !op.transpose && op.K > 1 && op.bias < 0;
-      if (!stem_shape) {
-        // MFMA-shaped kernels only (the generic VALU shapes stay on the per-operator path)
-        ok = (op.cin % 32) == 0 && (op.cout % 32) == 0 && op.K <= 27 && P->widx[op.w] >= 0;
-        if (!ok) break;
-        const int q = P->widx[op.w];
-        P->wK[q] = op.K; P->wcin[q] = op.cin; P->wcout[q] = op.cout;
-        // input-gradient layout recorded by the forward pass: mirrored offsets on a stride-1 map, plain transpose otherwise
-        // (the caller tells stride-1 3^3 / 5^3 maps apart through `transpose` and level_in == level_out)
-        if (op.x != 0) P->wmode[q] = (op.K > 1 && !op.transpose && op.level_in == op.level_out) ? 2 : 1;
-      } else {
-        ok = op.x == 0;      // the Cin <= 4 first layer has no input gradient
-      }
-    } else if (op.kind == GCL_OP_CAT) {
-      ok = op.x2 >= 0 && op.cin % 4 == 0 && (op.cout - op.cin) > 0 && (op.cout - op.cin) % 4 == 0 && op.level_in == op.level_out;
-    } else if (op.kind == GCL_OP_RELU || op.kind == GCL_OP_ROWNORM) {
-      ok = op.cin == op.cout && op.cout % 4 == 0 && op.level_in == op.level_out;
-    } else {
-      ok = false;
-    }
-    P->made[op.y] = 1;
-  }
-  // CONV directly followed by the RELU that is its only consumer (model/resunet.py:222-224: conv1_tr, MEF.relu, final): the
-  // convolution's epilogue applies the ReLU and publishes max|y|
-  P->fuse_relu.assign(P->ops.size(), 0);
-  for (size_t i = 0; ok && i + 1 < P->ops.size(); ++i) {
-    const gcl_plan_op &a = P->ops[i], &b = P->ops[i + 1];
-    if (a.kind != GCL_OP_CONV || b.kind != GCL_OP_RELU || b.x != a.y || a.cin <= 4) continue;
-    bool other = a.y == P->ops.back().y;       // the plan's output keeps its own tensor
-    for (size_t j = 0; j < P->ops.size(); ++j)
-      if (j != i + 1 && (P->ops[j].x == a.y || P->ops[j].x2 == a.y)) other = true;
-    if (!other) P->fuse_relu[i] = 1;
-  }
-  P->cat_left.assign(P->ops.size(), -1);
-  for (size_t i = 0; ok && i < P->ops.size(); ++i) {
-    const gcl_plan_op& a = P->ops[i];
-    if (a.kind != GCL_OP_CONVBN || a.cin <= 4 || a.y == P->ops.back().y) continue;
-    int cat = -1, consumers = 0;
-    for (size_t j = 0; j < P->ops.size(); ++j) {
-      if (P->ops[j].kind == GCL_OP_CAT && P->ops[j].x == a.y && P->ops[j].x2 != a.y && j > i) cat = (int)j;
-      consumers += (P->ops[j].x == a.y) + (P->ops[j].x2 == a.y);
-    }
-    if (cat >= 0 && consumers == 1) P->cat_left[i] = cat;
-  }
-  P->mask_from.assign(P->ops.size(), -1);
-  for (size_t i = 0; ok && i < P->ops.size(); ++i) {
-    const gcl_plan_op& a = P->ops[i];
-    if ((a.kind != GCL_OP_CONV && a.kind != GCL_OP_CONVBN) || a.cin <= 4 || a.x == 0) continue;
-    int r = -1, consumers = 0;
-    for (size_t j = 0; j < P->ops.size(); ++j) {
-      if (P->ops[j].kind == GCL_OP_RELU && P->ops[j].y == a.x) r = (int)j;
-      consumers += (P->ops[j].x == a.x) + (P->ops[j].x2 == a.x);
-    }
-    if (r >= 0 && consumers == 1 && a.x != P->ops.back().y) P->mask_from[i] = r;
-  }
-  if (!ok) {
-    set_error("gcl_plan_create: malformed or unsupported operator records");
+  for (std::vector<long long>* v : {&P->wK, &P->wcin, &P->wcout, &P->off_fwd, &P->off_bwd}) v->assign((size_t)n_weights, 0);
+  P->wmode.assign((size_t)n_weights, 0);
+  if (validate_records(*P) != GCL_OK || weight_tables(*P) != GCL_OK) {      // (each has set its own error text)
     delete P;
     return nullptr;
   }
-  // touched-row suffix: the longest chain of row-local records that ends at the last record (each one the only reader of the
-  // record in front of it), cut at the front until nothing but the chain reads its input (model/resunet.py:222-230: conv1_tr,
-  // MEF.relu, final, the row normalisation -- behind the ME.cat)
-  {
-    auto consumers = [&](int t) {
-      int c = 0;
-      for (const gcl_plan_op& o : P->ops) c += (o.x == t) + (o.x2 == t);
-      return c;
-    };
-    auto row_local = [](const gcl_plan_op& o) {
-      return o.kind == GCL_OP_ROWNORM || o.kind == GCL_OP_RELU ||
-             (o.kind == GCL_OP_CONV && o.K == 1 && !o.transpose && o.level_in == o.level_out && o.cin > 4);
-    };
-    int s = n_ops;
-    while (s > 0 && row_local(P->ops[s - 1]) &&
-           (s == n_ops || (P->ops[s].x == P->ops[s - 1].y && consumers(P->ops[s - 1].y) == 1)))
-      --s;
-    while (s < n_ops && consumers(P->ops[s].x) != 1) ++s;
-    P->suffix_first = s;
-    P->suffix_rows_ok = true;
-    for (int i = s; i < n_ops; ++i)
-      if (P->ops[i].kind == GCL_OP_CONV && gcl_conv_bwd_weight_rows_scratch_len(P->ops[i].cin, P->ops[i].cout, 4, 128) <= 0)
-        P->suffix_rows_ok = false;
-  }
-  for (size_t q = 0; q < nw; ++q) {
-    if (!P->wK[q]) {
-      set_error("gcl_plan_create: weight_order names a parameter no record uses");
-      delete P;
-      return nullptr;
-    }
-    const long long bytes = (gcl_pack_weights_bytes((int)P->wK[q], (int)P->wcin[q], (int)P->wcout[q], 4) + 255) / 256 * 256;
-    P->off_fwd[q] = P->bytes_fwd;
-    P->bytes_fwd += bytes;
-    if (P->wmode[q]) {
-      P->off_bwd[q] = P->bytes_bwd;
-      P->bytes_bwd += bytes;
-      ++P->n_bwd;
-    }
-  }
-  plane_only_analysis(*P);
+  analyse_graph(*P);
   return P;
 }
 
@@ -1877,16 +1924,15 @@ int64_t gcl_plan_state_bytes(const void* plan) {
   return state_words(*(const Plan*)plan) * 8 + 256;
 }
 
-int64_t gcl_plan_arena_bytes(void* plan, const gcl_maps_desc* maps_host) {
-  Plan* P = (Plan*)plan;
-  if (!P || check_maps(*P, maps_host) != GCL_OK) return -1;
-  P->maps = maps_host;
-  P->params.assign(P->n_params, nullptr);
-  P->keep_twins = P->keep_fp32;
+static int64_t sized_pass(void* plan, const char* who, const gcl_maps_desc* maps_host, bool eval) {
   long long need = 0;
-  const int rc = dry_pass(*P, nullptr, nullptr, true, &need);
-  P->forward_done = false;
-  return rc == GCL_OK ? need + 4096 : -1;
+  if (!plan || bind_pass(*(Plan*)plan, who, maps_host, nullptr, DRY_BASE, nullptr, 0, FwdArgs{nullptr, eval, nullptr, true}, &need))
+    return -1;
+  return need + 4096;
+}
+
+int64_t gcl_plan_arena_bytes(void* plan, const gcl_maps_desc* maps_host) {
+  return sized_pass(plan, "gcl_plan_arena_bytes", maps_host, false);
 }
 
 int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x, void* const* params_host,
@@ -1894,22 +1940,10 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
                      void* stream) {
   Plan* P = (Plan*)plan;
   GCL_CHECK_ARG(P && maps_host && x && params_host && bn_stats_host && state && arena && y_out_host, "gcl_plan_forward: null pointer");
-  int rc = check_maps(*P, maps_host);
+  const FwdArgs a{x, false, bn_stats_host, true};
+  long long need = 0;      // (both passes)
+  int rc = bind_pass(*P, "gcl_plan_forward", maps_host, params_host, state, arena, arena_bytes, a, &need);
   if (rc) return rc;
-  P->maps_copy = *maps_host;        // the backward pass runs after the caller may have released its descriptor
-  P->maps = &P->maps_copy;
-  P->params.assign(params_host, params_host + P->n_params);
-  P->state = state;
-  P->A = Arena{(char*)arena, arena_bytes, 0, false};
-  P->forward_done = false;
-  P->keep_twins = P->keep_fp32;      // parked with the pass: its backward pass follows the sizing made here
-  // size check first (cheap dry run of both passes): never launch into an arena that cannot hold the pass
-  long long need = 0;
-  if ((rc = dry_pass(*P, x, bn_stats_host, true, &need))) return rc;
-  if (need > arena_bytes) {
-    set_error("gcl_plan_forward: arena too small (%lld bytes needed, %lld given)", need, (long long)arena_bytes);
-    return GCL_ERR_ARENA;
-  }
   // a list handed over before the pass: the touched-row suffix runs on its rows in this pass too, under the rules of the
   // backward pass -- a suffix, shapes the row-stream weight gradient takes, 2 cap < n_rows, and room in the arena for both
   // passes (the same calls, counted)
@@ -1919,12 +1953,13 @@ int gcl_plan_forward(void* plan, const gcl_maps_desc* maps_host, const float* x,
       2 * P->touched_cap < maps_host->n_rows[P->ops[P->suffix_first].level_in]) {
     P->fwd_rows = P->touched;
     P->fwd_cap = P->touched_cap;
-    if (dry_pass(*P, x, bn_stats_host, true, &need) != GCL_OK || need > arena_bytes) {
+    if (dry_pass(*P, a, &need) != GCL_OK || need > arena_bytes) {
       P->fwd_rows = nullptr;
       P->fwd_cap = 0;
     }
   }
-  rc = plan_forward(*P, x, bn_stats_host, y_out_host, (hipStream_t)stream);
+  rc = plan_forward(*P, a, y_out_host, (hipStream_t)stream);
+  if (rc == GCL_OK) rc = check_pass(*P, "gcl_plan_forward");
   P->forward_done = rc == GCL_OK;
   if (rc != GCL_OK) {
     P->fwd_rows = nullptr;
@@ -1958,18 +1993,7 @@ int64_t gcl_plan_eval_state_bytes(const void* plan) {
 }
 
 int64_t gcl_plan_eval_arena_bytes(void* plan, const gcl_maps_desc* maps_host) {
-  Plan* P = (Plan*)plan;
-  if (!P || check_maps(*P, maps_host) != GCL_OK) return -1;
-  P->maps = maps_host;
-  P->params.assign(P->n_params, nullptr);
-  P->eval = true;
-  P->bn_eval = nullptr;
-  P->state = DRY_BASE;
-  long long need = 0;
-  const int rc = dry_pass(*P, nullptr, nullptr, false, &need);
-  P->eval = false;
-  P->forward_done = false;
-  return rc == GCL_OK ? need + 4096 : -1;
+  return sized_pass(plan, "gcl_plan_eval_arena_bytes", maps_host, true);
 }
 
 int gcl_plan_forward_eval(void* plan, const gcl_maps_desc* maps_host, const float* x, void* const* params_host,
@@ -1978,33 +2002,11 @@ int gcl_plan_forward_eval(void* plan, const gcl_maps_desc* maps_host, const floa
   Plan* P = (Plan*)plan;
   GCL_CHECK_ARG(P && maps_host && x && params_host && bn_eval_host && state && arena && y_out_host,
                 "gcl_plan_forward_eval: null pointer");
-  int rc = check_maps(*P, maps_host);
-  if (rc) return rc;
-  P->maps_copy = *maps_host;
-  P->maps = &P->maps_copy;
-  P->params.assign(params_host, params_host + P->n_params);
-  P->state = state;
-  P->eval = true;
-  P->bn_eval = bn_eval_host;
-  P->eval_repack = repack != 0;
-  std::vector<void*> nulls(2 * (P->n_bn > 0 ? P->n_bn : 1), nullptr);
-  long long need = 0;      // size check first
-  rc = dry_pass(*P, x, nulls.data(), false, &need);
-  if (rc == GCL_OK && need > arena_bytes) {
-    set_error("gcl_plan_forward_eval: arena too small (%lld bytes needed, %lld given)", need, (long long)arena_bytes);
-    rc = GCL_ERR_ARENA;
-  }
-  if (rc == GCL_OK) {
-    P->A = Arena{(char*)arena, arena_bytes, 0, false};
-    rc = plan_forward(*P, x, nulls.data(), y_out_host, (hipStream_t)stream);
-  }
-  if (rc == GCL_OK && P->slots_exhausted) {
-    set_error("gcl_plan_forward_eval: amax slot pool exhausted");
-    rc = GCL_ERR_ARG;
-  }
-  P->eval = false;
-  P->bn_eval = nullptr;
-  P->forward_done = false;
+  const FwdArgs a{x, true, bn_eval_host, repack != 0};
+  long long need = 0;
+  int rc = bind_pass(*P, "gcl_plan_forward_eval", maps_host, params_host, state, arena, arena_bytes, a, &need);
+  if (rc == GCL_OK) rc = plan_forward(*P, a, y_out_host, (hipStream_t)stream);
+  if (rc == GCL_OK) rc = check_pass(*P, "gcl_plan_forward_eval");
   static_cast<PassState&>(*P) = PassState();      // nothing waits for a backward pass
   return rc;
 }
@@ -2052,14 +2054,7 @@ int gcl_plan_backward(void* plan, void* arena, const float* dy, void* const* gra
   }
   unpark(*P, slot);
   int rc = plan_backward(*P, dy, grads_host, first_op, last_op, (hipStream_t)stream, rows, cap);
-  if (rc == GCL_OK && !P->A.fits()) {
-    set_error("gcl_plan_backward: arena overrun");
-    rc = GCL_ERR_ARENA;
-  }
-  if (rc == GCL_OK && P->slots_exhausted) {
-    set_error("gcl_plan_backward: amax slot pool exhausted");
-    rc = GCL_ERR_ARG;
-  }
+  if (rc == GCL_OK) rc = check_pass(*P, "gcl_plan_backward");
   if (first_op == 0 || rc != GCL_OK) P->forward_done = false;      // the pass is finished (or broken): its slot is free again
   park(*P, slot);
   return rc;

@@ -1,5 +1,5 @@
 """Tensors the training plan keeps as a plane image only (include/gcl_amd.h, "Plane-only tensors"; csrc/plan.hip:
-plane_only_analysis; csrc/norm.hip: k_bn_apply / k_bn_bwd_apply with a NULL fp32 output).
+analyse_graph; csrc/norm.hip: k_bn_apply / k_bn_bwd_apply with a NULL fp32 output).
 
 Host level (no GPU): ResUNetBN2C's record list written out by hand -- the reader analysis names the 4 forward and 8 backward
 tensors, and the dry sizing shrinks by exactly their blocks, at presplit 128 and 64.

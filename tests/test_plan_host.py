@@ -33,14 +33,14 @@ def _mini_records():
     ]
 
 
-def _create(records, n_tensors=11, n_params=18, worder=(3, 6, 9, 12, 15, 16)):
+def _create(records, n_tensors=11, n_params=18, worder=(3, 6, 9, 12, 15, 16), presplit=128):
     lib = _lib.load()
     arr = (_lib.PlanOp * len(records))()
     for a, r in zip(arr, records):
         for k, v in r.items():
             setattr(a, k, v)
     wo = (ctypes.c_int32 * max(1, len(worder)))(*worder)
-    return lib.gcl_plan_create(arr, len(records), n_tensors, n_params, wo, len(worder), 128)
+    return lib.gcl_plan_create(arr, len(records), n_tensors, n_params, wo, len(worder), presplit)
 
 
 def _maps(n=10000, n1=3000):
@@ -98,15 +98,7 @@ def test_arena_sizes_are_the_ones_the_dense_and_touched_row_bodies_took_before_t
         rec, kw["n_tensors"] = rec[:9], 10
     elif case == "no_suffix":
         rec, kw = rec[:5], dict(n_tensors=6, n_params=15, worder=(3, 6, 9, 12))
-    if case == "presplit_64":      # _create fixes presplit_min_c = 128
-        arr = (_lib.PlanOp * len(rec))()
-        for a, r in zip(arr, rec):
-            for k, v in r.items():
-                setattr(a, k, v)
-        wo = (ctypes.c_int32 * len(kw["worder"]))(*kw["worder"])
-        h = lib.gcl_plan_create(arr, len(rec), kw["n_tensors"], kw["n_params"], wo, len(kw["worder"]), 64)
-    else:
-        h = _create(rec, **kw)
+    h = _create(rec, presplit=64 if case == "presplit_64" else 128, **kw)
     assert h, lib.gcl_last_error()
     h = ctypes.c_void_p(h)
     for (n, n1), want in zip(((10000, 3000), (300, 100)), _ARENA_PINS[case]):
@@ -114,6 +106,91 @@ def test_arena_sizes_are_the_ones_the_dense_and_touched_row_bodies_took_before_t
         got = (lib.gcl_plan_arena_bytes(h, ctypes.byref(d)), lib.gcl_plan_eval_arena_bytes(h, ctypes.byref(d)))
         assert got == want, (case, n, got, want)
     lib.gcl_plan_destroy(h)
+
+
+def _graph_variant(case):
+    """_mini_records() with one edit per graph analysis of gcl_plan_create whose condition the edit flips."""
+    r = _mini_records()
+    kw = {}
+    if case in ("g_wide", "h_wide_cat_swapped"):      # every width x 4 (the stem keeps its one input channel): bound mode
+        for o in r:
+            o.update(cin=o["cin"] * 4 if o["cin"] > 1 else 1, cout=o["cout"] * 4)
+    if case == "a_conv_read_twice":            # the 1x1 conv's output has a second reader: no ReLU in its epilogue
+        r[8].update(x=7)
+    elif case == "b_cat_left_read_twice":      # the cat's left input has a second reader: no cat in place
+        r[6].update(x=5, cin=32)
+    elif case in ("c_cat_swapped", "h_wide_cat_swapped"):
+        r[5]["x"], r[5]["x2"] = r[5]["x2"], r[5]["x"]
+    elif case == "d_relu_read_twice":          # the ReLU has two readers: no mask_from, and the suffix moves
+        r[9].update(x=8, cin=64, cout=64)
+    elif case == "e_ends_in_relu":
+        r, kw = r[:8], dict(n_tensors=9, n_params=16, worder=(3, 6, 9, 12, 15))
+    elif case == "f_ends_in_conv":
+        r, kw = r[:7], dict(n_tensors=8, n_params=16, worder=(3, 6, 9, 12, 15))
+    return r, kw
+
+
+# case -> presplit -> (touched suffix, plane-only flags, (arena, eval arena) at _maps(10000, 3000), the same at _maps(300, 100)),
+# as returned by the library of commit 1a22491 ("Loss backward without float atomics: opt-in bitwise-reproducible steps")
+# cross-compiled for gfx950: what fuse_relu, cat_left, mask_from, the suffix search and the plane-only analysis decided from the
+# records before they shared one reader table.  "base" is _mini_records() itself; every variant differs from it.
+_GRAPH_PINS = {
+    "base": {
+        128: (6, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (45784320, 15055936), (4207744, 617136)),
+        64: (6, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (53758464, 20175936), (4451200, 770736)),
+    },
+    "a_conv_read_twice": {
+        128: (9, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (49042176, 17615936), (4297856, 693936)),
+        64: (9, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (58258688, 22735936), (4579968, 847536)),
+    },
+    "b_cat_left_read_twice": {
+        128: (7, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (45760256, 15055936), (4183680, 617136)),
+        64: (7, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (52416768, 17615936), (4388992, 693936)),
+    },
+    "c_cat_swapped": {
+        128: (6, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (47064320, 15055936), (4246144, 617136)),
+        64: (6, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (55038464, 20175936), (4489600, 770736)),
+    },
+    "d_relu_read_twice": {
+        128: (10, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (45695232, 16335936), (4194688, 655536)),
+        64: (10, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0], (54911744, 21455936), (4476800, 809136)),
+    },
+    "e_ends_in_relu": {
+        128: (6, [0, 0, 0, 0, 0, 0, 0, 0], (41772800, 12431360), (4039552, 514560)),
+        64: (6, [0, 0, 0, 0, 0, 0, 0, 0], (47149056, 14991360), (4206208, 591360)),
+    },
+    "f_ends_in_conv": {
+        128: (6, [0, 0, 0, 0, 0, 0, 0], (39201024, 12419072), (3950976, 502272)),
+        64: (6, [0, 0, 0, 0, 0, 0, 0], (44577280, 14979072), (4117632, 579072)),
+    },
+    "g_wide": {
+        128: (6, [0, 3, 0, 3, 0, 0, 0, 0, 0, 0], (251622144, 80079936), (50534656, 2575536)),
+        64: (6, [0, 3, 0, 3, 0, 0, 0, 0, 0, 0], (251622144, 80079936), (50534656, 2575536)),
+    },
+    "h_wide_cat_swapped": {
+        128: (6, [0, 3, 0, 3, 0, 0, 0, 0, 0, 0], (261862144, 80079936), (50841856, 2575536)),
+        64: (6, [0, 3, 0, 3, 0, 0, 0, 0, 0, 0], (261862144, 80079936), (50841856, 2575536)),
+    },
+}
+
+
+@pytest.mark.parametrize("presplit", [128, 64])
+@pytest.mark.parametrize("case", ["base", "a_conv_read_twice", "b_cat_left_read_twice", "c_cat_swapped", "d_relu_read_twice",
+                                  "e_ends_in_relu", "f_ends_in_conv", "g_wide", "h_wide_cat_swapped"])
+def test_graph_analyses_decide_what_they_decided_before_the_reader_table(case, presplit):
+    lib = _lib.load()
+    rec, kw = _graph_variant(case)
+    h = _create(rec, presplit=presplit, **kw)
+    assert h, lib.gcl_last_error()
+    h = ctypes.c_void_p(h)
+    flags = (ctypes.c_int32 * len(rec))()
+    assert lib.gcl_plan_plane_only(h, flags, len(rec)) >= 0
+    got = (lib.gcl_plan_touched_suffix(h), list(flags)) + tuple(
+        (lib.gcl_plan_arena_bytes(h, ctypes.byref(d)), lib.gcl_plan_eval_arena_bytes(h, ctypes.byref(d)))
+        for d in (_maps(10000, 3000), _maps(300, 100)))
+    lib.gcl_plan_destroy(h)
+    assert got == _GRAPH_PINS[case][presplit], (case, presplit, got)
+    assert case == "base" or got != _GRAPH_PINS["base"][presplit]
 
 
 @pytest.mark.parametrize("mutate,why", [
