@@ -69,6 +69,57 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned nwg, int swi
 }
 constexpr int LDS_STRIDE = 36;   // 32 floats + 4 pad: conflict-free ds_read_b128 (MI355X_MICROARCH LDS table)
 
+// The walk of every MFMA forward kernel: step (k, cc) = one kernel offset of `mask` (ascending) x one 32-channel slice.
+// A kernel that stages ahead copies the cursor and advances the copy: `m_rest` travels with the newest one.
+struct StepCursor {
+  int k, cc;
+  bool has;            // false: the walk is over, (k, cc) are stale
+  unsigned m_rest;     // offsets of the mask behind k
+  // member-wise copies: the implicit ones move the padding behind `has` as well, through scratch memory
+  StepCursor() = default;
+  __device__ __forceinline__ StepCursor(const StepCursor& o) : k(o.k), cc(o.cc), has(o.has), m_rest(o.m_rest) {}
+  __device__ __forceinline__ StepCursor& operator=(const StepCursor& o) {
+    k = o.k, cc = o.cc, has = o.has, m_rest = o.m_rest;
+    return *this;
+  }
+  __device__ __forceinline__ void start(unsigned mask) {
+    has = mask != 0u;
+    k = has ? __builtin_ctz(mask) : 0;
+    cc = 0;
+    m_rest = mask & (mask - 1u);
+  }
+  __device__ __forceinline__ void advance(int CC) {
+    cc += 1;
+    if (cc == CC) {
+      cc = 0;
+      if (m_rest) {
+        k = __builtin_ctz(m_rest);
+        m_rest &= m_rest - 1;
+      } else {
+        has = false;
+      }
+    }
+  }
+};
+
+// Offsets a wave's 32-row tile has to visit (wave-uniform): its entry of the map's tile masks, else all K; cut to `cut`
+// (offset_group: one of k_conv_fwd_tall's four groups).  A wave without rows visits none.
+__device__ __forceinline__ unsigned offset_group(unsigned g) { return 0x11111111u << g; }      // offsets k with k mod 4 == g
+__device__ __forceinline__ unsigned tile_offsets(const int* __restrict__ tile_mask, long long tile, int K, bool active,
+                                                 unsigned cut = ~0u) {
+  unsigned m = 0u;
+  if (active) m = tile_mask ? (unsigned)tile_mask[tile] : ((K >= 32) ? ~0u : ((1u << K) - 1u));
+  return __builtin_amdgcn_readfirstlane(m & cut);
+}
+
+template <int N>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int b = 0; b < N; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+}
+
 template <int NB>  // 32-column blocks per wave
 __global__ void __launch_bounds__(256) k_conv_fwd(const float* __restrict__ X, const float4* __restrict__ Wp,
                                                   const int* __restrict__ tbl, const int* __restrict__ order,
@@ -88,14 +139,9 @@ __global__ void __launch_bounds__(256) k_conv_fwd(const float* __restrict__ X, c
   const bool row_ok = (l < 32) && (row0 + l < n_out);
 
   f32x16 acc[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+  zero_acc(acc);
 
-  // offsets this tile has to visit (wave-uniform)
-  unsigned kmask = tile_mask ? (unsigned)tile_mask[tile] : ((K >= 32) ? ~0u : ((1u << K) - 1u));
-  kmask = __builtin_amdgcn_readfirstlane(kmask);
+  const unsigned kmask = tile_offsets(tile_mask, tile, K, true);
 
   // all neighbour indices of the tile go to (wave-private) LDS once: no index -> gather dependency in the loop
   for (int e = l; e < K * 32; e += 64) {
@@ -116,33 +162,24 @@ __global__ void __launch_bounds__(256) k_conv_fwd(const float* __restrict__ X, c
 
   if (kmask != 0u) {
     // software pipeline over the steps (k, cc): the gather of step s+1 is in flight while step s computes
-    int k_cur = __builtin_ctz(kmask), cc_cur = 0;
-    unsigned m_rest = kmask & (kmask - 1);
+    StepCursor cur;
+    cur.start(kmask);
     float4 st[4];
-    gather(k_cur, 0, st);
+    gather(cur.k, 0, st);
     while (true) {
-      int k_nxt = k_cur, cc_nxt = cc_cur + 1;
-      bool has_nxt = true;
-      if (cc_nxt == CC) {
-        cc_nxt = 0;
-        if (m_rest) {
-          k_nxt = __builtin_ctz(m_rest);
-          m_rest &= m_rest - 1;
-        } else {
-          has_nxt = false;
-        }
-      }
+      StepCursor nxt = cur;
+      nxt.advance(CC);
       WAVE_FENCE();   // the previous step's fragment reads are done before the tile is overwritten
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<float4*>(&lds[w][rsub + 8 * ps][p * 4]) = st[ps];
-      if (has_nxt) gather(k_nxt, cc_nxt, st);
+      if (nxt.has) gather(nxt.k, nxt.cc, st);
       WAVE_FENCE();
       float4 a[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) a[q] = *reinterpret_cast<const float4*>(&lds[w][i][8 * q + 4 * h]);
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        const float4* wb = Wp + (((long long)k_cur * TNB + nb0 + b) * Q + cc_cur * 4) * 64 + l;
+        const float4* wb = Wp + (((long long)cur.k * TNB + nb0 + b) * Q + cur.cc * 4) * 64 + l;
         float4 bv[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) bv[q] = wb[q * 64];
@@ -154,9 +191,8 @@ __global__ void __launch_bounds__(256) k_conv_fwd(const float* __restrict__ X, c
           acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, bv[q].w, acc[b], 0, 0, 0);
         }
       }
-      if (!has_nxt) break;
-      k_cur = k_nxt;
-      cc_cur = cc_nxt;
+      if (!nxt.has) break;
+      cur = nxt;
     }
   }
   // epilogue: acc[b][r] is element (row = (r&3) + 8*(r>>2) + 4*h, col = i) of the wave's 32 x 32 block b
@@ -632,6 +668,196 @@ __device__ __forceinline__ void conv_fwd_epilogue(f32x16 (&acc)[NB], float* tile
   }
 }
 
+// ---- pieces shared by k_conv_fwd_split, k_conv_fwd_dma and k_conv_fwd_tall ------------------------------------------------
+
+// Workgroup -> (row tile of 128 rows, column block[, offset group]), and wave `wt` -> its 32 rows.  `swizzle` & 15:
+//   0 / 1 (2-D grid): blockIdx.y = column block, blockIdx.x = row tile, 1 = XCD-contiguous (xcd_tile);
+//   2 (1-D grid): the cout / (32 NB) column blocks [x NGRP offset groups] that gather the SAME 128 rows get consecutive
+//     slots of one XCD (workgroups are dealt round-robin over the 8 XCDs) and share its L2;
+//   3 (1-D grid): as 2, and every XCD owns a CONTIGUOUS range of row tiles (spatially ordered tables).
+// Bit 4 of `swizzle`: process the row tiles in DESCENDING order.  The mask sort puts the rows that own rare offsets
+// last; their tiles visit 2 - 3x the average number of offsets (per-workgroup union: mean 8.9, p90 17, max 27 at
+// stride 1), so in ascending order the longest workgroups start last and the launch ends on a thin, slow tail.
+struct FwdTile {
+  unsigned bxx, byy, grp;      // row tile, column block, offset group (NGRP > 1)
+  long long tile, row0;        // the wave's 32-row tile and its first row
+  bool active;                 // the wave has rows
+  int nb0;                     // first 32-column block
+  // false: the grid's padding, this workgroup has nothing to do (the caller returns, before any barrier)
+  template <int NB, int NGRP>
+  __device__ __forceinline__ bool map(int swizzle, long long n_out, int cout, int wt) {
+    bxx = blockIdx.x;
+    byy = blockIdx.y;
+    grp = 0u;
+    const bool heavy_first = (swizzle & 16) != 0;
+    swizzle &= 15;
+    const unsigned nrw = (unsigned)((n_out + CONV_ROWS - 1) / CONV_ROWS);
+    if (swizzle >= 2) {
+      const unsigned ncb1 = (unsigned)(cout / (32 * NB)), ncb = ncb1 * (unsigned)NGRP;      // (group, column block) slots
+      const unsigned xcd = bxx & 7u, slot = bxx >> 3;
+      byy = slot % ncb;
+      if (NGRP > 1) {
+        grp = byy / ncb1;
+        byy -= grp * ncb1;
+      }
+      if (swizzle == 2) {
+        bxx = (slot / ncb) * 8u + xcd;
+        if (bxx >= nrw) return false;
+      } else {
+        const unsigned q = nrw >> 3, r = nrw & 7u, mine = q + (xcd < r ? 1u : 0u), j = slot / ncb;
+        if (j >= mine) return false;
+        bxx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+      }
+    } else {
+      bxx = xcd_tile(bxx, gridDim.x, swizzle);
+    }
+    if (heavy_first) bxx = nrw - 1u - bxx;
+    tile = (long long)bxx * 4 + wt;
+    row0 = tile * 32;
+    active = row0 < n_out;
+    nb0 = byy * NB;
+    return true;
+  }
+};
+
+// Neighbour rows of a wave's tile in LDS, one offset = 32 ints at slot (row & 7) * 4 + (row >> 3): the four rows a lane
+// gathers (row, row + 8, row + 16, row + 24) are one 16-byte read.
+__device__ __forceinline__ int idx_slot(int r) { return (r & 7) * 4 + (r >> 3); }
+__device__ __forceinline__ int4 idx_rows(const int* offset_rows, int rsub) {
+  return *reinterpret_cast<const int4*>(offset_rows + rsub * 4);
+}
+__device__ __forceinline__ int idx_lookup(const int* __restrict__ tbl, long long n_out, long long row0, int k, int r) {
+  return tbl ? tbl[(long long)k * n_out + row0 + r] : (int)(row0 + r);
+}
+
+// The table of the four-wave kernels holds HALF of the offsets at a time (k < 15, later k >= 15: the loop visits offsets in
+// ascending order; the second half waits in registers and is written when the first unit with k >= 15 is issued) -- 7.5 KB
+// instead of 14 KB per workgroup, which is what lets a fourth workgroup of the NB = 2 instances share a CU's 160 KB LDS
+// (occupancy is what hides the gather latency here).  K <= 27.
+constexpr int ISM_H = 15;
+struct HalfIndexTable {
+  int (*T)[32];        // the wave's [ISM_H][32] ints of LDS
+  int ib[6];           // entries e = 32 ISM_H + l + 64 j (offsets k = e / 32 >= 15, rows e % 32), j = 0 .. 5
+  bool second_half;
+  // all neighbour indices of the tile go to LDS once: no index load (and no index -> gather dependency) in the loop
+  // only the offsets of the wave's mask are ever looked up: the other table rows are not fetched (a wave tile visits
+  // ~8 of 27 offsets on the KITTI batch: the index table is as large as a C = 32 output tile)
+  __device__ __forceinline__ void fill(int (*mine)[32], const int* __restrict__ tbl, long long n_out, int K,
+                                       const FwdTile& ft, unsigned mymask, int l) {
+    T = mine;
+    for (int e = l; e < (K < ISM_H ? K : ISM_H) * 32; e += 64) {
+      const int k = e >> 5, r = e & 31;
+      int v = -1;
+      if (ft.active && ((mymask >> k) & 1u) && ft.row0 + r < n_out) v = idx_lookup(tbl, n_out, ft.row0, k, r);
+      T[k][idx_slot(r)] = v;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int e = 32 * ISM_H + l + 64 * j, k = e >> 5, r = e & 31;
+      int v = -1;
+      if (k < K && ft.active && ((mymask >> k) & 1u) && ft.row0 + r < n_out) v = tbl[(long long)k * n_out + ft.row0 + r];
+      ib[j] = v;
+    }
+    second_half = false;
+  }
+  // the four rows of lane `l` at offset k; the first k >= ISM_H switches the table (every gather of an offset < ISM_H has
+  // been issued by then)
+  __device__ __forceinline__ int4 rows(int k, int K, int l) {
+    if (k >= ISM_H && !second_half) {
+      second_half = true;
+      WAVE_FENCE();
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const int e = 32 * ISM_H + l + 64 * j;
+        if ((e >> 5) < K) T[(e >> 5) - ISM_H][idx_slot(e & 31)] = ib[j];
+      }
+      WAVE_FENCE();
+    }
+    return idx_rows(T[k >= ISM_H ? k - ISM_H : k], l >> 3);
+  }
+};
+
+// Register-staged gather of a step's A tile: a lane fetches piece p = l & 7 of its four rows `ri` (rows rsub + 8 ps,
+// rsub = l >> 3), `co` = byte offset of the piece inside a row.  Through a buffer resource: a missing neighbour (row -1)
+// wraps to a byte offset beyond the tensor and the hardware returns zeros -- no compare / branch / 64-bit address arithmetic
+// per row (the loop is issue-bound).
+__device__ __forceinline__ void gather_rows(float4 (&st)[4], __amdgpu_buffer_rsrc_t xrsrc, const int4& ri, unsigned row_bytes,
+                                            unsigned co) {
+  st[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri.x * row_bytes + co), 0, 0));
+  st[1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri.y * row_bytes + co), 0, 0));
+  st[2] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri.z * row_bytes + co), 0, 0));
+  st[3] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri.w * row_bytes + co), 0, 0));
+}
+// ... and its way into the wave's tile: un-padded 128-byte rows, 16-byte pieces XOR-swizzled with the row
+__device__ __forceinline__ void store_a_tile(float (*tile)[32], const float4 (&st)[4], int l) {
+  const int p = l & 7, rsub = l >> 3;
+#pragma unroll
+  for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<float4*>(&tile[rsub + 8 * ps][(p ^ a_swz(rsub + 8 * ps)) << 2]) = st[ps];
+}
+// The (k, cc) weight block of a workgroup's columns, BLK uint4, lane-linear: global -> registers -> LDS by `t` of 256 threads
+template <int BLK>
+__device__ __forceinline__ void load_b_block(u32x4 (&br)[(BLK + 255) / 256], const u32x4* __restrict__ src, int t) {
+#pragma unroll
+  for (int e = 0; e < (BLK + 255) / 256; ++e)
+    if ((BLK % 256 == 0) || (e * 256 + t < BLK)) br[e] = src[e * 256 + t];
+}
+template <int BLK>
+__device__ __forceinline__ void store_b_block(u32x4* dst, const u32x4 (&br)[(BLK + 255) / 256], int t) {
+#pragma unroll
+  for (int e = 0; e < (BLK + 255) / 256; ++e)
+    if ((BLK % 256 == 0) || (e * 256 + t < BLK)) dst[e * 256 + t] = br[e];
+}
+
+// A fragments of half m (16 of the slice's 32 channels) of tile row i = l & 31, h = l >> 5, out of the swizzled tile.
+// Plane images: dwords [0,16) of a row = hi of channels 0..31, [16,32) = lo -- the two planes of the fragment as they are.
+__device__ __forceinline__ void a_frag_planes(float (*tile)[32], int m, int l, u32x4* ap) {
+  const int i = l & 31, h = l >> 5;
+  ap[0] = *reinterpret_cast<const u32x4*>(&tile[i][((2 * m + h) ^ a_swz(i)) << 2]);
+  ap[1] = *reinterpret_cast<const u32x4*>(&tile[i][((4 + 2 * m + h) ^ a_swz(i)) << 2]);
+}
+// fp32 rows: the fragment's eight channels, to be split into planes by the caller (split8)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void a_frag_rows(float (*tile)[32], int m, int l, f32x4 (&f)[2]) {
+  const int i = l & 31, h = l >> 5;
+  f[0] = *reinterpret_cast<const f32x4*>(&tile[i][((4 * m + 2 * h) ^ a_swz(i)) << 2]);
+  f[1] = *reinterpret_cast<const f32x4*>(&tile[i][((4 * m + 2 * h + 1) ^ a_swz(i)) << 2]);
+}
+template <int PL>
+__device__ __forceinline__ void split8(const f32x4 (&f)[2], float scale, u32x4* pl) {
+  split8<PL>(make_float4(f[0][0], f[0][1], f[0][2], f[0][3]), make_float4(f[1][0], f[1][1], f[1][2], f[1][3]), scale, pl);
+}
+
+// B fragments of half m out of the weight block `blk` (LDS; [(b * 2 + m) * NPL + plane][64 lanes]) and all product terms of
+// the NB column blocks: with cross accumulators (mfma_terms) ...
+template <int PL>
+__device__ __forceinline__ void b_frag(const u32x4* blk, int b, int m, int l, u32x4* bp) {
+  constexpr int NPL = Prec<PL>::planes;
+  const u32x4* bb = &blk[((b * 2 + m) * NPL) * 64 + l];
+  bp[0] = bb[0];
+  bp[1] = bb[64];
+  if (NPL == 3) bp[2] = bb[128];
+}
+template <int PL, int NB, int NX>
+__device__ __forceinline__ void mma_blocks(const u32x4* ap, const u32x4* blk, int m, int l, f32x16 (&acc)[NB],
+                                           f32x16 (&accx)[NX]) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    u32x4 bp[3];
+    b_frag<PL>(blk, b, m, l, bp);
+    mfma_terms<PL>(ap, bp, acc[b], accx[(PL == 4) ? b : 0]);
+  }
+}
+// ... and with ONE accumulator, `ap` re-scaled by dw_a_planes (mfma_terms_dw): the inference launches in offset groups
+template <int PL, int NB>
+__device__ __forceinline__ void mma_blocks_dw(const u32x4* ap, const u32x4* blk, int m, int l, f32x16 (&acc)[NB]) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    u32x4 bp[3];
+    b_frag<PL>(blk, b, m, l, bp);
+    mfma_terms_dw<PL>(ap, bp, acc[b]);
+  }
+}
+
 // PRE: X is not the fp32 tensor but its fp16 plane image made by gcl_split_planes -- per row and 32-channel slice
 // 64 bytes of hi followed by 64 bytes of lo, i.e. the same 128 bytes per (row, slice) and the same addressing as the
 // fp32 rows.  The main loop then has no split at all (the kernels are instruction-issue-bound: the split was 48 of ~120
@@ -646,85 +872,25 @@ __global__ void __launch_bounds__(256, GCL_FWD_MIN_WAVES(NB, PL)) k_conv_fwd_spl
                                                         const int* __restrict__ w_amax, unsigned x_bytes, ConvEpi epi) {
   constexpr int NPL = Prec<PL>::planes;
   constexpr int BLK = NB * 2 * NPL * 64;                // uint4 per (k, cc) weight block of this workgroup
-  constexpr int BREG = (BLK + 255) / 256;
   const float a_scale = (PL == 4) ? amax_scale(x_amax) : 1.f;
   const float out_scale = (PL == 4) ? 1.f / (a_scale * amax_scale(w_amax)) : 1.f;   // exact: powers of two
-  __shared__ __attribute__((aligned(16))) float Asm[4][32][32];   // wave-private A tiles: un-padded 128-byte rows, 16-byte pieces XOR-swizzled with the row
+  __shared__ __attribute__((aligned(16))) float Asm[4][32][32];   // wave-private A tiles (store_a_tile)
   __shared__ __attribute__((aligned(16))) u32x4 Bsm[2][BLK];              // weight block, double-buffered
-  // neighbour rows of the wave's tile, [wave][k][(row & 7) * 4 + (row >> 3)] (K <= 27): the four rows a lane gathers
-  // (row, row + 8, row + 16, row + 24) are one 16-byte read.  The table holds HALF of the offsets at a time (k < 15, later
-  // k >= 15: the loop visits offsets in ascending order; the second half waits in registers and is written when the first
-  // unit with k >= 15 is issued) -- 7.5 KB instead of 14 KB per workgroup, which is what lets a fourth workgroup of the
-  // NB = 2 instances share a CU's 160 KB LDS (occupancy is what hides the gather latency here)
-  constexpr int ISM_H = 15;
-  __shared__ __attribute__((aligned(16))) int Ism[4][ISM_H][32];
+  __shared__ __attribute__((aligned(16))) int Ism[4][ISM_H][32];          // HalfIndexTable of every wave
   __shared__ unsigned wmask[4];
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int i = l & 31, h = l >> 5;
-  // swizzle 2 (1-D grid): the cout / (32 NB) column blocks that gather the SAME 128 rows get consecutive slots of one
-  // XCD (workgroups are dealt round-robin over the 8 XCDs) and share its L2
-  unsigned bxx = blockIdx.x, byy = blockIdx.y;
-  // bit 4 of `swizzle`: process the row tiles in DESCENDING order.  The mask sort puts the rows that own rare offsets
-  // last; their tiles visit 2 - 3x the average number of offsets (per-workgroup union: mean 8.9, p90 17, max 27 at
-  // stride 1), so in ascending order the longest workgroups start last and the launch ends on a thin, slow tail
-  const bool heavy_first = (swizzle & 16) != 0;
-  swizzle &= 15;
-  const unsigned nrw = (unsigned)((n_out + CONV_ROWS - 1) / CONV_ROWS);
-  if (swizzle >= 2) {
-    const unsigned ncb = (unsigned)(cout / (32 * NB));
-    const unsigned xcd = bxx & 7u, slot = bxx >> 3;
-    byy = slot % ncb;
-    if (swizzle == 2) {
-      bxx = (slot / ncb) * 8u + xcd;
-      if (bxx >= nrw) return;   // whole workgroup, before any barrier
-    } else {                    // 3: every XCD owns a CONTIGUOUS range of row tiles (spatially ordered tables)
-      const unsigned q = nrw >> 3, r = nrw & 7u, mine = q + (xcd < r ? 1u : 0u), j = slot / ncb;
-      if (j >= mine) return;
-      bxx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-  } else {
-    bxx = xcd_tile(bxx, gridDim.x, swizzle);
-  }
-  if (heavy_first) bxx = nrw - 1u - bxx;
-  const long long tile = (long long)bxx * 4 + w;
-  const long long row0 = tile * 32;
-  const bool active = row0 < n_out;
-  const int nb0 = byy * NB;
+  FwdTile ft;
+  if (!ft.map<NB, 1>(swizzle, n_out, cout, w)) return;   // whole workgroup, before any barrier
   const int TNB = cout >> 5, CC = cin >> 5;
-  const int p = l & 7, rsub = l >> 3;
 
   f32x16 acc[NB], accx[(PL == 4) ? NB : 1];      // accx: the fp16x3 cross terms (mfma_terms)
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-#pragma unroll
-  for (int b = 0; b < (int)(sizeof(accx) / sizeof(accx[0])); ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accx[b][r] = 0.f;
+  zero_acc(acc);
+  zero_acc(accx);
 
-  unsigned mymask = 0u;
-  if (active) mymask = tile_mask ? (unsigned)tile_mask[tile] : ((K >= 32) ? ~0u : ((1u << K) - 1u));
-  mymask = __builtin_amdgcn_readfirstlane(mymask);
+  const unsigned mymask = tile_offsets(tile_mask, ft.tile, K, ft.active);
   if (l == 0) wmask[w] = mymask;
-  // all neighbour indices of the tile go to LDS once: no index load (and no index -> gather dependency) in the loop
-  // only the offsets of the wave's mask are ever looked up: the other table rows are not fetched (a wave tile visits
-  // ~8 of 27 offsets on the KITTI batch: the index table is as large as a C = 32 output tile)
-  for (int e = l; e < (K < ISM_H ? K : ISM_H) * 32; e += 64) {
-    const int k = e >> 5, r = e & 31;
-    int v = -1;
-    if (active && ((mymask >> k) & 1u) && row0 + r < n_out) v = tbl ? tbl[(long long)k * n_out + row0 + r] : (int)(row0 + r);
-    Ism[w][k][(r & 7) * 4 + (r >> 3)] = v;
-  }
-  int ib[6];                       // entries e = 32 ISM_H + l + 64 j (offsets k = e / 32 >= 15, rows e % 32), j = 0 .. 5
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const int e = 32 * ISM_H + l + 64 * j, k = e >> 5, r = e & 31;
-    int v = -1;
-    if (k < K && active && ((mymask >> k) & 1u) && row0 + r < n_out) v = tbl[(long long)k * n_out + row0 + r];
-    ib[j] = v;
-  }
-  bool second_half = false;
+  HalfIndexTable idx;
+  idx.fill(Ism[w], tbl, n_out, K, ft, mymask, l);
   __syncthreads();
   const unsigned wgmask = wmask[0] | wmask[1] | wmask[2] | wmask[3];
 
@@ -732,81 +898,40 @@ __global__ void __launch_bounds__(256, GCL_FWD_MIN_WAVES(NB, PL)) k_conv_fwd_spl
   //   loads of step s+2 are issued at the end of step s and land in registers during step s+1,
   //   they are written to LDS at the end of step s+1 (A: wave-private tile; B: the buffer not being read),
   //   the barrier closing step s+1 publishes B(s+2).
-  // Gather through a buffer resource: a missing neighbour (row -1) wraps to a byte offset beyond the tensor and the
-  // hardware returns zeros -- no compare / branch / 64-bit address arithmetic per row (the loop is issue-bound)
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (int)x_bytes, 0x00020000);
   const unsigned row_bytes = (unsigned)cin * 4u;
-#define GCL_GATHER_A(KK, CCV)                                                                                  \
-  {                                                                                                            \
-    if ((KK) >= ISM_H && !second_half) {   /* every gather of an offset < 14 has been issued: switch the table */ \
-      second_half = true;                                                                                      \
-      WAVE_FENCE();                                                                                            \
-      _Pragma("unroll") for (int j_ = 0; j_ < 6; ++j_) {                                                       \
-        const int e_ = 32 * ISM_H + l + 64 * j_;                                                               \
-        if ((e_ >> 5) < K) Ism[w][(e_ >> 5) - ISM_H][((e_ & 31) & 7) * 4 + ((e_ & 31) >> 3)] = ib[j_];         \
-      }                                                                                                        \
-      WAVE_FENCE();                                                                                            \
-    }                                                                                                          \
-    const int4 ri_ = *reinterpret_cast<const int4*>(&Ism[w][(KK) >= ISM_H ? (KK) - ISM_H : (KK)][rsub * 4]);    \
-    const unsigned co_ = (unsigned)(CCV)*128u + (unsigned)p * 16u;                                             \
-    st[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.x * row_bytes + co_), 0, 0)); \
-    st[1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.y * row_bytes + co_), 0, 0)); \
-    st[2] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.z * row_bytes + co_), 0, 0)); \
-    st[3] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.w * row_bytes + co_), 0, 0)); \
-  }
-#define GCL_LOAD_B(KK, CCV)                                                                      \
-  {                                                                                              \
-    const u32x4* src_ = Wp + (((long long)(KK)*CC + (CCV)) * TNB + nb0) * (2 * NPL * 64);        \
-    _Pragma("unroll") for (int e = 0; e < BREG; ++e) {                                           \
-      if ((BLK % 256 == 0) || (e * 256 + t < BLK)) br[e] = src_[e * 256 + t];                    \
-    }                                                                                            \
-  }
-#define GCL_STORE_LDS(MINE, BUF)                                                                             \
-  {                                                                                                          \
-    if (MINE) {                                                                                              \
-      _Pragma("unroll") for (int ps = 0; ps < 4; ++ps)                                                       \
-          *reinterpret_cast<float4*>(&Asm[w][rsub + 8 * ps][(p ^ a_swz(rsub + 8 * ps)) << 2]) = st[ps];      \
-    }                                                                                                        \
-    _Pragma("unroll") for (int e = 0; e < BREG; ++e) {                                                       \
-      if ((BLK % 256 == 0) || (e * 256 + t < BLK)) Bsm[BUF][e * 256 + t] = br[e];                           \
-    }                                                                                                        \
-  }
-#define GCL_ADVANCE(KV, CV, HAS)             \
-  {                                          \
-    CV += 1;                                 \
-    if (CV == CC) {                          \
-      CV = 0;                                \
-      if (m_rest) {                          \
-        KV = __builtin_ctz(m_rest);          \
-        m_rest &= m_rest - 1;                \
-      } else {                               \
-        HAS = false;                         \
-      }                                      \
-    }                                        \
-  }
+  float4 st[4];
+  u32x4 br[(BLK + 255) / 256];
+  auto gather_a = [&](const StepCursor& s) __attribute__((always_inline)) {
+    gather_rows(st, xrsrc, idx.rows(s.k, K, l), row_bytes, (unsigned)s.cc * 128u + (unsigned)(l & 7) * 16u);
+  };
+  auto load_b = [&](const StepCursor& s) __attribute__((always_inline)) {
+    load_b_block<BLK>(br, Wp + (((long long)s.k * CC + s.cc) * TNB + ft.nb0) * (2 * NPL * 64), t);
+  };
+  auto store_lds = [&](bool mine, int buf) __attribute__((always_inline)) {
+    if (mine) store_a_tile(Asm[w], st, l);
+    store_b_block<BLK>(Bsm[buf], br, t);
+  };
 
 #ifdef GCL_STAMPS
   const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime(), wg_c0 = __builtin_amdgcn_s_memtime();
   unsigned long long wg_steps = 0;
 #endif
   if (wgmask != 0u) {
-    unsigned m_rest = wgmask & (wgmask - 1);
-    float4 st[4];
-    u32x4 br[BREG];
     // step 0 -> LDS, step 1 -> registers
-    int k0 = __builtin_ctz(wgmask), c0 = 0;
-    bool mine0 = (mymask >> k0) & 1u;
-    if (mine0) GCL_GATHER_A(k0, 0);
-    GCL_LOAD_B(k0, 0);
-    int k1 = k0, c1 = 0;
-    bool has1 = true;
-    GCL_ADVANCE(k1, c1, has1);
-    GCL_STORE_LDS(mine0, 0);
+    StepCursor s0;
+    s0.start(wgmask);
+    const bool mine0 = (mymask >> s0.k) & 1u;
+    if (mine0) gather_a(s0);
+    load_b(s0);
+    StepCursor s1 = s0;
+    s1.advance(CC);
+    store_lds(mine0, 0);
     bool mine1 = false;
-    if (has1) {
-      mine1 = (mymask >> k1) & 1u;
-      if (mine1) GCL_GATHER_A(k1, c1);
-      GCL_LOAD_B(k1, c1);
+    if (s1.has) {
+      mine1 = (mymask >> s1.k) & 1u;
+      if (mine1) gather_a(s1);
+      load_b(s1);
     }
     __syncthreads();
     int buf = 0;
@@ -822,39 +947,30 @@ __global__ void __launch_bounds__(256, GCL_FWD_MIN_WAVES(NB, PL)) k_conv_fwd_spl
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
           u32x4 ap[3];
-          if (PRE) {   // row image: dwords [0,16) = hi of channels 0..31, [16,32) = lo
-            ap[0] = *reinterpret_cast<const u32x4*>(&Asm[w][i][((2 * m + h) ^ a_swz(i)) << 2]);
-            ap[1] = *reinterpret_cast<const u32x4*>(&Asm[w][i][((4 + 2 * m + h) ^ a_swz(i)) << 2]);
+          if (PRE) {
+            a_frag_planes(Asm[w], m, l, ap);
           } else {
-            float4 f0 = *reinterpret_cast<const float4*>(&Asm[w][i][((4 * m + 2 * h) ^ a_swz(i)) << 2]);
-            float4 f1 = *reinterpret_cast<const float4*>(&Asm[w][i][((4 * m + 2 * h + 1) ^ a_swz(i)) << 2]);
-            split8<PL>(f0, f1, a_scale, ap);
+            f32x4 f[2];
+            a_frag_rows(Asm[w], m, l, f);
+            split8<PL>(f, a_scale, ap);
           }
-#pragma unroll
-          for (int b = 0; b < NB; ++b) {
-            const u32x4* bb = &Bsm[buf][((b * 2 + m) * NPL) * 64 + l];
-            u32x4 bp[3];
-            bp[0] = bb[0];
-            bp[1] = bb[64];
-            if (NPL == 3) bp[2] = bb[128];
-            mfma_terms<PL>(ap, bp, acc[b], accx[(PL == 4) ? b : 0]);
-          }
+          mma_blocks<PL>(ap, Bsm[buf], m, l, acc, accx);
         }
       }
       STAMP(ts1)
-      if (!has1) break;   // no step staged in registers: done
+      if (!s1.has) break;   // no step staged in registers: done
       // ---- next step: registers -> LDS (A: own tile, after this wave's reads; B: the buffer nobody reads)
       WAVE_FENCE();
-      GCL_STORE_LDS(mine1, buf ^ 1);
+      store_lds(mine1, buf ^ 1);
       STAMP(ts2)
       // ---- the step after: issue its loads (in flight across the barrier and the next compute phase)
-      int k2 = k1, c2 = c1;
-      bool has2 = true, mine2 = false;
-      GCL_ADVANCE(k2, c2, has2);
-      if (has2) {
-        mine2 = (mymask >> k2) & 1u;
-        if (mine2) GCL_GATHER_A(k2, c2);
-        GCL_LOAD_B(k2, c2);
+      StepCursor s2 = s1;
+      s2.advance(CC);
+      bool mine2 = false;
+      if (s2.has) {
+        mine2 = (mymask >> s2.k) & 1u;
+        if (mine2) gather_a(s2);
+        load_b(s2);
       }
       STAMP(ts3)
       __syncthreads();   // publishes the weight block just written; its buffer was last read two steps ago
@@ -867,9 +983,7 @@ __global__ void __launch_bounds__(256, GCL_FWD_MIN_WAVES(NB, PL)) k_conv_fwd_spl
       buf ^= 1;
       mine_cur = mine1;
       mine1 = mine2;
-      k1 = k2;
-      c1 = c2;
-      has1 = has2;
+      s1 = s2;
     }
 #ifdef GCL_STAMPS
     wg_steps = st_n;
@@ -879,10 +993,6 @@ __global__ void __launch_bounds__(256, GCL_FWD_MIN_WAVES(NB, PL)) k_conv_fwd_spl
     }
 #endif
   }
-#undef GCL_GATHER_A
-#undef GCL_LOAD_B
-#undef GCL_STORE_LDS
-#undef GCL_ADVANCE
 #ifdef GCL_STAMPS
   if (t == 0 && blockIdx.x < WG_TRACE_MAX && gridDim.y == 1) {
     unsigned long long* o = g_wgtrace + (long long)blockIdx.x * 4;
@@ -891,7 +1001,8 @@ __global__ void __launch_bounds__(256, GCL_FWD_MIN_WAVES(NB, PL)) k_conv_fwd_spl
 #endif
 #pragma unroll
   for (int b = 0; b < NB; ++b) fold_cross<PL>(acc[b], accx[(PL == 4) ? b : 0]);
-  conv_fwd_epilogue<NB, EPI>(acc, &Asm[0][0][0], order, n_out, cout, bias, Y, stats, out_scale, epi, tile, bxx, nb0, active);
+  conv_fwd_epilogue<NB, EPI>(acc, &Asm[0][0][0], order, n_out, cout, bias, Y, stats, out_scale, epi, ft.tile, ft.bxx, ft.nb0,
+                             ft.active);
 }
 
 // One LDS-DMA piece: every lane fetches 16 bytes at byte offset (voff + soff) of the buffer `rsrc` (beyond num_records: zeros)
@@ -951,10 +1062,8 @@ __global__ void __launch_bounds__(256, (NB <= 2 ? 4 : 2)) k_conv_fwd_dma(const f
                                                         const int* __restrict__ w_amax, unsigned x_bytes, unsigned w_bytes,
                                                         ConvEpi epi) {
   static_assert(!GRP || (!PRE && !EPI), "offset-group launches: fp32 rows, raw accumulators");
-  constexpr int NGRP = GRP ? 4 : 1;
   constexpr int PL = 4, NPL = 2;
   constexpr int BLK = NB * 2 * NPL * 64;                // uint4 per (k, cc) weight block of this workgroup = NB x 4 KB
-  constexpr int ISM_H = 15;
   const float a_scale = amax_scale(x_amax);
   const float out_scale = 1.f / (a_scale * amax_scale(w_amax));   // exact: powers of two
   // ONE LDS object (a second one beside an LDS-DMA target makes hipcc wait for the DMA before unrelated reads)
@@ -965,70 +1074,20 @@ __global__ void __launch_bounds__(256, (NB <= 2 ? 4 : 2)) k_conv_fwd_dma(const f
   int (*Ism)[ISM_H][32] = reinterpret_cast<int (*)[ISM_H][32]>(smem + A_BYTES + B_BYTES);
   unsigned* const wmask = reinterpret_cast<unsigned*>(smem + A_BYTES + B_BYTES + I_BYTES);
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int i = l & 31, h = l >> 5;
-  unsigned bxx = blockIdx.x, byy = blockIdx.y;
-  const bool heavy_first = (swizzle & 16) != 0;
-  swizzle &= 15;
-  const unsigned nrw = (unsigned)((n_out + CONV_ROWS - 1) / CONV_ROWS);
-  unsigned grp = 0u;
-  if (swizzle >= 2) {
-    const unsigned ncb1 = (unsigned)(cout / (32 * NB)), ncb = ncb1 * (unsigned)NGRP;      // GRP: (group, column block) slots
-    const unsigned xcd = bxx & 7u, slot = bxx >> 3;
-    byy = slot % ncb;
-    if (GRP) {
-      grp = byy / ncb1;
-      byy -= grp * ncb1;
-    }
-    if (swizzle == 2) {
-      bxx = (slot / ncb) * 8u + xcd;
-      if (bxx >= nrw) return;
-    } else {
-      const unsigned q = nrw >> 3, r = nrw & 7u, mine = q + (xcd < r ? 1u : 0u), j = slot / ncb;
-      if (j >= mine) return;
-      bxx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-  } else {
-    bxx = xcd_tile(bxx, gridDim.x, swizzle);
-  }
-  if (heavy_first) bxx = nrw - 1u - bxx;
-  if (GRP) Y += (long long)grp * n_out * cout;
-  const long long tile = (long long)bxx * 4 + w;
-  const long long row0 = tile * 32;
-  const bool active = row0 < n_out;
-  const int nb0 = byy * NB;
+  FwdTile ft;      // GRP: the group index rides in the column-block slot of the 1-D grid
+  if (!ft.map<NB, (GRP ? 4 : 1)>(swizzle, n_out, cout, w)) return;
+  if (GRP) Y += (long long)ft.grp * n_out * cout;
   const int TNB = cout >> 5, CC = cin >> 5;
   const int p = l & 7, rsub = l >> 3;
 
   f32x16 acc[NB], accx[NB];      // accx: the fp16x3 cross terms (mfma_terms)
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-#pragma unroll
-  for (int b = 0; b < (int)(sizeof(accx) / sizeof(accx[0])); ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accx[b][r] = 0.f;
+  zero_acc(acc);
+  zero_acc(accx);
 
-  unsigned mymask = 0u;
-  if (active) mymask = tile_mask ? (unsigned)tile_mask[tile] : ((K >= 32) ? ~0u : ((1u << K) - 1u));
-  if (GRP) mymask &= 0x11111111u << grp;      // offsets k with k mod 4 == grp (k_conv_fwd_tall's groups)
-  mymask = __builtin_amdgcn_readfirstlane(mymask);
+  const unsigned mymask = tile_offsets(tile_mask, ft.tile, K, ft.active, GRP ? offset_group(ft.grp) : ~0u);
   if (l == 0) wmask[w] = mymask;
-  for (int e = l; e < (K < ISM_H ? K : ISM_H) * 32; e += 64) {
-    const int k = e >> 5, r = e & 31;
-    int v = -1;
-    if (active && ((mymask >> k) & 1u) && row0 + r < n_out) v = tbl ? tbl[(long long)k * n_out + row0 + r] : (int)(row0 + r);
-    Ism[w][k][(r & 7) * 4 + (r >> 3)] = v;
-  }
-  int ib[6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const int e = 32 * ISM_H + l + 64 * j, k = e >> 5, r = e & 31;
-    int v = -1;
-    if (k < K && active && ((mymask >> k) & 1u) && row0 + r < n_out) v = tbl[(long long)k * n_out + row0 + r];
-    ib[j] = v;
-  }
-  bool second_half = false;
+  HalfIndexTable idx;
+  idx.fill(Ism[w], tbl, n_out, K, ft, mymask, l);
   __syncthreads();
   const unsigned wgmask = __builtin_amdgcn_readfirstlane(wmask[0] | wmask[1] | wmask[2] | wmask[3]);
 
@@ -1041,28 +1100,19 @@ __global__ void __launch_bounds__(256, (NB <= 2 ? 4 : 2)) k_conv_fwd_dma(const f
   unsigned pc[4];
 #pragma unroll
   for (int ps = 0; ps < 4; ++ps) pc[ps] = (unsigned)((p ^ a_swz(rsub + 8 * ps)) << 4);
-#define GCL_DMA_A(KK, CCV)                                                                                     \
+#define GCL_DMA_A(S)                                                                                           \
   {                                                                                                            \
-    if ((KK) >= ISM_H && !second_half) {                                                                       \
-      second_half = true;                                                                                      \
-      WAVE_FENCE();                                                                                            \
-      _Pragma("unroll") for (int j_ = 0; j_ < 6; ++j_) {                                                       \
-        const int e_ = 32 * ISM_H + l + 64 * j_;                                                               \
-        if ((e_ >> 5) < K) Ism[w][(e_ >> 5) - ISM_H][((e_ & 31) & 7) * 4 + ((e_ & 31) >> 3)] = ib[j_];         \
-      }                                                                                                        \
-      WAVE_FENCE();                                                                                            \
-    }                                                                                                          \
-    const int4 ri_ = *reinterpret_cast<const int4*>(&Ism[w][(KK) >= ISM_H ? (KK) - ISM_H : (KK)][rsub * 4]);    \
-    const unsigned co_ = (unsigned)(CCV)*128u;                                                                 \
+    const int4 ri_ = idx.rows((S).k, K, l);                                                                    \
+    const unsigned co_ = (unsigned)(S).cc * 128u;                                                              \
     dma16<0>(xrsrc, lds_a, (unsigned)ri_.x * row_bytes + pc[0], co_);                                          \
     dma16<1024>(xrsrc, lds_a, (unsigned)ri_.y * row_bytes + pc[1], co_);                                       \
     dma16<2048>(xrsrc, lds_a, (unsigned)ri_.z * row_bytes + pc[2], co_);                                       \
     dma16<3072>(xrsrc, lds_a, (unsigned)ri_.w * row_bytes + pc[3], co_);                                       \
   }
   // weight block (k, cc) of this workgroup's columns: BLK uint4, lane-linear; wave w moves pieces e * 256 + 64 w .. + 63
-#define GCL_DMA_B(KK, CCV, BUF)                                                                                \
+#define GCL_DMA_B(S, BUF)                                                                                      \
   {                                                                                                            \
-    const unsigned blk_ = (unsigned)((((KK)*CC + (CCV)) * TNB + nb0) * (2 * NPL * 64)) * 16u;                   \
+    const unsigned blk_ = (unsigned)((((S).k * CC + (S).cc) * TNB + ft.nb0) * (2 * NPL * 64)) * 16u;            \
     const unsigned dst_ = lds_b + (unsigned)(BUF) * (unsigned)(BLK * 16);                                      \
     dma16<0>(wrsrc, dst_, (unsigned)t * 16u, blk_);                                                            \
     if (NB >= 2) dma16<4096>(wrsrc, dst_, (unsigned)t * 16u + 4096u, blk_);                                    \
@@ -1071,117 +1121,72 @@ __global__ void __launch_bounds__(256, (NB <= 2 ? 4 : 2)) k_conv_fwd_dma(const f
       dma16<12288>(wrsrc, dst_, (unsigned)t * 16u + 12288u, blk_);                                             \
     }                                                                                                          \
   }
-#define GCL_ADVANCE(KV, CV, HAS)             \
-  {                                          \
-    CV += 1;                                 \
-    if (CV == CC) {                          \
-      CV = 0;                                \
-      if (m_rest) {                          \
-        KV = __builtin_ctz(m_rest);          \
-        m_rest &= m_rest - 1;                \
-      } else {                               \
-        HAS = false;                         \
-      }                                      \
-    }                                        \
-  }
   // every ordinary load of the prologue is consumed HERE: with loads of its own pending hipcc would put vmcnt waits into the
   // loop (it counts the DMAs it cannot see as nothing and would wait in the middle of a DMA sequence)
-  asm volatile("" ::"v"(ib[0]), "v"(ib[1]), "v"(ib[2]), "v"(ib[3]), "v"(ib[4]), "v"(ib[5]) : "memory");
+  asm volatile("" ::"v"(idx.ib[0]), "v"(idx.ib[1]), "v"(idx.ib[2]), "v"(idx.ib[3]), "v"(idx.ib[4]), "v"(idx.ib[5]) : "memory");
   if (wgmask != 0u) {
-    unsigned m_rest = wgmask & (wgmask - 1);
-    int kc = __builtin_ctz(wgmask), cc = 0;
-    bool mine_cur = (mymask >> kc) & 1u;
-    if (mine_cur) GCL_DMA_A(kc, 0);
-    GCL_DMA_B(kc, 0, 0);
+    StepCursor cur;
+    cur.start(wgmask);
+    bool mine_cur = (mymask >> cur.k) & 1u;
+    if (mine_cur) GCL_DMA_A(cur);
+    GCL_DMA_B(cur, 0);
     int buf = 0;
     while (true) {
       dma_wait_all();       // this wave's DMAs have landed: A(s) in its tile, its part of B(s)
       __syncthreads();      // everybody's part of B(s) is in LDS; everybody's reads of step s-1 are done
-      int kn = kc, cn = cc;
-      bool hasn = true;
-      GCL_ADVANCE(kn, cn, hasn);
-      const bool mine_n = hasn && ((mymask >> kn) & 1u);
-      if (hasn) GCL_DMA_B(kn, cn, buf ^ 1);
+      StepCursor nxt = cur;
+      nxt.advance(CC);
+      const bool mine_n = nxt.has && ((mymask >> nxt.k) & 1u);
+      if (nxt.has) GCL_DMA_B(nxt, buf ^ 1);
       if (mine_cur) {
-        u32x4 ap[2][2];
-        if (PRE) {   // row image: dwords [0,16) = hi of channels 0..31, [16,32) = lo
+        // A fragments of step s -> registers, then A(s+1) -> the wave's tile: the DMA overwrites the tile, so this wave's
+        // fragment reads must have returned (the asm consumes them)
+        u32x4 ap[2][3];
+        if (PRE) {
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            ap[m][0] = *reinterpret_cast<const u32x4*>(&Asm[w][i][((2 * m + h) ^ a_swz(i)) << 2]);
-            ap[m][1] = *reinterpret_cast<const u32x4*>(&Asm[w][i][((4 + 2 * m + h) ^ a_swz(i)) << 2]);
-          }
+          for (int m = 0; m < 2; ++m) a_frag_planes(Asm[w], m, l, ap[m]);
           if (mine_n) {
-            // the DMA overwrites the tile: this wave's fragment reads must have returned (the asm consumes them)
             asm volatile("" : "+v"(ap[0][0]), "+v"(ap[0][1]), "+v"(ap[1][0]), "+v"(ap[1][1])::"memory");
-            GCL_DMA_A(kn, cn);
+            GCL_DMA_A(nxt);
           }
         } else {     // fp32 rows: the raw pieces come out of the tile and are split into the two fp16 planes here
-          typedef float f32x4 __attribute__((ext_vector_type(4)));
           f32x4 f[2][2];
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            f[m][0] = *reinterpret_cast<const f32x4*>(&Asm[w][i][((4 * m + 2 * h) ^ a_swz(i)) << 2]);
-            f[m][1] = *reinterpret_cast<const f32x4*>(&Asm[w][i][((4 * m + 2 * h + 1) ^ a_swz(i)) << 2]);
-          }
+          for (int m = 0; m < 2; ++m) a_frag_rows(Asm[w], m, l, f[m]);
           if (mine_n) {
             asm volatile("" : "+v"(f[0][0]), "+v"(f[0][1]), "+v"(f[1][0]), "+v"(f[1][1])::"memory");
-            GCL_DMA_A(kn, cn);
+            GCL_DMA_A(nxt);
           }
-          if (!GRP) {
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
-              split8<PL>(make_float4(f[m][0][0], f[m][0][1], f[m][0][2], f[m][0][3]),
-                         make_float4(f[m][1][0], f[m][1][1], f[m][1][2], f[m][1][3]), a_scale, ap[m]);
-          } else {      // k_conv_fwd_tall's products, in its order: m, then the column blocks
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-              u32x4 ad[3];
-              split8<PL>(make_float4(f[m][0][0], f[m][0][1], f[m][0][2], f[m][0][3]),
-                         make_float4(f[m][1][0], f[m][1][1], f[m][1][2], f[m][1][3]), a_scale, ad);
-              dw_a_planes(ad);
-#pragma unroll
-              for (int b = 0; b < NB; ++b) {
-                const u32x4* bb = &Bsm[buf * BLK + ((b * 2 + m) * NPL) * 64 + l];
-                u32x4 bp[3];
-                bp[0] = bb[0];
-                bp[1] = bb[64];
-                mfma_terms_dw<PL>(ad, bp, acc[b]);
-              }
+          for (int m = 0; m < 2; ++m) {
+            split8<PL>(f[m], a_scale, ap[m]);
+            if (GRP) {      // k_conv_fwd_tall's products, in its order: m, then the column blocks
+              dw_a_planes(ap[m]);
+              mma_blocks_dw<PL>(ap[m], Bsm + buf * BLK, m, l, acc);
             }
           }
         }
         if (!GRP) {
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-              const u32x4* bb = &Bsm[buf * BLK + ((b * 2 + m) * NPL) * 64 + l];
-              u32x4 bp[2];
-              bp[0] = bb[0];
-              bp[1] = bb[64];
-              mfma_terms<PL>(ap[m], bp, acc[b], accx[b]);
-            }
-          }
+          for (int m = 0; m < 2; ++m) mma_blocks<PL>(ap[m], Bsm + buf * BLK, m, l, acc, accx);
         }
       } else if (mine_n) {
-        GCL_DMA_A(kn, cn);
+        GCL_DMA_A(nxt);
       }
-      if (!hasn) break;
+      if (!nxt.has) break;
       buf ^= 1;
-      kc = kn;
-      cc = cn;
+      cur = nxt;
       mine_cur = mine_n;
     }
   }
 #undef GCL_DMA_A
 #undef GCL_DMA_B
-#undef GCL_ADVANCE
   if (!GRP) {
 #pragma unroll
-    for (int b = 0; b < NB; ++b) fold_cross<PL>(acc[b], accx[(PL == 4) ? b : 0]);
+    for (int b = 0; b < NB; ++b) fold_cross<PL>(acc[b], accx[b]);
   }
-  conv_fwd_epilogue<NB, EPI>(acc, &Asm[0][0][0], order, n_out, cout, bias, Y, stats, GRP ? 1.f : out_scale, epi, tile, bxx, nb0,
-                             active);
+  conv_fwd_epilogue<NB, EPI>(acc, &Asm[0][0][0], order, n_out, cout, bias, Y, stats, GRP ? 1.f : out_scale, epi, ft.tile,
+                             ft.bxx, ft.nb0, ft.active);
 }
 
 // y = epilogue(((slab 0 + slab 1) + slab 2) + slab 3): k_conv_fwd_tall's group order and its epilogue expression, on the raw
@@ -1276,54 +1281,30 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
   // [A tiles: 16 waves x 4 KB][weight blocks: 4 groups x 2 buffers x 8 KB]; after the loop the same 128 KB hold the partial
   // accumulators of groups 1 - 3 (96 KB)
   __shared__ __attribute__((aligned(16))) float lds[16 * 1024 + G * 2 * BLK * 4];
-  __shared__ __attribute__((aligned(16))) int Ism[4][27][32];
+  __shared__ __attribute__((aligned(16))) int Ism[4][27][32];      // all 27 offsets of a tile (idx_slot), shared by its four waves
   __shared__ unsigned wmask[G][4];
   float (*Asm)[32][32] = reinterpret_cast<float (*)[32][32]>(lds);
   u32x4* const Ball = reinterpret_cast<u32x4*>(lds + 16 * 1024);
   const int t = threadIdx.x, l = t & 63, w16 = t >> 6, wt = w16 & 3, g = w16 >> 2, tg = t & 255;
-  const int i = l & 31, h = l >> 5;
   u32x4* const Bg = Ball + g * 2 * BLK;
-  unsigned bxx = blockIdx.x, byy;
-  const bool heavy_first = (swizzle & 16) != 0;
-  const unsigned nrw = (unsigned)((n_out + CONV_ROWS - 1) / CONV_ROWS);
-  {
-    const unsigned ncb = (unsigned)(cout / (32 * NB));
-    const unsigned xcd = bxx & 7u, slot = bxx >> 3;
-    byy = slot % ncb;
-    bxx = (slot / ncb) * 8u + xcd;
-    if (bxx >= nrw) return;
-  }
-  if (heavy_first) bxx = nrw - 1u - bxx;
-  const long long tile = (long long)bxx * 4 + wt;
-  const long long row0 = tile * 32;
-  const bool active = row0 < n_out;
-  const int nb0 = byy * NB;
+  FwdTile ft;      // always the 1-D grid of swizzle 2
+  if (!ft.map<NB, 1>(2 | (swizzle & 16), n_out, cout, wt)) return;
   const int TNB = cout >> 5, CC = cin >> 5;
-  const int p = l & 7, rsub = l >> 3;
-  // offsets of group g: k with k mod 4 == g
-  unsigned gsel = 0u;
-  for (int k = 0; k < K; ++k)
-    if ((k & 3) == g) gsel |= 1u << k;
 
   // ONE accumulator set (1024 threads per workgroup leave 128 registers per wave): both operands of an inference launch
   // are narrow-range (activations, weights), so the activation planes are re-scaled on the fly as in the weight-gradient
   // kernels (mfma_terms_dw) instead of summing the cross terms apart
   f32x16 acc[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+  zero_acc(acc);
 
-  unsigned tmask = 0u;
-  if (active) tmask = tile_mask ? (unsigned)tile_mask[tile] : ((1u << K) - 1u);
-  tmask = __builtin_amdgcn_readfirstlane(tmask);
-  const unsigned mymask = tmask & gsel;
+  const unsigned tmask = tile_offsets(tile_mask, ft.tile, K, ft.active);
+  const unsigned mymask = tmask & offset_group(g) & ((1u << K) - 1u);      // offsets of group g
   if (l == 0) wmask[g][wt] = mymask;
   for (int e = l + 64 * g; e < K * 32; e += 64 * G) {      // the four waves of a tile share the index loads
     const int k = e >> 5, r = e & 31;
     int v = -1;
-    if (active && ((tmask >> k) & 1u) && row0 + r < n_out) v = tbl[(long long)k * n_out + row0 + r];
-    Ism[wt][k][(r & 7) * 4 + (r >> 3)] = v;
+    if (ft.active && ((tmask >> k) & 1u) && ft.row0 + r < n_out) v = tbl[(long long)k * n_out + ft.row0 + r];
+    Ism[wt][k][idx_slot(r)] = v;
   }
   __syncthreads();
   const unsigned wgmask = wmask[g][0] | wmask[g][1] | wmask[g][2] | wmask[g][3];
@@ -1335,63 +1316,35 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
   }
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (int)x_bytes, 0x00020000);
   const unsigned row_bytes = (unsigned)cin * 4u;
-#define GCLT_GATHER_A(KK, CCV)                                                                                  \
-  {                                                                                                             \
-    const int4 ri_ = *reinterpret_cast<const int4*>(&Ism[wt][(KK)][rsub * 4]);                                 \
-    const unsigned co_ = (unsigned)(CCV)*128u + (unsigned)p * 16u;                                              \
-    st[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.x * row_bytes + co_), 0, 0)); \
-    st[1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.y * row_bytes + co_), 0, 0)); \
-    st[2] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.z * row_bytes + co_), 0, 0)); \
-    st[3] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)((unsigned)ri_.w * row_bytes + co_), 0, 0)); \
-  }
-#define GCLT_LOAD_B(KK, CCV)                                                                     \
-  {                                                                                              \
-    const u32x4* src_ = Wp + (((long long)(KK)*CC + (CCV)) * TNB + nb0) * (2 * NPL * 64);        \
-    br[0] = src_[tg];                                                                            \
-    br[1] = src_[256 + tg];                                                                      \
-  }
-#define GCLT_STORE_LDS(MINE, BUF)                                                                            \
-  {                                                                                                          \
-    if (MINE) {                                                                                              \
-      _Pragma("unroll") for (int ps = 0; ps < 4; ++ps)                                                       \
-          *reinterpret_cast<float4*>(&Asm[w16][rsub + 8 * ps][(p ^ a_swz(rsub + 8 * ps)) << 2]) = st[ps];    \
-    }                                                                                                        \
-    Bg[(BUF)*BLK + tg] = br[0];                                                                              \
-    Bg[(BUF)*BLK + 256 + tg] = br[1];                                                                        \
-  }
-#define GCLT_ADVANCE(KV, CV, HAS)            \
-  {                                          \
-    CV += 1;                                 \
-    if (CV == CC) {                          \
-      CV = 0;                                \
-      if (m_rest) {                          \
-        KV = __builtin_ctz(m_rest);          \
-        m_rest &= m_rest - 1;                \
-      } else {                               \
-        HAS = false;                         \
-      }                                      \
-    }                                        \
-  }
+  float4 st[4];
+  u32x4 br[2];
+  auto gather_a = [&](const StepCursor& s) __attribute__((always_inline)) {
+    gather_rows(st, xrsrc, idx_rows(Ism[wt][s.k], l >> 3), row_bytes, (unsigned)s.cc * 128u + (unsigned)(l & 7) * 16u);
+  };
+  auto load_b = [&](const StepCursor& s) __attribute__((always_inline)) {
+    load_b_block<BLK>(br, Wp + (((long long)s.k * CC + s.cc) * TNB + ft.nb0) * (2 * NPL * 64), tg);
+  };
+  auto store_lds = [&](bool mine, int buf) __attribute__((always_inline)) {
+    if (mine) store_a_tile(Asm[w16], st, l);
+    store_b_block<BLK>(Bg + buf * BLK, br, tg);
+  };
   if (n_iter > 0) {
-    unsigned m_rest = wgmask ? (wgmask & (wgmask - 1)) : 0u;
-    float4 st[4];
-    u32x4 br[2];
-    bool has0 = wgmask != 0u;
-    int k0 = has0 ? __builtin_ctz(wgmask) : 0;
-    bool mine0 = has0 && ((mymask >> k0) & 1u);
-    int k1 = k0, c1 = 0;
-    bool has1 = has0;
-    if (has0) {
-      if (mine0) GCLT_GATHER_A(k0, 0);
-      GCLT_LOAD_B(k0, 0);
-      GCLT_ADVANCE(k1, c1, has1);
-      GCLT_STORE_LDS(mine0, 0);
+    // as k_conv_fwd_split: step 0 -> LDS, step 1 -> registers; a group without offsets only takes the barriers
+    StepCursor s0;
+    s0.start(wgmask);
+    const bool mine0 = s0.has && ((mymask >> s0.k) & 1u);
+    StepCursor s1 = s0;
+    if (s0.has) {
+      if (mine0) gather_a(s0);
+      load_b(s0);
+      s1.advance(CC);
+      store_lds(mine0, 0);
     }
     bool mine1 = false;
-    if (has1) {
-      mine1 = (mymask >> k1) & 1u;
-      if (mine1) GCLT_GATHER_A(k1, c1);
-      GCLT_LOAD_B(k1, c1);
+    if (s1.has) {
+      mine1 = (mymask >> s1.k) & 1u;
+      if (mine1) gather_a(s1);
+      load_b(s1);
     }
     __syncthreads();
     int buf = 0;
@@ -1402,45 +1355,38 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
           u32x4 ap[3];
-          float4 f0 = *reinterpret_cast<const float4*>(&Asm[w16][i][((4 * m + 2 * h) ^ a_swz(i)) << 2]);
-          float4 f1 = *reinterpret_cast<const float4*>(&Asm[w16][i][((4 * m + 2 * h + 1) ^ a_swz(i)) << 2]);
-          split8<PL>(f0, f1, a_scale, ap);
+          f32x4 f[2];
+          a_frag_rows(Asm[w16], m, l, f);
+          split8<PL>(f, a_scale, ap);
           dw_a_planes(ap);
+          // mma_blocks_dw's loop, written out: through the helper the EPI instance's private segment grows from 52 to 60 bytes
 #pragma unroll
           for (int b = 0; b < NB; ++b) {
-            const u32x4* bb = &Bg[buf * BLK + ((b * 2 + m) * NPL) * 64 + l];
             u32x4 bp[3];
-            bp[0] = bb[0];
-            bp[1] = bb[64];
+            b_frag<PL>(Bg + buf * BLK, b, m, l, bp);
             mfma_terms_dw<PL>(ap, bp, acc[b]);
           }
         }
       }
-      if (has1) {      // next step: registers -> LDS (A: own tile, after this wave's reads; B: the group's other buffer)
+      if (s1.has) {      // next step: registers -> LDS (A: own tile, after this wave's reads; B: the group's other buffer)
         WAVE_FENCE();
-        GCLT_STORE_LDS(mine1, buf ^ 1);
+        store_lds(mine1, buf ^ 1);
       }
-      int k2 = k1, c2 = c1;
-      bool has2 = has1, mine2 = false;
-      if (has1) GCLT_ADVANCE(k2, c2, has2);
-      if (has2) {
-        mine2 = (mymask >> k2) & 1u;
-        if (mine2) GCLT_GATHER_A(k2, c2);
-        GCLT_LOAD_B(k2, c2);
+      StepCursor s2 = s1;
+      if (s1.has) s2.advance(CC);
+      bool mine2 = false;
+      if (s2.has) {
+        mine2 = (mymask >> s2.k) & 1u;
+        if (mine2) gather_a(s2);
+        load_b(s2);
       }
       __syncthreads();
       buf ^= 1;
-      mine_cur = has1 && mine1;
+      mine_cur = s1.has && mine1;
       mine1 = mine2;
-      k1 = k2;
-      c1 = c2;
-      has1 = has2;
+      s1 = s2;
     }
   }
-#undef GCLT_GATHER_A
-#undef GCLT_LOAD_B
-#undef GCLT_STORE_LDS
-#undef GCLT_ADVANCE
   // partial accumulators of groups 1 - 3 through LDS (the loop's last barrier has passed: tiles and weight blocks are free)
   float* const red = lds;      // [g - 1][wt][b * 16 + r][64 lanes]
   if (g > 0) {
@@ -1450,15 +1396,17 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
       for (int r = 0; r < 16; ++r) red[(((g - 1) * 4 + wt) * (NB * 16) + b * 16 + r) * 64 + l] = acc[b][r];
   }
   __syncthreads();
-  if (g > 0 || !active) return;
+  if (g > 0 || !ft.active) return;
 #pragma unroll
   for (int q = 0; q < G - 1; ++q)      // group order: ((g0 + g1) + g2) + g3
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[b][r] += red[((q * 4 + wt) * (NB * 16) + b * 16 + r) * 64 + l];
+  // conv_fwd_epilogue's expression without the statistics, not conv_fwd_epilogue<2, EPI>: that spills 108 / 144 bytes, not 56 / 52
+  const int i = l & 31, h = l >> 5, nb0 = ft.nb0;
   int orow_l = -1;
-  if ((l < 32) && (row0 + l < n_out)) orow_l = order ? order[row0 + l] : (int)(row0 + l);
+  if ((l < 32) && (ft.row0 + l < n_out)) orow_l = order ? order[ft.row0 + l] : (int)(ft.row0 + l);
   float ymax = 0.f;
   // as in conv_fwd_epilogue: the residual / gate operand of all NB x 16 elements is fetched before the first store
   const bool has_rsd = EPI && epi.residual;
@@ -1497,7 +1445,7 @@ __global__ void __launch_bounds__(1024, 1) k_conv_fwd_tall(const float* __restri
   if (EPI && epi.y_amax) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) ymax = fmaxf(ymax, __shfl_xor(ymax, o));
-    if (l == 0) amax_slot_publish(epi.y_amax, __float_as_int(ymax), (unsigned)tile);
+    if (l == 0) amax_slot_publish(epi.y_amax, __float_as_int(ymax), (unsigned)ft.tile);
   }
 }
 
