@@ -119,6 +119,14 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N]) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 }
+template <int NI, int NJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NI][NJ]) {
+#pragma unroll
+  for (int a = 0; a < NI; ++a) zero_acc(acc[a]);
+}
+// Row of accumulator cell r of lane l inside its 32 x 32 MFMA block (the column is l & 31).  A sum of a part of r and a part
+// of l: a kernel that keeps the lane's part in a base pointer takes the two apart as acc_cell_row(r, 0) and acc_cell_row(0, l).
+__device__ __forceinline__ int acc_cell_row(int r, int l) { return (r & 3) + 8 * (r >> 2) + 4 * (l >> 5); }
 
 template <int NB>  // 32-column blocks per wave
 __global__ void __launch_bounds__(256) k_conv_fwd(const float* __restrict__ X, const float4* __restrict__ Wp,
@@ -1456,6 +1464,99 @@ struct SegOffW {
   long long off[130];
 };
 
+// The work of a workgroup of a pair-list kernel: chunks [c0, c1) of the k-major pair list, channel tile (ca0, cb0) of
+// TA x TB, slab bx + k for offset k.  Three grids: 2-D (x = chunk range, y = tile); with n_tiles > 0 the XCD-aware 1-D
+// grid -- workgroups are dealt round-robin to the 8 XCDs, so the n_tiles channel tiles that re-read the SAME pair range
+// get consecutive slots of ONE XCD and share its L2; RG: the same deal with the K offsets of row range j in the place of
+// the tiles, the workgroup then takes the cell [rg_lo, rg_hi) of offset rg_k as chunks [0, c1) (slab j K + rg_k).
+// idle: nothing to do, uniform over the workgroup (an empty RG cell is not idle: it still writes its zero slab).
+constexpr int DW_SUB = GCL_PAIR_CHUNK / 32;      // sub-chunks of 32 pairs (a wave's gather tile) per 128-pair chunk
+template <int TA, int TB, bool RG = false>
+struct DwTile {
+  int bx, by, ca0, cb0, rg_k;
+  long long c0, c1, rg_lo, rg_hi;
+  bool idle;
+  __device__ __forceinline__ void map(int cb, long long n_chunks, int per, int n_wg_x = 0, int n_tiles = 0, int K = 0,
+                                      const int* __restrict__ bounds = nullptr, int n_ranges = 0) {
+    rg_k = 0, rg_lo = 0, rg_hi = 0;
+    c0 = 0, c1 = 0, ca0 = 0, cb0 = 0;      // an idle workgroup has an empty range
+    if (RG || n_tiles > 0) {
+      const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, n = RG ? K : n_tiles;
+      by = slot % n;
+      bx = (slot / n) * 8 + xcd;
+      idle = bx >= (RG ? n_ranges : n_wg_x);
+    } else {
+      bx = blockIdx.x, by = blockIdx.y;
+      idle = false;
+    }
+    if (RG) {
+      if (idle) return;
+      rg_k = by;
+      rg_lo = bounds[rg_k * (n_ranges + 1) + bx];
+      rg_hi = bounds[rg_k * (n_ranges + 1) + bx + 1];
+      bx *= K, by = 0;
+      c0 = 0, c1 = (rg_hi - rg_lo + GCL_PAIR_CHUNK - 1) / GCL_PAIR_CHUNK;
+    } else {
+      c0 = (long long)bx * per;
+      c1 = (c0 + per < n_chunks) ? c0 + per : n_chunks;
+      idle = idle || c0 >= c1;
+    }
+    const int tiles_b = (cb + TB - 1) / TB;
+    ca0 = (by / tiles_b) * TA, cb0 = (by % tiles_b) * TB;
+  }
+  // lanes 0 .. 31: the pair of row `lane` of 32-pair sub-chunk sc (four per chunk) of the workgroup's list, -1 behind its end
+  __device__ __forceinline__ void load_pairs(const int* __restrict__ pair_a, const int* __restrict__ pair_b, long long sc,
+                                             int l, int& ia, int& ib) const {
+    ia = -1, ib = -1;
+    const long long p = rg_lo + sc * 32 + l;
+    if (l < 32 && (RG ? p < rg_hi : sc < c1 * DW_SUB)) {      // a cell ends inside its last chunk
+      ia = pair_a[p];
+      ib = pair_b[p];
+    }
+  }
+};
+
+// The offset whose segment of the pair list a workgroup is in.  step: the chunk at pair position pbase comes next; where it
+// lies behind the segment, the sums of offset k are flushed and the cursor moves on past empty segments.
+struct SegCursor {
+  int k;
+  __device__ __forceinline__ void init(const SegOffW& seg, long long c0) {
+    k = 0;
+    while (seg.off[k + 1] <= c0 * GCL_PAIR_CHUNK) ++k;
+  }
+  template <class Flush>
+  __device__ __forceinline__ void step(const SegOffW& seg, long long pbase, Flush&& flush) {
+    if (pbase >= seg.off[k + 1]) {
+      flush(k);
+      while (seg.off[k + 1] <= pbase) ++k;
+    }
+  }
+};
+
+// One gathered operand: rows through a buffer resource -- a padding pair (row -1) wraps beyond the tensor and reads zeros
+// (no branch, no 64-bit address arithmetic per row) -- and the byte offset of the lane's 16-byte piece inside a row.
+struct DwOperand {
+  __amdgpu_buffer_rsrc_t rsrc;
+  unsigned row_bytes, col;
+  __device__ __forceinline__ DwOperand(const float* p, unsigned bytes, int channels, unsigned col_bytes)
+      : rsrc(__builtin_amdgcn_make_buffer_rsrc((void*)p, 0, (int)bytes, 0x00020000)), row_bytes((unsigned)channels * 4u),
+        col(col_bytes) {}
+  __device__ __forceinline__ float4 piece(unsigned row) const {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(row * row_bytes + col), 0, 0));
+  }
+};
+// g[ps] = the lane's piece of the row whose index lane row_of(ps) of the wave holds in idx (DwTile::load_pairs)
+template <int N, class RowOf>
+__device__ __forceinline__ void gather_pairs(const DwOperand& op, int idx, RowOf row_of, float4 (&g)[N]) {
+#pragma unroll
+  for (int ps = 0; ps < N; ++ps) g[ps] = op.piece((unsigned)__shfl(idx, row_of(ps)));
+}
+template <int N>
+__device__ __forceinline__ void store_row_image(unsigned char* img, const unsigned (&dst)[N], const float4 (&g)[N]) {
+#pragma unroll
+  for (int ps = 0; ps < N; ++ps) *reinterpret_cast<float4*>(img + dst[ps]) = g[ps];
+}
+
 // Flush of the weight-gradient accumulators: the four waves of a workgroup hold partial sums over disjoint pairs;
 // they are added in wave order through LDS (deterministic) and ONE slab per (workgroup, offset) goes to memory.
 template <int TCA, int TCB>
@@ -1478,7 +1579,7 @@ __device__ __forceinline__ void bwd_weight_flush(f32x16 (&acc)[TCA / 32][TCB / 3
     float v = lds[e] + lds[TCA * TCB + e] + lds[2 * TCA * TCB + e] + lds[3 * TCA * TCB + e];
     int ll = e & 63, r = (e >> 6) & 15, blk = e >> 10;
     int a = blk / NBJ, b = blk % NBJ;
-    int row = ca0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (ll >> 5);
+    int row = ca0 + a * 32 + acc_cell_row(r, ll);
     slab[(long long)row * cb + cb0 + b * 32 + (ll & 31)] = v;
   }
   __syncthreads();   // LDS goes back to the gather tiles
@@ -1497,32 +1598,22 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight(const float* __restrict
   float (*Bs)[32][TCB] = reinterpret_cast<float (*)[32][TCB]>(lds_all + 4 * 32 * TCA);
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = l & 31, h = l >> 5;
-  const int tiles_b = cb / TCB;
-  const int ca0 = (blockIdx.y / tiles_b) * TCA, cb0 = (blockIdx.y % tiles_b) * TCB;
-  const long long c0 = (long long)blockIdx.x * per;
-  const long long c1 = (c0 + per < n_chunks) ? c0 + per : n_chunks;
-  if (c0 >= c1) return;   // uniform over the workgroup
+  DwTile<TCA, TCB> tile;
+  tile.map(cb, n_chunks, per);
+  if (tile.idle) return;
+  const int ca0 = tile.ca0, cb0 = tile.cb0;
 
   f32x16 acc[NBI][NBJ];
-#pragma unroll
-  for (int a = 0; a < NBI; ++a)
-#pragma unroll
-    for (int b = 0; b < NBJ; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
+  zero_acc(acc);
   auto flush = [&](int k) {
-    bwd_weight_flush<TCA, TCB>(acc, lds_all, slabs + (long long)(blockIdx.x + k) * ((long long)ca * cb), ca0, cb0, cb);
+    bwd_weight_flush<TCA, TCB>(acc, lds_all, slabs + (long long)(tile.bx + k) * ((long long)ca * cb), ca0, cb0, cb);
   };
 
-  int kcur = 0;
-  while (seg.off[kcur + 1] <= c0 * GCL_PAIR_CHUNK) ++kcur;
-  for (long long c = c0; c < c1; ++c) {
+  SegCursor cur;
+  cur.init(seg, tile.c0);
+  for (long long c = tile.c0; c < tile.c1; ++c) {
     const long long pbase = c * GCL_PAIR_CHUNK;
-    if (pbase >= seg.off[kcur + 1]) {
-      flush(kcur);
-      while (seg.off[kcur + 1] <= pbase) ++kcur;
-    }
+    cur.step(seg, pbase, flush);
     const long long p0 = pbase + w * 32;
     int ia = -1, ib = -1;
     if (l < 32) {
@@ -1561,7 +1652,7 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight(const float* __restrict
           acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
     }
   }
-  flush(kcur);
+  flush(cur.k);
 }
 
 // ---- weight gradient on PRE-SPLIT operands (fp16 plane images from gcl_split_planes) -----------------------------
@@ -1580,6 +1671,23 @@ __device__ __forceinline__ u32x2 lds_read_tr16(unsigned base) {      // one base
 }
 template <int TC>
 __device__ __forceinline__ int tr_swz(int row) { return (TC == 64) ? ((row & 3) << 1) : (((row >> 1) & 1) << 1); }
+__device__ __forceinline__ unsigned lds_address(const void* p) {
+  return (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)p);
+}
+// byte offset of 16-byte piece `piece` of row `row` inside a row image
+template <int TC>
+__device__ __forceinline__ unsigned tr_piece_offset(int row, int piece) {
+  return (unsigned)(row * (TC * 4) + (((piece >> 1) ^ tr_swz<TC>(row)) * 32) + (piece & 1) * 16);
+}
+// The lane's read addresses [plane] for 32-channel slice `slice` of the row image at LDS address `lds`: lane 16 g + 4 q + p
+// of a transposed read supplies row q (+ 8 in the upper half of the wave), 16-channel half g & 1, 8-byte piece p
+template <int TC>
+__device__ __forceinline__ void tr_read_bases(unsigned lds, int slice, unsigned (&base)[2]) {
+  const int l = threadIdx.x & 63, q = (l & 15) >> 2, pp = l & 3, c16 = (l >> 4) & 1, trow = 8 * (l >> 5) + q;
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl)
+    base[pl] = lds + trow * (TC * 4) + (((slice * 4 + pl * 2 + c16) ^ tr_swz<TC>(q)) * 32) + pp * 8;
+}
 // both planes of the fragment of 32-channel slice (base addresses precomputed per lane) for the 16-pair half HALF
 template <int TC, int HALF, int EXTRA = 0>      // EXTRA: constant byte offset added to every read (a second tile buffer)
 __device__ __forceinline__ void tr_fragment(unsigned base_hi, unsigned base_lo, u32x4* f) {
@@ -1619,6 +1727,25 @@ __device__ __forceinline__ void tr_mma_half(const unsigned (*baseA)[2], const un
     for (int b = 0; b < NBJ; ++b) mfma_terms_dw<4>(fa[a], fb[b], acc[a][b]);
   }
 }
+// The same products from fp32 rows: va[a] / vb[b] = the lane's eight consecutive pairs of its channel of slice a / b, split
+// here into PL planes.  A fragments first, then per B slice.
+template <int PL, int NBI, int NBJ>
+__device__ __forceinline__ void mma_rows_dw(const float (&va)[NBI][8], const float (&vb)[NBJ][8], float sa, float sb,
+                                            f32x16 (&acc)[NBI][NBJ]) {
+  u32x4 pa[NBI][3];
+#pragma unroll
+  for (int a = 0; a < NBI; ++a) {
+    split8<PL>(make_float4(va[a][0], va[a][1], va[a][2], va[a][3]), make_float4(va[a][4], va[a][5], va[a][6], va[a][7]), sa, pa[a]);
+    if (PL == 4) dw_a_planes(pa[a]);
+  }
+#pragma unroll
+  for (int b = 0; b < NBJ; ++b) {
+    u32x4 pb[3];
+    split8<PL>(make_float4(vb[b][0], vb[b][1], vb[b][2], vb[b][3]), make_float4(vb[b][4], vb[b][5], vb[b][6], vb[b][7]), sb, pb);
+#pragma unroll
+    for (int a = 0; a < NBI; ++a) mfma_terms_dw<PL>(pa[a], pb, acc[a][b]);
+  }
+}
 
 // split-precision weight gradient: both operands are gathered activations, split on the fly into PL bf16 planes.
 // Same decomposition as k_conv_bwd_weight (wave-private LDS tiles, per-wave slabs, no workgroup barrier), plus a
@@ -1650,64 +1777,24 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_split(const float* __re
   float (*Bs)[32][TCB] = reinterpret_cast<float (*)[32][TCB]>(lds_all + 4 * 32 * TCA);
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int i = l & 31, h = l >> 5;
-  // PRE: wave-private row images (same bytes as the fp32 tiles); lane 16 g + 4 q + p of a transposed read supplies
-  // row q (+ 8 in the upper half of the wave), 16-channel half g & 1, 8-byte piece p
+  // PRE: wave-private row images (same bytes as the fp32 tiles)
   unsigned char* const imgA = reinterpret_cast<unsigned char*>(&As[w][0][0]);
   unsigned char* const imgB = reinterpret_cast<unsigned char*>(&Bs[w][0][0]);
   unsigned trA[NBI][2], trB[NBJ][2];
   if (PRE) {
-    const unsigned ldsA = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)imgA);
-    const unsigned ldsB = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)imgB);
-    const int q = (l & 15) >> 2, pp = l & 3, c16 = (l >> 4) & 1, trow = 8 * (l >> 5) + q;
 #pragma unroll
-    for (int a = 0; a < NBI; ++a)
+    for (int a = 0; a < NBI; ++a) tr_read_bases<TCA>(lds_address(imgA), a, trA[a]);
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-        trA[a][pl] = ldsA + trow * (TCA * 4) + (((a * 4 + pl * 2 + c16) ^ tr_swz<TCA>(q)) * 32) + pp * 8;
-#pragma unroll
-    for (int b = 0; b < NBJ; ++b)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl)
-        trB[b][pl] = ldsB + trow * (TCB * 4) + (((b * 4 + pl * 2 + c16) ^ tr_swz<TCB>(q)) * 32) + pp * 8;
+    for (int b = 0; b < NBJ; ++b) tr_read_bases<TCB>(lds_address(imgB), b, trB[b]);
   }
-  // XCD-aware launch order (1-D grid): workgroups are dealt round-robin to the 8 XCDs, so the n_tiles channel tiles
-  // that re-read the SAME pair range are given consecutive slots of ONE XCD and share its L2
-  int bx, by;
-  long long rg_lo = 0, rg_hi = 0;
-  int rg_k = 0;
-  if (RG) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    rg_k = slot % K;
-    const int j = (slot / K) * 8 + xcd;
-    if (j >= n_ranges) return;
-    rg_lo = bounds[rg_k * (n_ranges + 1) + j];
-    rg_hi = bounds[rg_k * (n_ranges + 1) + j + 1];
-    bx = j * K;              // slab of the cell = bx + rg_k
-    by = 0;
-  } else if (n_tiles > 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    by = slot % n_tiles;
-    bx = (slot / n_tiles) * 8 + xcd;
-    if (bx >= n_wg_x) return;
-  } else {
-    bx = blockIdx.x;
-    by = blockIdx.y;
-  }
-  const int tiles_b = cb / TCB;
-  const int ca0 = (by / tiles_b) * TCA, cb0 = (by % tiles_b) * TCB;
-  const long long c0 = RG ? 0 : (long long)bx * per;
-  const long long c1 = RG ? (rg_hi - rg_lo + GCL_PAIR_CHUNK - 1) / GCL_PAIR_CHUNK
-                          : ((c0 + per < n_chunks) ? c0 + per : n_chunks);
-  if (!RG && c0 >= c1) return;   // uniform over the workgroup (an empty RG cell still writes its zero slab)
+  DwTile<TCA, TCB, RG> tile;
+  tile.map(cb, n_chunks, per, n_wg_x, n_tiles, K, bounds, n_ranges);
+  if (tile.idle) return;
+  const int ca0 = tile.ca0, cb0 = tile.cb0;
+  const long long c0 = tile.c0, c1 = tile.c1;
 
   f32x16 acc[NBI][NBJ];
-#pragma unroll
-  for (int a = 0; a < NBI; ++a)
-#pragma unroll
-    for (int b = 0; b < NBJ; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
+  zero_acc(acc);
   auto flush = [&](int k) {
     if (PL == 4) {
 #pragma unroll
@@ -1717,75 +1804,43 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_split(const float* __re
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[a][b][r] *= out_scale;
     }
-    bwd_weight_flush<TCA, TCB>(acc, lds_all, slabs + (long long)(bx + k) * ((long long)ca * cb), ca0, cb0, cb);
-  };
-  auto load_pairs = [&](long long c, int& ia, int& ib) {
-    ia = -1;
-    ib = -1;
-    if (c < c1 && l < 32) {
-      long long p0 = (RG ? rg_lo : 0) + c * GCL_PAIR_CHUNK + w * 32 + l;
-      if (!RG || p0 < rg_hi) {
-        ia = pair_a[p0];
-        ib = pair_b[p0];
-      }
-    }
+    bwd_weight_flush<TCA, TCB>(acc, lds_all, slabs + (long long)(tile.bx + k) * ((long long)ca * cb), ca0, cb0, cb);
   };
 
+  // a lane's share of a 32-pair tile: 16-byte piece l % P of the rows l / P + R ps, and where each goes in the wave's tile
+  // (PRE: unchanged into the row image, 32-byte blocks swizzled with the row)
+  auto row_a = [&](int ps) { return l / PA + RA * ps; };
+  auto row_b = [&](int ps) { return l / PB + RB * ps; };
+  unsigned dst_a[NPA], dst_b[NPB];
+#pragma unroll
+  for (int ps = 0; ps < NPA; ++ps)
+    dst_a[ps] = PRE ? tr_piece_offset<TCA>(row_a(ps), l % PA) : (unsigned)(row_a(ps) * TCA + (l % PA) * 4) * 4u;
+#pragma unroll
+  for (int ps = 0; ps < NPB; ++ps)
+    dst_b[ps] = PRE ? tr_piece_offset<TCB>(row_b(ps), l % PB) : (unsigned)(row_b(ps) * TCB + (l % PB) * 4) * 4u;
+  const DwOperand op_a(A, a_bytes, ca, (unsigned)(ca0 + (l % PA) * 4) * 4u), op_b(B, b_bytes, cb, (unsigned)(cb0 + (l % PB) * 4) * 4u);
   float4 ga[NPA], gb[NPB];
-  // rows through buffer resources: a padding pair (row -1) wraps beyond the tensor and reads zeros (no branch, no
-  // 64-bit address arithmetic per row)
-  const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, (int)a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc((void*)B, 0, (int)b_bytes, 0x00020000);
-  const unsigned a_row = (unsigned)ca * 4u, b_row = (unsigned)cb * 4u;
-  const unsigned a_col = (unsigned)(ca0 + (l % PA) * 4) * 4u, b_col = (unsigned)(cb0 + (l % PB) * 4) * 4u;
-#define GCL_GATHER(IA, IB)                                                                              \
-  {                                                                                                     \
-    _Pragma("unroll") for (int ps = 0; ps < NPA; ++ps) {                                                \
-      unsigned ridx = (unsigned)__shfl(IA, l / PA + RA * ps);                                           \
-      ga[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)(ridx * a_row + a_col), 0, 0)); \
-    }                                                                                                   \
-    _Pragma("unroll") for (int ps = 0; ps < NPB; ++ps) {                                                \
-      unsigned ridx = (unsigned)__shfl(IB, l / PB + RB * ps);                                           \
-      gb[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(brsrc, (int)(ridx * b_row + b_col), 0, 0)); \
-    }                                                                                                   \
-  }
 
-  int kcur = RG ? rg_k : 0;
-  if (!RG)
-    while (seg.off[kcur + 1] <= c0 * GCL_PAIR_CHUNK) ++kcur;
+  SegCursor cur;
+  if (RG) cur.k = tile.rg_k; else cur.init(seg, c0);
   int ia1, ib1, ia2, ib2;
-  load_pairs(c0, ia1, ib1);
-  load_pairs(c0 + 1, ia2, ib2);
-  GCL_GATHER(ia1, ib1);
+  tile.load_pairs(pair_a, pair_b, c0 * DW_SUB + w, l, ia1, ib1);
+  tile.load_pairs(pair_a, pair_b, (c0 + 1) * DW_SUB + w, l, ia2, ib2);
+  gather_pairs(op_a, ia1, row_a, ga);
+  gather_pairs(op_b, ib1, row_b, gb);
   for (long long c = c0; c < c1; ++c) {
-    const long long pbase = c * GCL_PAIR_CHUNK;
-    if (!RG && pbase >= seg.off[kcur + 1]) {
-      flush(kcur);
-      while (seg.off[kcur + 1] <= pbase) ++kcur;
-    }
+    if (!RG) cur.step(seg, c * GCL_PAIR_CHUNK, flush);
     WAVE_FENCE();
-    if (PRE) {   // 16-byte pieces go to LDS unchanged, 32-byte blocks swizzled with the row
-#pragma unroll
-      for (int ps = 0; ps < NPA; ++ps) {
-        const int row = l / PA + RA * ps, pc = l % PA;
-        *reinterpret_cast<float4*>(imgA + row * (TCA * 4) + (((pc >> 1) ^ tr_swz<TCA>(row)) * 32) + (pc & 1) * 16) = ga[ps];
-      }
-#pragma unroll
-      for (int ps = 0; ps < NPB; ++ps) {
-        const int row = l / PB + RB * ps, pc = l % PB;
-        *reinterpret_cast<float4*>(imgB + row * (TCB * 4) + (((pc >> 1) ^ tr_swz<TCB>(row)) * 32) + (pc & 1) * 16) = gb[ps];
-      }
-    } else {
-#pragma unroll
-      for (int ps = 0; ps < NPA; ++ps) *reinterpret_cast<float4*>(&As[w][l / PA + RA * ps][(l % PA) * 4]) = ga[ps];
-#pragma unroll
-      for (int ps = 0; ps < NPB; ++ps) *reinterpret_cast<float4*>(&Bs[w][l / PB + RB * ps][(l % PB) * 4]) = gb[ps];
-    }
+    store_row_image(imgA, dst_a, ga);
+    store_row_image(imgB, dst_b, gb);
     // rows of chunk c+1 (indices arrived a chunk ago), indices of chunk c+2
     ia1 = ia2;
     ib1 = ib2;
-    if (c + 1 < c1) GCL_GATHER(ia1, ib1);
-    load_pairs(c + 2, ia2, ib2);
+    if (c + 1 < c1) {
+      gather_pairs(op_a, ia1, row_a, ga);
+      gather_pairs(op_b, ib1, row_b, gb);
+    }
+    tile.load_pairs(pair_a, pair_b, (c + 2) * DW_SUB + w, l, ia2, ib2);
     WAVE_FENCE();
     if (PRE) {
       tr_mma_half<TCA, TCB, 0>(trA, trB, acc);
@@ -1794,29 +1849,18 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_split(const float* __re
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      u32x4 pa[NBI][3];
+      float va[NBI][8], vb[NBJ][8];
 #pragma unroll
-      for (int a = 0; a < NBI; ++a) {
-        float v[8];
+      for (int jj = 0; jj < 8; ++jj) {
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) v[jj] = As[w][16 * half + 8 * h + jj][a * 32 + i];
-        split8<PL>(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sa, pa[a]);
-        if (PL == 4) dw_a_planes(pa[a]);
+        for (int a = 0; a < NBI; ++a) va[a][jj] = As[w][16 * half + 8 * h + jj][a * 32 + i];
+#pragma unroll
+        for (int b = 0; b < NBJ; ++b) vb[b][jj] = Bs[w][16 * half + 8 * h + jj][b * 32 + i];
       }
-#pragma unroll
-      for (int b = 0; b < NBJ; ++b) {
-        float v[8];
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) v[jj] = Bs[w][16 * half + 8 * h + jj][b * 32 + i];
-        u32x4 pb[3];
-        split8<PL>(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sb, pb);
-#pragma unroll
-        for (int a = 0; a < NBI; ++a) mfma_terms_dw<PL>(pa[a], pb, acc[a][b]);
-      }
+      mma_rows_dw<PL>(va, vb, sa, sb, acc);
     }
   }
-  flush(kcur);
-#undef GCL_GATHER
+  flush(cur.k);
 }
 
 // ---- weight gradient on plane images, 128 x 128 output block per workgroup (round 4) ---------------------------------
@@ -1838,160 +1882,123 @@ __global__ void __launch_bounds__(256, 2) k_conv_bwd_weight_wg128(const float* _
                                                                const int* __restrict__ b_amax, int n_wg_x, int n_tiles,
                                                                unsigned a_bytes, unsigned b_bytes) {
   constexpr int TC = 64;                   // a wave's channel half of each operand
-  constexpr int SUB = GCL_PAIR_CHUNK / 32; // sub-chunks of 32 pairs per 128-pair chunk
   const float out_scale = 1.f / (amax_scale(a_amax) * amax_scale(b_amax));
   // [buffer][operand A | B][channel half][32 rows][256 B]: each [32][256 B] piece is the row image of the 64-channel kernels
   __shared__ __attribute__((aligned(16))) unsigned char tiles[2][2][2][32 * TC * 4];
   const int t = threadIdx.x, l = t & 63, w = t >> 6, wi = w >> 1, wj = w & 1;
   constexpr int BUF_BYTES = 2 * 2 * 32 * TC * 4;      // one buffer: both operands, both halves (32 KB)
   unsigned trA[2][2], trB[2][2];           // buffer 0: [32-channel slice of the half][plane]; buffer 1 = + BUF_BYTES (immediate)
-  {
-    const int q = (l & 15) >> 2, pp = l & 3, c16 = (l >> 4) & 1, trow = 8 * (l >> 5) + q;
-    const unsigned la = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)&tiles[0][0][wi][0]);
-    const unsigned lb = (unsigned)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)&tiles[0][1][wj][0]);
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) {
-        const unsigned off = trow * (TC * 4) + (((a * 4 + pl * 2 + c16) ^ tr_swz<TC>(q)) * 32) + pp * 8;
-        trA[a][pl] = la + off;
-        trB[a][pl] = lb + off;
-      }
+  for (int a = 0; a < 2; ++a) {
+    tr_read_bases<TC>(lds_address(&tiles[0][0][wi][0]), a, trA[a]);
+    tr_read_bases<TC>(lds_address(&tiles[0][1][wj][0]), a, trB[a]);
   }
-  int bx, by;
-  if (n_tiles > 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    by = slot % n_tiles;
-    bx = (slot / n_tiles) * 8 + xcd;
-    if (bx >= n_wg_x) return;
-  } else {
-    bx = blockIdx.x;
-    by = blockIdx.y;
-  }
-  const int tiles_b = cb / 128;
-  const int ca0 = (by / tiles_b) * 128, cb0 = (by % tiles_b) * 128;
-  const long long c0 = (long long)bx * per;
-  const long long c1 = (c0 + per < n_chunks) ? c0 + per : n_chunks;
-  if (c0 >= c1) return;
-  const long long s0 = c0 * SUB, s1 = c1 * SUB;      // sub-chunk range of this workgroup
+  DwTile<128, 128> tile;
+  tile.map(cb, n_chunks, per, n_wg_x, n_tiles);
+  if (tile.idle) return;
+  const int ca0 = tile.ca0, cb0 = tile.cb0;
+  const long long s0 = tile.c0 * DW_SUB, s1 = tile.c1 * DW_SUB;      // sub-chunk range of this workgroup
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  zero_acc(acc);
 
-  const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, (int)a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc((void*)B, 0, (int)b_bytes, 0x00020000);
-  const unsigned a_row = (unsigned)ca * 4u, b_row = (unsigned)cb * 4u;
   // a lane's share of a sub-chunk: rows 8 w + 2 ps + (l >> 5), ps = 0 .. 3, 16-byte piece l & 31 of the 512-byte row
-  const int pc = l & 31, rsub = l >> 5;
-  const unsigned a_col = (unsigned)ca0 * 4u + (unsigned)pc * 16u, b_col = (unsigned)cb0 * 4u + (unsigned)pc * 16u;
-  // where piece pc of row r goes: half pc / 16, then the 64-channel row image (32-byte blocks XOR-swizzled with the row)
+  const int pc = l & 31;
+  auto row_of = [&](int ps) { return 8 * w + 2 * ps + (l >> 5); };
+  const DwOperand op_a(A, a_bytes, ca, (unsigned)ca0 * 4u + (unsigned)pc * 16u);
+  const DwOperand op_b(B, b_bytes, cb, (unsigned)cb0 * 4u + (unsigned)pc * 16u);
+  // where piece pc of row r goes: half pc / 16, then the 64-channel row image
   unsigned dst[4];
 #pragma unroll
-  for (int ps = 0; ps < 4; ++ps) {
-    const int row = 8 * w + 2 * ps + rsub, p16 = pc & 15;
-    dst[ps] = (unsigned)((pc >> 4) * (32 * TC * 4) + row * (TC * 4) + (((p16 >> 1) ^ tr_swz<TC>(row)) * 32) + (p16 & 1) * 16);
-  }
-  auto load_pairs = [&](long long sc, int& ia, int& ib) {      // lanes 0 .. 31: the pair of row `lane` of sub-chunk sc
-    ia = -1;
-    ib = -1;
-    if (sc < s1 && l < 32) {
-      const long long p0 = sc * 32 + l;
-      ia = pair_a[p0];
-      ib = pair_b[p0];
-    }
-  };
-#define GCLW_GATHER(IA, IB, GA, GB)                                                                            \
-  {                                                                                                            \
-    _Pragma("unroll") for (int ps = 0; ps < 4; ++ps) {                                                         \
-      const int row_ = 8 * w + 2 * ps + rsub;                                                                  \
-      const unsigned ra_ = (unsigned)__shfl(IA, row_), rb_ = (unsigned)__shfl(IB, row_);                       \
-      GA[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)(ra_ * a_row + a_col), 0, 0)); \
-      GB[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(brsrc, (int)(rb_ * b_row + b_col), 0, 0)); \
-    }                                                                                                          \
-  }
-#define GCLW_STORE(BUF, GA, GB)                                                                                \
-  {                                                                                                            \
-    _Pragma("unroll") for (int ps = 0; ps < 4; ++ps) {                                                         \
-      *reinterpret_cast<float4*>(&tiles[BUF][0][0][0] + dst[ps]) = GA[ps];                                     \
-      *reinterpret_cast<float4*>(&tiles[BUF][1][0][0] + dst[ps]) = GB[ps];                                     \
-    }                                                                                                          \
-  }
+  for (int ps = 0; ps < 4; ++ps) dst[ps] = (unsigned)((pc >> 4) * (32 * TC * 4)) + tr_piece_offset<TC>(row_of(ps), pc & 15);
+  unsigned char* const buf_a[2] = {&tiles[0][0][0][0], &tiles[1][0][0][0]};
+  unsigned char* const buf_b[2] = {&tiles[0][1][0][0], &tiles[1][1][0][0]};
   auto flush = [&](int k) {      // this wave's 64 x 64 block of the slab of (workgroup, offset k)
     int cbv = cb;
     asm volatile("" : "+s"(cbv));      // opaque here: keeps the 64 element offsets out of the loop's live registers (they spilled)
-    float* base = slabs + (long long)(bx + k) * ((long long)ca * cb) +
-                  (long long)(ca0 + wi * 64 + 4 * (l >> 5)) * cb + cb0 + wj * 64 + (l & 31);
+    float* base = slabs + (long long)(tile.bx + k) * ((long long)ca * cb) +
+                  (long long)(ca0 + wi * 64 + acc_cell_row(0, l)) * cb + cb0 + wj * 64 + (l & 31);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          base[(unsigned)((a * 32 + (r & 3) + 8 * (r >> 2)) * cbv + b * 32)] = acc[a][b][r] * out_scale;
+          base[(unsigned)((a * 32 + acc_cell_row(r, 0)) * cbv + b * 32)] = acc[a][b][r] * out_scale;
           acc[a][b][r] = 0.f;
         }
   };
+  // after the last sub-chunk s of a 128-pair chunk: does the next chunk start a new offset?
+  SegCursor cur;
+  cur.init(seg, tile.c0);
+  auto segment = [&](long long s) {
+    if ((s + 1) % DW_SUB == 0 && s + 1 < s1) cur.step(seg, (s + 1) * 32, flush);
+  };
 
-  int kcur = 0;
-  while (seg.off[kcur + 1] <= c0 * GCL_PAIR_CHUNK) ++kcur;
   float4 ga0[4], gb0[4], ga1[4], gb1[4];
   int ia, ib, ian, ibn;
   // sub-chunks s0 and s0 + 1 -> registers, s0 -> buffer 0, then s0 + 2 -> the freed registers; indices two ahead
-  load_pairs(s0, ia, ib);
-  load_pairs(s0 + 1, ian, ibn);
-  GCLW_GATHER(ia, ib, ga0, gb0);
-  GCLW_GATHER(ian, ibn, ga1, gb1);
-  load_pairs(s0 + 2, ia, ib);
-  load_pairs(s0 + 3, ian, ibn);
-  GCLW_STORE(0, ga0, gb0);
-  GCLW_GATHER(ia, ib, ga0, gb0);          // rows of s0 + 2 (out of range: row -1 reads zeros, never used)
-  load_pairs(s0 + 4, ia, ib);
+  tile.load_pairs(pair_a, pair_b, s0, l, ia, ib);
+  tile.load_pairs(pair_a, pair_b, s0 + 1, l, ian, ibn);
+  gather_pairs(op_a, ia, row_of, ga0);
+  gather_pairs(op_b, ib, row_of, gb0);
+  gather_pairs(op_a, ian, row_of, ga1);
+  gather_pairs(op_b, ibn, row_of, gb1);
+  tile.load_pairs(pair_a, pair_b, s0 + 2, l, ia, ib);
+  tile.load_pairs(pair_a, pair_b, s0 + 3, l, ian, ibn);
+  store_row_image(buf_a[0], dst, ga0);
+  store_row_image(buf_b[0], dst, gb0);
+  gather_pairs(op_a, ia, row_of, ga0);          // rows of s0 + 2 (out of range: row -1 reads zeros, never used)
+  gather_pairs(op_b, ib, row_of, gb0);
+  tile.load_pairs(pair_a, pair_b, s0 + 4, l, ia, ib);
   __syncthreads();
   // steady state, two sub-chunks per trip (static register sets): at the top of the trip for sub-chunk s, buffer s & 1 holds
   // s, set 1 holds s + 1, set 0 holds s + 2 (in flight), `ian/ibn` = pairs of s + 3, `ia/ib` = pairs of s + 4
-#define GCLW_COMPUTE(BUF)                                                                                      \
-  {                                                                                                            \
-    tr_mma_half<TC, TC, 0, (BUF)*BUF_BYTES>(trA, trB, acc);                                                    \
-    tr_mma_half<TC, TC, 1, (BUF)*BUF_BYTES>(trA, trB, acc);                                                    \
-  }
-#define GCLW_SEGMENT(S)                                                                                        \
-  if (((S) + 1) % SUB == 0) {        /* last sub-chunk of a 128-pair chunk: does the next chunk start a new offset? */ \
-    const long long nb_ = ((S) + 1) / SUB * GCL_PAIR_CHUNK;                                                    \
-    if ((S) + 1 < s1 && nb_ >= seg.off[kcur + 1]) {                                                            \
-      flush(kcur);                                                                                             \
-      while (seg.off[kcur + 1] <= nb_) ++kcur;                                                                 \
-    }                                                                                                          \
-  }
   for (long long s = s0; s < s1; s += 2) {
     // ---- sub-chunk s (buffer 0 of this trip's pair = (s - s0) & 1 == 0 -> buffer index alternates with s - s0)
-    GCLW_COMPUTE(0);
-    GCLW_SEGMENT(s);
-    GCLW_STORE(1, ga1, gb1);              // s + 1 -> buffer 1 (last read one sub-chunk ago, before the previous barrier)
-    GCLW_GATHER(ian, ibn, ga1, gb1);      // s + 3
-    load_pairs(s + 5, ian, ibn);
+    tr_mma_half<TC, TC, 0>(trA, trB, acc);
+    tr_mma_half<TC, TC, 1>(trA, trB, acc);
+    segment(s);
+    store_row_image(buf_a[1], dst, ga1);          // s + 1 -> buffer 1 (last read one sub-chunk ago, before the previous barrier)
+    store_row_image(buf_b[1], dst, gb1);
+    gather_pairs(op_a, ian, row_of, ga1);         // s + 3
+    gather_pairs(op_b, ibn, row_of, gb1);
+    tile.load_pairs(pair_a, pair_b, s + 5, l, ian, ibn);
     __syncthreads();
     if (s + 1 >= s1) break;
     // ---- sub-chunk s + 1
-    GCLW_COMPUTE(1);
-    GCLW_SEGMENT(s + 1);
-    GCLW_STORE(0, ga0, gb0);              // s + 2 -> buffer 0
-    GCLW_GATHER(ia, ib, ga0, gb0);        // s + 4
-    load_pairs(s + 6, ia, ib);
+    tr_mma_half<TC, TC, 0, BUF_BYTES>(trA, trB, acc);
+    tr_mma_half<TC, TC, 1, BUF_BYTES>(trA, trB, acc);
+    segment(s + 1);
+    store_row_image(buf_a[0], dst, ga0);          // s + 2 -> buffer 0
+    store_row_image(buf_b[0], dst, gb0);
+    gather_pairs(op_a, ia, row_of, ga0);          // s + 4
+    gather_pairs(op_b, ib, row_of, gb0);
+    tile.load_pairs(pair_a, pair_b, s + 6, l, ia, ib);
     __syncthreads();
   }
-  flush(kcur);
-#undef GCLW_SEGMENT
-#undef GCLW_COMPUTE
-#undef GCLW_STORE
-#undef GCLW_GATHER
+  flush(cur.k);
 }
 
+// Element e of slabs first, first + stride, ... (`count` of them) summed in a fixed order: four chains with four slab loads
+// in flight, the tail on the first chain, then one tree.
 // T: the slab type -- float for the MFMA kernels, double for the generic kernel (whose result may be ONE cancelling sum)
+template <typename T>
+__device__ __forceinline__ T sum_slabs4(const T* __restrict__ slabs, long long first, long long stride, long long count,
+                                        long long mat, long long e) {
+  T s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  long long j = 0;
+  for (; j + 3 < count; j += 4) {
+    s0 += slabs[(first + j * stride) * mat + e];
+    s1 += slabs[(first + (j + 1) * stride) * mat + e];
+    s2 += slabs[(first + (j + 2) * stride) * mat + e];
+    s3 += slabs[(first + (j + 3) * stride) * mat + e];
+  }
+  for (; j < count; ++j) s0 += slabs[(first + j * stride) * mat + e];
+  return (s0 + s1) + (s2 + s3);
+}
+
+// dw[k] = sum of the slabs bx + k of the workgroups bx whose chunks hold pairs of offset k, in order
 template <typename T>
 __global__ void __launch_bounds__(256) k_bwd_weight_reduce(const T* __restrict__ slabs, SegOffW seg, int per,
                                                            long long mat, float* dw) {
@@ -2000,38 +2007,19 @@ __global__ void __launch_bounds__(256) k_bwd_weight_reduce(const T* __restrict__
   if (e >= mat) return;
   T s = 0;
   if (seg.off[k + 1] > seg.off[k]) {
-    long long first = seg.off[k] / GCL_PAIR_CHUNK, last = seg.off[k + 1] / GCL_PAIR_CHUNK - 1;
-    long long lo = first / per, hi = last / per;
-    T s0 = 0, s1 = 0, s2 = 0, s3 = 0;     // four slab loads in flight; fixed summation order
-    long long bx = lo;
-    for (; bx + 3 <= hi; bx += 4) {
-      s0 += slabs[(bx + k) * mat + e];
-      s1 += slabs[(bx + 1 + k) * mat + e];
-      s2 += slabs[(bx + 2 + k) * mat + e];
-      s3 += slabs[(bx + 3 + k) * mat + e];
-    }
-    for (; bx <= hi; ++bx) s0 += slabs[(bx + k) * mat + e];
-    s = (s0 + s1) + (s2 + s3);
+    const long long lo = seg.off[k] / GCL_PAIR_CHUNK / per, hi = (seg.off[k + 1] / GCL_PAIR_CHUNK - 1) / per;
+    s = sum_slabs4(slabs, lo + k, 1, hi - lo + 1, mat, e);
   }
   dw[(long long)k * mat + e] = (float)s;
 }
 
-// RG mode: dw[k] = sum over the row ranges j of slab (j K + k), in order (four loads in flight, fixed tree)
+// RG mode: dw[k] = sum over the row ranges j of slab (j K + k), in order
 __global__ void __launch_bounds__(256) k_bwd_weight_reduce_rg(const float* __restrict__ slabs, int n_ranges, int K,
                                                               long long mat, float* dw) {
   const int k = blockIdx.y;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= mat) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int j = 0;
-  for (; j + 3 < n_ranges; j += 4) {
-    s0 += slabs[((long long)j * K + k) * mat + e];
-    s1 += slabs[((long long)(j + 1) * K + k) * mat + e];
-    s2 += slabs[((long long)(j + 2) * K + k) * mat + e];
-    s3 += slabs[((long long)(j + 3) * K + k) * mat + e];
-  }
-  for (; j < n_ranges; ++j) s0 += slabs[((long long)j * K + k) * mat + e];
-  dw[(long long)k * mat + e] = (s0 + s1) + (s2 + s3);
+  dw[(long long)k * mat + e] = sum_slabs4(slabs, k, K, n_ranges, mat, e);
 }
 
 // ---- weight gradient of a kernel_size-1 convolution (identity map): dW = A^T B as a row STREAM (round 5) -----------------
@@ -2060,12 +2048,7 @@ __global__ void __launch_bounds__(256, 2) k_bwd_weight_rows(const float* __restr
   const long long s0 = (long long)blockIdx.x * steps_per_wg;
   const long long s1 = (s0 + steps_per_wg < n_steps) ? s0 + steps_per_wg : n_steps;
   f32x16 acc[NBI][NBJ];
-#pragma unroll
-  for (int a = 0; a < NBI; ++a)
-#pragma unroll
-    for (int b = 0; b < NBJ; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  zero_acc(acc);
   float ra[2][NBI][8], rb[2][NBJ][8];
   // One base offset per operand and step (byte offsets fit 32 bits: operands < 4 GiB, checked by the entry), the (row j,
   // slice) part is an instruction immediate.  A step beyond the wave's share is redirected past the tensor: the buffer
@@ -2085,31 +2068,15 @@ __global__ void __launch_bounds__(256, 2) k_bwd_weight_rows(const float* __restr
         xb[b][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brsrc, vb + (j * CB + b * 32) * 4, 0, 0));
     }
   };
-  auto mma = [&](float (&xa)[NBI][8], float (&xb)[NBJ][8]) {
-    u32x4 pa[NBI][3];
-#pragma unroll
-    for (int a = 0; a < NBI; ++a)
-    {
-      split8<4>(make_float4(xa[a][0], xa[a][1], xa[a][2], xa[a][3]), make_float4(xa[a][4], xa[a][5], xa[a][6], xa[a][7]), sa, pa[a]);
-      dw_a_planes(pa[a]);
-    }
-#pragma unroll
-    for (int b = 0; b < NBJ; ++b) {
-      u32x4 pb[3];
-      split8<4>(make_float4(xb[b][0], xb[b][1], xb[b][2], xb[b][3]), make_float4(xb[b][4], xb[b][5], xb[b][6], xb[b][7]), sb, pb);
-#pragma unroll
-      for (int a = 0; a < NBI; ++a) mfma_terms_dw<4>(pa[a], pb, acc[a][b]);
-    }
-  };
   // the four waves interleave over the workgroup's steps (the workgroup streams one contiguous row range); two steps per
   // iteration so that the register buffers alternate without copies; loads run one step ahead of their products
   long long st = s0 + wv;
   load(st, ra[0], rb[0]);
   for (; st < s1; st += 8) {
     load(st + 4, ra[1], rb[1]);
-    mma(ra[0], rb[0]);
+    mma_rows_dw<4>(ra[0], rb[0], sa, sb, acc);
     load(st + 8, ra[0], rb[0]);
-    mma(ra[1], rb[1]);
+    mma_rows_dw<4>(ra[1], rb[1], sa, sb, acc);
   }
   // the four waves' sums are added in wave order through ONE slab image in LDS (lane-owned cells: ((w0 + w1) + w2) + w3)
 #pragma unroll 1
@@ -2131,7 +2098,7 @@ __global__ void __launch_bounds__(256, 2) k_bwd_weight_rows(const float* __restr
   for (int e = threadIdx.x; e < CA * CB; e += 256) {
     const int ll = e & 63, r = (e >> 6) & 15, blk = e >> 10;
     const int a = blk / NBJ, b = blk % NBJ;
-    const int row = a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (ll >> 5);
+    const int row = a * 32 + acc_cell_row(r, ll);
     slab[row * CB + b * 32 + (ll & 31)] = lds_sum[e] * out_scale;
   }
 }
@@ -2454,10 +2421,7 @@ __global__ void __launch_bounds__(256, TILE == 64 ? 4 : 2)
   if (r_end > n_out) r_end = n_out;
   for (int ci = 0; ci < cin; ++ci) {
     f32x16 acc[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[kb][r] = 0.f;
+    zero_acc(acc);
     for (long long r0 = r_begin; r0 < r_end; r0 += TILE) {
       __syncthreads();
       {
@@ -2526,15 +2490,15 @@ __global__ void __launch_bounds__(256, TILE == 64 ? 4 : 2)
       }
     }
     if (w == 3) {
-      int h_o = h;      // opaque: keeps the 64 store offsets out of the kernel's prologue (they were hoisted and spilled)
-      asm volatile("" : "+v"(h_o));
+      int l_o = l;      // opaque: keeps the 64 store offsets out of the kernel's prologue (they were hoisted and spilled)
+      asm volatile("" : "+v"(l_o));
       float* slab = slabs + ((long long)blockIdx.x * K * cin + ci) * cout + cb0 + i;
       const int kstep = cin * cout;
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int k = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h_o;
+          const int k = kb * 32 + acc_cell_row(r, l_o);
           if (k < K) slab[k * kstep] = acc[kb][r];
         }
     }
@@ -2671,25 +2635,21 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_generic(const float* __
                                                                  double* slabs) {
   __shared__ float As[GCL_PAIR_CHUNK][17], Bs[GCL_PAIR_CHUNK][17];
   const int t = threadIdx.x, i = t >> 4, j = t & 15;
-  const int tiles_b = (cb + 15) / 16;
-  const int ca0 = (blockIdx.y / tiles_b) * 16, cb0 = (blockIdx.y % tiles_b) * 16;
-  const long long c0 = (long long)blockIdx.x * per;
-  const long long c1 = (c0 + per < n_chunks) ? c0 + per : n_chunks;
-  if (c0 >= c1) return;
+  DwTile<16, 16> tile;
+  tile.map(cb, n_chunks, per);
+  if (tile.idle) return;
+  const int ca0 = tile.ca0, cb0 = tile.cb0;
   const long long mat = (long long)ca * cb;
   double acc = 0.;
-  int kcur = 0;
-  while (seg.off[kcur + 1] <= c0 * GCL_PAIR_CHUNK) ++kcur;
   auto flush = [&](int k) {
-    if (ca0 + i < ca && cb0 + j < cb) slabs[(long long)(blockIdx.x + k) * mat + (long long)(ca0 + i) * cb + cb0 + j] = acc;
+    if (ca0 + i < ca && cb0 + j < cb) slabs[(long long)(tile.bx + k) * mat + (long long)(ca0 + i) * cb + cb0 + j] = acc;
     acc = 0.;
   };
-  for (long long c = c0; c < c1; ++c) {
+  SegCursor cur;
+  cur.init(seg, tile.c0);
+  for (long long c = tile.c0; c < tile.c1; ++c) {
     const long long pbase = c * GCL_PAIR_CHUNK;
-    if (pbase >= seg.off[kcur + 1]) {
-      flush(kcur);
-      while (seg.off[kcur + 1] <= pbase) ++kcur;
-    }
+    cur.step(seg, pbase, flush);
     __syncthreads();
     for (int e = t; e < GCL_PAIR_CHUNK * 16; e += 256) {
       const int p = e >> 4, ch = e & 15;
@@ -2701,7 +2661,7 @@ __global__ void __launch_bounds__(256) k_conv_bwd_weight_generic(const float* __
 #pragma unroll 8
     for (int p = 0; p < GCL_PAIR_CHUNK; ++p) acc = fma((double)As[p][i], (double)Bs[p][j], acc);
   }
-  flush(kcur);
+  flush(cur.k);
 }
 
 }  // namespace gcl
@@ -3052,69 +3012,56 @@ int gcl_conv_bwd_weight_rg(const float* a, int64_t n_a, const float* b, int64_t 
   const long long n_sorted = sorted_side == 1 ? n_a : n_b;
   const DwLaunch s = dw_launch_shape(K, ca, cb, prec, planes_arg, sorted_side, n_sorted, nc);
   const int W = s.W, per = s.per;
+  const int* bounds = nullptr;
   if (s.path == GCL_DW_PATH_RG) {
-    const int nr = s.nr;
-    const int* bounds = (const int*)rg_bounds;      // gcl_conv_bwd_weight_bounds of the sorted list, made once per map ...
+    bounds = (const int*)rg_bounds;                 // gcl_conv_bwd_weight_bounds of the sorted list, made once per map ...
     if (!bounds) {                                  // ... or here, per launch
-      int* own = (int*)(scratch + (long long)nr * K * mat);
-      hipLaunchKernelGGL(k_pair_bounds, dim3((unsigned)cdiv((long long)K * (nr + 1), 256)), dim3(256), 0, st,
-                         sorted_side == 1 ? pair_a : pair_b, seg, K, s.rr, nr, own);
+      int* own = (int*)(scratch + (long long)s.nr * K * mat);
+      hipLaunchKernelGGL(k_pair_bounds, dim3((unsigned)cdiv((long long)K * (s.nr + 1), 256)), dim3(256), 0, st,
+                         sorted_side == 1 ? pair_a : pair_b, seg, K, s.rr, s.nr, own);
       bounds = own;
     }
-    dim3 rgrid((unsigned)(cdiv(nr, 8) * 8 * K));
-#define LAUNCH_RG(TA, TB, PLV)                                                                                      \
-  hipLaunchKernelGGL((k_conv_bwd_weight_split<TA, TB, PLV, false, true>), rgrid, dim3(256), 0, st, a, b, pair_a, pair_b, \
-                     seg, K, ca, cb, nc, per, scratch, a_amax, b_amax, 0, 0, a_bytes, b_bytes, (const int*)bounds, nr)
-#define LAUNCH_RG_P(TA, TB)                                            \
-  {                                                                    \
-    if (prec == 2) LAUNCH_RG(TA, TB, 2);                               \
-    else if (prec == 3) LAUNCH_RG(TA, TB, 3);                          \
-    else LAUNCH_RG(TA, TB, 4);                                         \
   }
-    if (s.ta == 64 && s.tb == 64) LAUNCH_RG_P(64, 64)
-    else if (s.ta == 64) LAUNCH_RG_P(64, 32)
-    else if (s.tb == 64) LAUNCH_RG_P(32, 64)
-    else LAUNCH_RG_P(32, 32)
-#undef LAUNCH_RG_P
-#undef LAUNCH_RG
+  if (s.path != GCL_DW_PATH_NONE) {
+    const dim3 grid = s.path == GCL_DW_PATH_RG ? dim3((unsigned)(cdiv(s.nr, 8) * 8 * K))
+                      : s.stiles               ? dim3((unsigned)(cdiv(W, 8) * 8 * s.stiles))
+                                               : dim3(W, (ca / s.ta) * (cb / s.tb));
+    // the template fan-out over the channel tile (s.ta, s.tb) and the arithmetic: L(TA, TB, [PL, PRE,] [RG])
+#define FAN_TILE(L, ...)                                                                                            \
+  do {                                                                                                              \
+    if (s.ta == 64 && s.tb == 64) L(64, 64, ##__VA_ARGS__); else if (s.ta == 64) L(64, 32, ##__VA_ARGS__);          \
+    else if (s.tb == 64) L(32, 64, ##__VA_ARGS__); else L(32, 32, ##__VA_ARGS__);                                   \
+  } while (0)
+#define FAN_PREC(TA, TB, RGV)                                                                                       \
+  do {                                                                                                              \
+    if (prec == 2) LAUNCH_SPLIT(TA, TB, 2, false, RGV); else if (prec == 3) LAUNCH_SPLIT(TA, TB, 3, false, RGV);    \
+    else LAUNCH_SPLIT(TA, TB, 4, false, RGV);                                                                       \
+  } while (0)
+#define DW(KERNEL, ...) \
+  hipLaunchKernelGGL((KERNEL), grid, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, ca, cb, nc, per, scratch, ##__VA_ARGS__)
+#define LAUNCH_F32(TA, TB) DW((k_conv_bwd_weight<TA, TB>))
+#define LAUNCH_SPLIT(TA, TB, PLV, PREV, RGV) \
+  DW((k_conv_bwd_weight_split<TA, TB, PLV, PREV, RGV>), a_amax, b_amax, W, s.stiles, a_bytes, b_bytes, bounds, s.nr)
+    switch (s.path) {
+      case GCL_DW_PATH_RG: FAN_TILE(FAN_PREC, true); break;
+      case GCL_DW_PATH_WG128: DW(k_conv_bwd_weight_wg128<false>, a_amax, b_amax, W, s.stiles, a_bytes, b_bytes); break;
+      case GCL_DW_PATH_F32: FAN_TILE(LAUNCH_F32); break;
+      case GCL_DW_PATH_SPLIT: FAN_TILE(FAN_PREC, false); break;
+      case GCL_DW_PATH_PLANES: FAN_TILE(LAUNCH_SPLIT, 4, true, false); break;
+      default: GCL_CHECK_ARG(false, "gcl_conv_bwd_weight: launch shape without a kernel (path %d)", s.path);
+    }
+#undef LAUNCH_SPLIT
+#undef LAUNCH_F32
+#undef DW
+#undef FAN_PREC
+#undef FAN_TILE
+  }
+  if (s.path == GCL_DW_PATH_RG)
     hipLaunchKernelGGL(k_bwd_weight_reduce_rg, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st, (const float*)scratch,
-                       nr, K, mat, dw);
-    GCL_CHECK_LAUNCH();
-    return GCL_OK;
-  }
-  if (s.path == GCL_DW_PATH_WG128) {
-    const int tiles = (ca / 128) * (cb / 128);
-    const dim3 g2 = s.stiles ? dim3((unsigned)(cdiv(W, 8) * 8 * s.stiles)) : dim3(W, tiles);
-    hipLaunchKernelGGL((k_conv_bwd_weight_wg128<false>), g2, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, ca, cb, nc, per,
-                       scratch, a_amax, b_amax, W, s.stiles, a_bytes, b_bytes);
-  } else if (s.path != GCL_DW_PATH_NONE) {
-    const int stiles = s.stiles;
-    dim3 grid(W, (ca / s.ta) * (cb / s.tb));
-    dim3 sgrid = stiles ? dim3((unsigned)(cdiv(W, 8) * 8 * stiles)) : grid;
-#define LAUNCH_BWS(TA, TB, PLV)                                                                                     \
-  hipLaunchKernelGGL((k_conv_bwd_weight_split<TA, TB, PLV>), sgrid, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, \
-                     ca, cb, nc, per, scratch, a_amax, b_amax, W, stiles, a_bytes, b_bytes)
-#define LAUNCH_BW(TA, TB)                                                                                          \
-  {                                                                                                                \
-    if (s.path == GCL_DW_PATH_F32)                                                                                 \
-      hipLaunchKernelGGL((k_conv_bwd_weight<TA, TB>), grid, dim3(256), 0, st, a, b, pair_a, pair_b, seg, K, ca, cb, \
-                         nc, per, scratch);                                                                        \
-    else if (prec == 2) LAUNCH_BWS(TA, TB, 2);                                                                     \
-    else if (prec == 3) LAUNCH_BWS(TA, TB, 3);                                                                     \
-    else if (s.path == GCL_DW_PATH_PLANES)                                                                         \
-      hipLaunchKernelGGL((k_conv_bwd_weight_split<TA, TB, 4, true>), sgrid, dim3(256), 0, st, a, b, pair_a, pair_b, \
-                         seg, K, ca, cb, nc, per, scratch, a_amax, b_amax, W, stiles, a_bytes, b_bytes);           \
-    else LAUNCH_BWS(TA, TB, 4);                                                                                    \
-  }
-    if (s.ta == 64 && s.tb == 64) LAUNCH_BW(64, 64)
-    else if (s.ta == 64) LAUNCH_BW(64, 32)
-    else if (s.tb == 64) LAUNCH_BW(32, 64)
-    else LAUNCH_BW(32, 32)
-#undef LAUNCH_BW
-#undef LAUNCH_BWS
-  }
-  hipLaunchKernelGGL(k_bwd_weight_reduce<float>, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st, (const float*)scratch,
-                     seg, per, mat, dw);
+                       s.nr, K, mat, dw);
+  else
+    hipLaunchKernelGGL(k_bwd_weight_reduce<float>, dim3((unsigned)cdiv(mat, 256), K), dim3(256), 0, st,
+                       (const float*)scratch, seg, per, mat, dw);
   GCL_CHECK_LAUNCH();
   return GCL_OK;
 }
